@@ -3,12 +3,13 @@
 (BASELINE.json configs[1]; with N GPUs: N*1024 spp sharded by samples + one RCCL film reduction,
 configs[2] at N=8).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A "step" is one complete transient render on every rank: film clear, the path kernel(s) over
 rank's sample slice of all 512^2 pixels, (N>1) reduce-scatter of the raw (H,W,T,4) film over
 RCCL + all-gather of the developed tensor, develop.  Scene, BVH and film live in HBM before the
-timed region starts.  Rank 0 prints ONE JSON line.
+timed region starts.  Rank 0 prints ONE JSON line.  --dump-outputs DIR: rank 0 also writes the (steady, transient) tensors the
+last timed step returned to DIR (see dump_outputs); the inputs are seeded, identical from run to run.
 """
 from __future__ import annotations
 
@@ -26,6 +27,7 @@ SPLAT_BYTES = 24.0         # algorithmic bytes per issued time-bin contribution 
 # f32 vector (VALU) roof: 256 CUs x 4 SIMD-32 x 2.4 GHz = 78.6e12 lane-operations/s (one v_fma_f32 of a wave64 occupies its
 # SIMD for 2 cycles; x2 flops per fma = the 157.3 TFLOP/s vector peak of MI355X_MICROARCH.md)
 VALU_PEAK_TLANEOPS = 256 * 4 * 32 * 2.4e9 / 1e12
+DUMP_BYTES = 48 * 2 ** 20  # --dump-outputs: array bytes written in all (the .npy files stay under 64 MB)
 
 
 def source_hash():
@@ -135,6 +137,34 @@ def cpu_baseline(width, height, bins, spp_total, target_s=15.0):
                       f"intersection, OpenMP {cores} threads, film pre-faulted)",
             "note": "the build's own scalar C restatement (libm, one lane at a time, no SIMD packets): NOT Mitsuba's Embree / "
                     "Dr.Jit-LLVM path, which is not installable here; the GPU/CPU ratio says little about kernel quality"}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: writes the tensors of `arrays` ({name: torch tensor}) as out_dir/<name>.npy, float64 kept, everything else
+    as float32, smallest first.  An array that no longer fits whole in what is left of DUMP_BYTES (the (H,W,T,C) transient of
+    the default workload is 3 GiB) is written as a fixed sample of its pixels: as many of the H*W positions of its first two
+    axes as fit, drawn without replacement by numpy.random.default_rng(0), in row-major order, each with all its other axes.
+    Returns {name: shape written}."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    left, shapes = DUMP_BYTES, {}
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel()):
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        item = 8 if dt == torch.float64 else 4
+        if t.numel() * item <= left:
+            a = t.detach().to(dt).cpu().numpy()
+        else:
+            h, w = t.shape[0], t.shape[1]
+            k = min(h * w, left // (t[0, 0].numel() * item))
+            if k == 0:
+                raise SystemExit(f"--dump-outputs: not one pixel of '{name}' {tuple(t.shape)} fits in the {DUMP_BYTES} bytes")
+            px = torch.from_numpy(np.sort(np.random.default_rng(0).choice(h * w, size=k, replace=False))).to(t.device)
+            a = t.detach()[px // w, px % w].to(dt).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 _TRAFFIC = None
@@ -447,7 +477,14 @@ def main():
                     help="N > 1: time ONLY the communication of a step (reduce-scatter + all-gather of a film-sized tensor in 8 row "
                          "bands + the steady all-reduce, no path kernel) and print that as the line's value; without the flag the same "
                          "measurement rides along as `comm_only`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the steady and transient tensors the last timed step returned as DIR/<name>.npy "
+                         "(float32; a fixed sample of the transient's pixels when the whole would exceed 48 MiB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.comm_only:
+        ap.error("--dump-outputs needs the render: --comm-only times no path kernel")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
     global SCENE, MATERIALS
@@ -472,7 +509,10 @@ def main():
     device_index = int(os.environ.get("MTR_BENCH_DEVICE", local_rank))
     backend = os.environ.get("MTR_BENCH_BACKEND", "nccl")
     torch.cuda.set_device(device_index)
-    if world > 1:
+    # under a launcher the process group exists whatever N: with one rank it issues no collective, but the RCCL set-up
+    # below runs on a one-GPU box too
+    grouped = world > 1 or "WORLD_SIZE" in os.environ
+    if grouped:
         if backend == "nccl":
             # RCCL's kernels on a HIGH-PRIORITY stream: k_fused is persistent and fills every CU's LDS, so the film
             # reduction of band b can only get onto the chip at the boundary between the kernels of bands b and b+1 —
@@ -503,9 +543,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_run(renderer):
+    dumped = None
+
+    def timed_run(renderer, dump_dir=None):
         """W untimed + K timed steps of `renderer`, fenced on both sides; returns (elapsed s = max over ranks, counters summed
-        over ranks, per-step kernel ms of this rank, launches, wavefront seen, sums of this rank's per-kernel HIP-event times)"""
+        over ranks, per-step kernel ms of this rank, launches, wavefront seen, sums of this rank's per-kernel HIP-event times).
+        `dump_dir`: rank 0 writes what the last timed step returned there, after the clock has stopped"""
+        nonlocal dumped
         totals = {"paths": 0, "rays_closest": 0, "rays_shadow": 0, "splats_issued": 0, "bounces": 0}
         kernel_ms, launches, wf_seen = [], 0, False
         wf = {"wf_trace_ms": 0.0, "wf_trace_kernel_launches": 0, "wf_shade_ms": 0.0, "scatter_ms": 0.0, "scatter_launches": 0}
@@ -530,6 +574,8 @@ def main():
                 wf[k] += integ.total_times.get(k, 0)
         fence()
         elapsed = time.perf_counter() - t0
+        if dump_dir and rank == 0:
+            dumped = dump_outputs(dump_dir, {"steady": out[0].torch(), "transient": out[1].torch()})
         del out
         rank_totals = dict(totals)
         if world > 1:
@@ -595,7 +641,7 @@ def main():
         return
 
     renderer = mdist.DistributedRenderer(scene, partition="spp", gather=True)
-    elapsed, totals, kernel_ms, trace_launches, wf_seen, wf_t = timed_run(renderer)
+    elapsed, totals, kernel_ms, trace_launches, wf_seen, wf_t = timed_run(renderer, args.dump_outputs)
     wft_ms, wft_n, wfs_ms, wsc_ms, wsc_n = (wf_t["wf_trace_ms"], wf_t["wf_trace_kernel_launches"], wf_t["wf_shade_ms"], wf_t["scatter_ms"],
                                             wf_t["scatter_launches"])
     totals_rank0 = wf_t["rank_totals"]
@@ -758,9 +804,10 @@ def main():
                 res["roofline_stale"] = True      # profiles/traffic.json was collected from other sources: counter-based lines omitted
         if not fused and wft_n:
             res["k_wf_trace_ms_per_step"] = wft_ms / args.steps
-        if world > 1:
+        if grouped:
             res["rccl_ranks"] = dist.get_world_size() if backend == "nccl" else 0
             res["comm_backend"] = backend
+        if world > 1:
             res["render_path"] = path_taken
             res["reduce_scatter_only"] = rs_only
             res["row_sharded"] = rows_leg
@@ -776,11 +823,13 @@ def main():
             res["extra_configs"] = extra
         if splat_mb:
             res["splat_microbench"] = splat_mb
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         if cpu_res is not None:
             res["cpu_baseline"] = cpu_res
             res["gpu_over_cpu"] = res["value"] / cpu_res["value"]
         print(json.dumps(res))
-    if world > 1:
+    if grouped:
         dist.destroy_process_group()
 
 

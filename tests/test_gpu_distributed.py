@@ -248,7 +248,12 @@ def test_two_rank_reduce_scatter_only(tmp_path):
     assert seen.all()
 
 
-def _worker8(rank, world, port, tmp, partition, gather, single, bands):
+# ranks that share the one GPU: with this test process that makes five processes holding the device, under the six
+# that may hold it at once
+SHARED_RANKS = 4
+
+
+def _worker_shared(rank, world, port, tmp, partition, gather, single, bands):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -260,7 +265,7 @@ def _worker8(rank, world, port, tmp, partition, gather, single, bands):
         from mitransient_amd import distributed as md
         scene = make_cornell(width=64, height=64, bins=64)
         r = md.DistributedRenderer(scene, partition=partition, gather=gather, bands=bands, single_launch=single)
-        steady, transient = r.render(spp=20, seed=3)          # 20 samples over 8 ranks: shards of 3 and 2
+        steady, transient = r.render(spp=18, seed=3)          # 18 samples over 4 ranks: shards of 5 and 4
         torch.cuda.synchronize()
         np.save(os.path.join(tmp, f"t{rank}.npy"), np.array(transient))
         np.save(os.path.join(tmp, f"s{rank}.npy"), np.array(steady))
@@ -272,18 +277,19 @@ def _worker8(rank, world, port, tmp, partition, gather, single, bands):
 
 @pytest.mark.parametrize("partition,gather,single", [("spp", True, False), ("spp", False, True), ("spp", True, True), ("spp", False, False),
                                                      ("rows", True, False), ("rows", False, False)])
-def test_eight_ranks_on_one_gpu(tmp_path, partition, gather, single):
-    """WORLD SIZE 8 (the node the 1/2/4/8 curve is measured on) through DistributedRenderer on this box's one GPU, gloo instead of
-    RCCL: 64 rows = 8 bands x 8 ranks x 1 row, 20 samples in shards of 3 and 2, both partitions, with and without the final
-    all-gather, per-band launches and the single launch with band completion words — the first 8-rank execution of this code
-    should not be the driver's"""
+def test_four_ranks_on_one_gpu(tmp_path, partition, gather, single):
+    """WORLD SIZE 4 through DistributedRenderer on this box's one GPU, gloo instead of RCCL: 64 rows = 8 bands x 4 ranks x 2 rows,
+    18 samples in shards of 5 and 4, both partitions, with and without the final all-gather, per-band launches and the single
+    launch with band completion words — the first multi-rank execution of this code should not be the driver's (world size 8
+    runs on CPU: test_distributed_cpu.py::test_gloo_spp_shard_reduce[8])"""
     from conftest import make_cornell, rel_l2
+    world = SHARED_RANKS
     scene = make_cornell(width=64, height=64, bins=64)
-    s_ref, t_ref = scene.integrator().render(scene, seed=3, spp=20)
+    s_ref, t_ref = scene.integrator().render(scene, seed=3, spp=18)
     s_ref, t_ref = np.array(s_ref), np.array(t_ref)
-    mp.spawn(_worker8, args=(8, _free_port(), str(tmp_path), partition, gather, single, 8), nprocs=8, join=True)
+    mp.spawn(_worker_shared, args=(world, _free_port(), str(tmp_path), partition, gather, single, 8), nprocs=world, join=True)
     seen = np.zeros(64, bool)
-    for r in range(8):
+    for r in range(world):
         t = np.load(tmp_path / f"t{r}.npy")
         s = np.load(tmp_path / f"s{r}.npy")
         info = (tmp_path / f"info{r}.txt").read_text().split()
@@ -294,29 +300,30 @@ def test_eight_ranks_on_one_gpu(tmp_path, partition, gather, single):
             assert t.shape == t_ref.shape and rel_l2(t, t_ref) <= 1e-6 and rel_l2(s, s_ref) <= 1e-6
         else:
             rows = np.array([int(x) for x in info[3:]])
-            assert len(rows) == 8 == t.shape[0] and not seen[rows].any()
+            assert len(rows) == 64 // world == t.shape[0] and not seen[rows].any()
             seen[rows] = True
             assert rel_l2(t, t_ref[rows]) <= 1e-6 and rel_l2(s, s_ref[rows]) <= 1e-6
     assert gather or seen.all()
 
 
-def test_bench_with_eight_ranks_dry_run():
-    """`python bench.py --gpus 8` in the dry-run form (every rank on this GPU, gloo): one JSON line, weak scaling, 17 collectives"""
+def test_bench_with_four_ranks_dry_run():
+    """`python bench.py --gpus 4` in the dry-run form (every rank on this GPU, gloo): one JSON line, weak scaling, 17 collectives"""
     res = _bench_line({"MTR_BENCH_BACKEND": "gloo", "MTR_BENCH_DEVICE": "0", "OMP_NUM_THREADS": "1"},
-                      ["--gpus", "8", "--steps", "2", "--warmup", "1", "--spp", "8", "--width", "128", "--height", "128", "--bins", "128", "--no-cpu-baseline"], timeout=900)
-    assert res["n_gpus"] == 8 and res["comm_backend"] == "gloo" and res["scaling"] == "weak"
-    assert res["counters_per_step"]["paths"] == 128 * 128 * 8 * 8
+                      ["--gpus", str(SHARED_RANKS), "--steps", "2", "--warmup", "1", "--spp", "8", "--width", "128", "--height", "128", "--bins", "128",
+                       "--no-cpu-baseline"], timeout=900)
+    assert res["n_gpus"] == SHARED_RANKS and res["comm_backend"] == "gloo" and res["scaling"] == "weak"
+    assert res["counters_per_step"]["paths"] == 128 * 128 * 8 * SHARED_RANKS
     assert res["render_path"] == "pipelined" and res["collectives_per_step"] == 17
     assert res["row_sharded"]["path"] == "rows" and res["value"] > 0
 
 
-def _bench_line(env_extra, args, timeout=600):
+def _bench_line(env_extra, args, timeout=600, launcher=()):
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(env_extra)
-    r = subprocess.run([sys.executable, "bench.py"] + args, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                       text=True, timeout=timeout)
+    r = subprocess.run([sys.executable] + list(launcher) + ["bench.py"] + args, cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=timeout)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]              # rank 0 prints ONE JSON line
@@ -348,6 +355,25 @@ def test_bench_comm_only_line():
     res = _bench_line({"MTR_BENCH_BACKEND": "gloo", "MTR_BENCH_DEVICE": "0"}, ["--gpus", "2", "--comm-only"] + BENCH_SMALL)
     assert res["n_gpus"] == 2 and res["unit"] == "ms" and res["higher_is_better"] is False
     assert res["value"] == res["comm_only"]["ms_per_step"] > 0 and res["comm_only_reduce_scatter"]["ms_per_step"] > 0
+
+
+def test_bench_dump_outputs_are_the_last_steps_result(tmp_path):
+    """`bench.py --dump-outputs DIR`: the steady image whole and, since the whole transient (48 MiB here) does not fit beside it,
+    the fixed sample of its pixels — both equal to the same render done directly"""
+    from conftest import make_cornell, rel_l2
+    res = _bench_line({}, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--spp", "8", "--width", "128", "--height", "128", "--bins", "256",
+                           "--no-cpu-baseline", "--no-scatter-leg", "--no-extra-configs", "--dump-outputs", str(tmp_path)])
+    assert res["steps"] == 3 and res["counters_per_step"]["paths"] == 128 * 128 * 8
+    steady, transient = np.load(tmp_path / "steady.npy"), np.load(tmp_path / "transient.npy")
+    assert steady.dtype == transient.dtype == np.float32 and steady.shape == (128, 128, 3)
+    assert res["dumped_outputs"] == {"steady": [128, 128, 3], "transient": list(transient.shape)}
+    assert 1000 < transient.shape[0] < 128 * 128 and transient.shape[1:] == (256, 3)
+    assert steady.nbytes + transient.nbytes <= 48 * 2 ** 20
+    scene = make_cornell(width=128, height=128, bins=256, max_depth=8)
+    s_ref, t_ref = scene.integrator().render(scene, seed=0, spp=8)
+    s_ref, t_ref = np.array(s_ref), np.array(t_ref)
+    px = np.sort(np.random.default_rng(0).choice(128 * 128, size=transient.shape[0], replace=False))
+    assert rel_l2(steady, s_ref) <= 1e-6 and rel_l2(transient, t_ref[px // 128, px % 128]) <= 1e-6
 
 
 def test_reserved_compute_units_change_nothing_but_the_grid():
@@ -394,8 +420,14 @@ def test_bench_under_torchrun_matches_the_contract():
 
 
 def test_bench_two_ranks_over_rccl():
-    """... and over RCCL proper wherever two GPUs are visible (skips on the one-GPU box)"""
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs >= 2 GPUs")
-    res = _bench_line({}, ["--gpus", "2"] + BENCH_SMALL)
-    assert res["n_gpus"] == 2 and res["rccl_ranks"] == 2 and res["comm_backend"] == "nccl" and res["render_path"] == "pipelined"
+    """... and over RCCL proper: two ranks wherever two GPUs are visible.  RCCL refuses two ranks on one device, so a one-GPU
+    box launches the one rank it can hold (torch.distributed.run --nproc-per-node 1): bench.py's own RCCL process group —
+    high-priority stream, device_id — is created and torn down around the render"""
+    if torch.cuda.device_count() >= 2:
+        res = _bench_line({}, ["--gpus", "2"] + BENCH_SMALL)
+        assert res["n_gpus"] == 2 and res["rccl_ranks"] == 2 and res["comm_backend"] == "nccl" and res["render_path"] == "pipelined"
+        return
+    res = _bench_line({}, ["--gpus", "1", "--no-scatter-leg", "--no-extra-configs"] + BENCH_SMALL, launcher=["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
+                                                                   "--master-addr", "127.0.0.1", "--master-port", str(_free_port())])
+    assert res["n_gpus"] == 1 and res["rccl_ranks"] == 1 and res["comm_backend"] == "nccl"
+    assert res["counters_per_step"]["paths"] == 128 * 128 * 8 and res["value"] > 0

@@ -215,13 +215,15 @@ def test_camera_nlos_three_bounce_arrival(oracle):
     assert prof.sum() > 0 and not np.isnan(prof).any()
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference/examples/transient-nlos"), reason="reference examples not present")
 def test_reference_nlos_xml_scenes(oracle, host_harness):
+    """the reference's examples/transient-nlos XML scenes and their PLY meshes (fixtures under tests/golden/reference_scenes)"""
+    import os
     import mitransient_amd.mi as mi
+    scenes = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_scenes", "transient-nlos")
     mi.set_variant("llvm_ad_mono")
     try:
         for name, n_tris in (("nlos-z-simple.xml", 8), ("nlos-z-room.xml", 18)):
-            sc = mi.load_file("/root/reference/examples/transient-nlos/" + name)
+            sc = mi.load_file(os.path.join(scenes, name))
             sd = sc.data()
             assert sd.tri_verts.shape[0] == n_tris and sc.integrator().laser_sampling and sc.integrator().hg_sampling
             p = sc.integrator().render_params(sc.sensors()[0].film(), 0, 32)

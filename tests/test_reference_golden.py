@@ -1,8 +1,9 @@
 """Parity against the REAL reference.
 
 `tests/golden/mitsuba_c1.npz` is written by tools/gen_golden_with_mitsuba.py on a machine that has mitsuba + mitransient;
-it is absent so far (PARITY UNPINNED), so the two reference tests skip.  The decision procedure itself is exercised on
-synthetic files made from the oracle (test_pin_procedure_on_synthetic_goldens), so that the day a real file is dropped in
+it is absent so far (PARITY UNPINNED), so the oracle's reference tests skip and the HIP path's runs against a file the oracle
+writes.  The decision procedure itself is exercised on synthetic files made from the oracle (test_pin_procedure_on_synthetic_goldens,
+test_hip_path_against_reference_render), so that the day a real file is dropped in
 it answers, without a code change:
   1. which PCG32 seeding Mitsuba's independent sampler uses (TEA only / TEA + lane offset on initseq — SURVEY A.9 — / the
      64-bit sample_tea_64 words, MTR_FLAG_PCG_TEA64): the variant whose 16-spp render reproduces the file's exact cells;
@@ -151,10 +152,11 @@ def test_oracle_rough_lobes_against_reference_render(oracle):
     assert v["exact_seeding"] is not None or v["statistical"], v
 
 
-@needs_gold
 @pytest.mark.gpu
-def test_hip_path_against_reference_render():
-    g = np.load(GOLD)
+def test_hip_path_against_reference_render(oracle):
+    """the HIP path through the pin procedure: against the Mitsuba file when there is one; until then against a file the CPU
+    oracle writes in the same format (pack_render, TEA seeding), which the HIP path must match as that seeding exactly and
+    statistically — so the GPU half of the procedure is known to work the day the real file is dropped in"""
     scene = make_cornell()
     integ, sens = scene.integrator(), scene.sensors()[0]
 
@@ -164,6 +166,19 @@ def test_hip_path_against_reference_render():
         integ.accumulate(scene, sens, passes, spp, spp_range=spp_range)
         s, t = sens.film().develop()
         return np.array(s), np.array(t)
+    if os.path.exists(GOLD):
+        g = np.load(GOLD)
+        v = classify(g, render)
+        print("HIP path vs", list(g["versions"]), "->", v)
+        assert v["exact_seeding"] is not None or v["statistical"], v
+        return
+    from gen_golden_with_mitsuba import pack_render
+    oracle_render = _oracle_render(oracle, make_cornell())
+    g = {}
+    for prefix, spp, seed in (("lo", 16, 0), ("hi", 256, 1)):
+        s3, t3 = oracle_render(spp, seed, "tea", None)
+        g.update(pack_render(prefix, s3, t3))
+        g[f"{prefix}_spp_seed"] = np.asarray([spp, seed])
     v = classify(g, render)
-    print("HIP path vs", list(g["versions"]), "->", v)
-    assert v["exact_seeding"] is not None or v["statistical"], v
+    print("HIP path vs the oracle's file ->", v)
+    assert v["exact_seeding"] == "tea" and v["statistical"], v

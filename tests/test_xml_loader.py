@@ -8,8 +8,8 @@ import pytest
 
 from conftest import hh_render
 
-REF = "/root/reference/examples"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+REF = os.path.join(GOLDEN, "reference_scenes")       # XML scenes and meshes of the reference's examples/ (data fixtures)
 
 XML = """<scene version="3.3.0">
     <default name="spp" value="8"/>
@@ -239,8 +239,27 @@ def test_staircase_fixture_product_equals_oracle(oracle, host_harness):
     assert cnt["bounces"] > 4 * cnt["paths"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference examples not present (GPU box)")
-def test_reference_xml_files_load_and_match_fixtures():
+def _staircase_with_stand_in_assets(tmp_path):
+    """the reference's diff-transient/staircase/scene.xml as it is (fixture), beside one-triangle stand-ins (positions, uv,
+    vertex normals) for its 774 OBJ meshes and 4 x 4 stand-ins for its JPEG textures: the 34 MB of real assets are not kept"""
+    import gzip
+    import re
+    from PIL import Image
+    xml = gzip.decompress(open(os.path.join(REF, "diff-transient", "staircase", "scene.xml.gz"), "rb").read()).decode()
+    (tmp_path / "scene.xml").write_text(xml)
+    tri = "v 0 0 0\nv 1 0 0\nv 0 1 0\nvt 0 0\nvt 1 0\nvt 0 1\nvn 0 0 1\nvn 0 0 1\nvn 0 0 1\nf 1/1/1 2/2/2 3/3/3\n"
+    files = set(re.findall(r'name="filename" value="([^"]+)"', xml))
+    assert len([f for f in files if f.endswith(".obj")]) == 774
+    for i, f in enumerate(sorted(files)):
+        (tmp_path / f).parent.mkdir(parents=True, exist_ok=True)
+        if f.endswith(".obj"):
+            (tmp_path / f).write_text(tri)
+        else:
+            Image.new("RGB", (4, 4), (20 * i % 256, 128, 200)).save(tmp_path / f)
+    return str(tmp_path / "scene.xml")
+
+
+def test_reference_xml_files_load_and_match_fixtures(tmp_path):
     import mitransient_amd.mi as mi
     from mitransient_amd.scenes import from_fixture
     mi.set_variant("llvm_ad_rgb")
@@ -254,7 +273,7 @@ def test_reference_xml_files_load_and_match_fixtures():
         assert a.integrator().max_depth == b.integrator().max_depth
     # the staircase loads as it is: GGX lobes, vertex normals, nine bitmap textures on (diffuse) reflectances; its one bumpmap
     # wraps a BSDF that the shapes reference directly by id, so the wrapper is never instantiated (in mitsuba neither)
-    st = mi.load_file(f"{REF}/diff-transient/staircase/scene.xml", resx=8, resy=8).data()
+    st = mi.load_file(_staircase_with_stand_in_assets(tmp_path), resx=8, resy=8).data()
     kinds = sorted(st.materials[i].type for i in range(st.n_materials))
     assert (kinds.count(5), kinds.count(4), len(st.textures)) == (6, 2, 9)
     assert sum(1 for i in range(st.n_materials) if st.materials[i].albedo_texture) == 9
