@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 12
+#define MTR_ABI_VERSION 13
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -104,6 +104,13 @@ typedef struct mtr_emitter {
     uint32_t flip_normals; /* rectangle (ABI 9): the shape's `flip_normals` — the emitting side is -normalize(du x dv);
                               sample positions are unchanged (mitsuba negates the normal, not the parameterisation).
                               A mesh emitter's flip is the winding of its triangles. */
+    /* ABI 13: mitransient's `angulararea` emitter (mitransient/emitters/angulararea.py) on the same shapes.  All zero: a plain `area`
+       emitter.  The constants are the f32 values AngularAreaLight.__init__ derives (:55-72), computed by the caller. */
+    uint32_t angular;      /* 1: radiance is scaled by the falloff of the angle to the shading normal (_fallof_curve, :74-82)      */
+    float cutoff;          /* deg2rad(cutoff_angle) (:58-59), default 10 degrees                                                   */
+    float cos_cutoff;      /* cos(cutoff) (:68)                                                                                     */
+    float cos_beam;        /* cos(deg2rad(beam_width)) (:60-61, :69), beam_width defaults to cutoff_angle                          */
+    float inv_transition;  /* 1 / (cutoff - beam), +inf when they are equal (:62-66)                                               */
 } mtr_emitter;
 
 /* ---- sensor: `perspective` (utils.py:92-105 of the reference) ----------- */
@@ -354,7 +361,7 @@ int  mtr_scene_bvh_info(const mtr_scene *, uint32_t *n_nodes, uint32_t *max_dept
 /* Which specialised kernels the scene's tables select (for tests and tools; no counterpart in the reference, whose tracing
  * JIT specialises on the scene implicitly): MTR_TRAIT_* bits. */
 #define MTR_TRAIT_DIFFUSE          1u   /* every material plain one-sided diffuse */
-#define MTR_TRAIT_ONE_RECT_EMITTER 2u   /* exactly one emitter, an analytic rectangle */
+#define MTR_TRAIT_ONE_RECT_EMITTER 2u   /* exactly one emitter, an analytic rectangle (`area`, not `angulararea`) */
 #define MTR_TRAIT_LEAF_PAIR        4u   /* no leaf of the LDS-staged tree beyond one triangle pair */
 #define MTR_TRAIT_FLAT_TOP         8u   /* top level = rectangles, triangle leaves and box nodes: the fused kernel does not walk a tree */
 #define MTR_TRAIT_FLAT_LEAVES     16u   /* ... and there are triangle leaves among them */

@@ -232,7 +232,7 @@ int mtr_scene_create(mtr_ctx *c, const mtr_scene_desc *d, mtr_scene **out)
         for (uint32_t i = 0; i < d->n_materials; ++i)
             if (d->materials[i].type != MTR_BSDF_DIFFUSE || (d->materials[i].flags & MTR_MAT_TWOSIDED)) diffuse_only = false;
         if (diffuse_only) s->dev.traits |= kTrDiffuse;
-        if (d->n_emitters == 1 && !hs.ems[0].is_mesh) s->dev.traits |= kTrOneRectEmitter;
+        if (d->n_emitters == 1 && !hs.ems[0].is_mesh && !hs.ems[0].angular) s->dev.traits |= kTrOneRectEmitter;     // (its kernels have no falloff code)
         bool leaf_pairs = hs.has_wide;
         for (const WNode &n : hs.wnodes)
             for (uint32_t k = 0; k < n.count; ++k) {

@@ -133,6 +133,25 @@ MTR_HD void sincos_quarter(float x, float &s, float &c)   // |x| <= pi/4
     float pc = fmaf(fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f);
     c = fmaf(z * z, pc, fmaf(-0.5f, z, 1.0f));
 }
+// acos on [-1, 1] in f32, the same operations on host and device (Dr.Jit's own acos is not reproducible bit for bit either):
+// asin(x) = x + x z P(z), z = x^2, on |x| <= 1/2 (the Cephes asinf minimax polynomial); acos(x) = pi/2 - asin(x) there, and
+// 2 asin(sqrt((1 - x) / 2)), pi - 2 asin(sqrt((1 + x) / 2)) outside it (1 -+ x and the halving are exact for |x| >= 1/2).
+// pi and pi/2 as two-term sums.  tests/test_angular_emitter.py bounds the error against f64 acos.
+MTR_HD float asin_half(float x)          // |x| <= 1/2
+{
+    const float z = x * x;
+    const float p = fmaf(fmaf(fmaf(fmaf(4.2163199048e-2f, z, 2.4181311049e-2f), z, 4.5470025998e-2f), z, 7.4953002686e-2f), z,
+                         1.6666752422e-1f);
+    return fmaf(x * z, p, x);
+}
+MTR_HD float acos_f32(float x)
+{
+    const float ax = fabsf(x);
+    if (ax <= 0.5f) return 1.5707963705062866f - (asin_half(x) + 4.371139000186243e-08f);          // pi/2 = hi - lo
+    const float s = 2.0f * asin_half(sqrtf(0.5f * (1.0f - ax)));
+    return x > 0.0f ? s : (3.1415927410125732f - s) - 8.742278000372475e-08f;                      // pi = hi - lo
+}
+
 // One frequency of a phasor-film contribution (phasor_image_block.py:49-56): phase = fmod(-2 pi f opl, 2 pi) with
 // fmod(x, y) = x - y * floor(x / y), all f32; cos / sin by reduction to a multiple of pi/2 (two-constant Cody-Waite)
 // and the quarter-range polynomials above (numerics contract; Dr.Jit's own sincos is not reproducible bit for bit).
@@ -315,10 +334,17 @@ constexpr uint32_t kLeafQuadBit = 0x40000000u;      // in the leaf code ~ref = (
 struct alignas(16) TriShade { q4 h[MTR_TSHADE_QUADS]; };
 constexpr uint32_t kShadeQuadBit = 0x80000000u;
 constexpr uint32_t kShadeSmoothBit = 0x40000000u;
-struct alignas(16) Emitter {                       // 80 B
+struct alignas(16) Emitter {                       // 96 B
     float center[3], du[3], dv[3], n[3], radiance[3], inv_area;       // rectangle: analytic sampling
-    uint32_t is_mesh, first_tri, n_tris, pad;                          // mesh: triangle range (ORIGINAL indices)
+    uint32_t is_mesh, first_tri, n_tris, angular;                      // mesh: triangle range (ORIGINAL indices); angular: `angulararea`
+    float cutoff, cos_cutoff, cos_beam, inv_transition;                // angulararea.py:55-72 (mtr_emitter), read only when `angular`
 };
+// angulararea.py:74-82 _fallof_curve of a unit direction whose cosine to the emitter's shading normal is c
+MTR_HD float angular_falloff(const Emitter &E, float c)
+{
+    const float beam = (c >= E.cos_beam) ? 1.0f : (E.cutoff - acos_f32(c)) * E.inv_transition;
+    return (c > E.cos_cutoff) ? beam : 0.0f;
+}
 
 struct Camera {
     float s2c[16];
@@ -1709,7 +1735,7 @@ MTR_HD void rough_sample(const mtr_material &m, f3 albedo, f3 wi, float u1, floa
 //   kTrDiffuse: every material is MTR_BSDF_DIFFUSE without MTR_MAT_TWOSIDED (transientpath.py:157 `si.bsdf(ray)` has ONE
 //     target): no delta lobe, so prev_bsdf_delta (:240) is true exactly at depth 0; bs.eta == 1, so eta (:232) stays 1 and
 //     `distance += t * eta` (:154), `rr_prob = min(beta_max * eta^2, .95)` (:248) lose their factors; no Fresnel code at all.
-//   kTrOneRectEmitter: exactly one emitter, an analytic rectangle (:192 `sample_emitter_direction` has one target): no
+//   kTrOneRectEmitter: exactly one emitter, an analytic `area` rectangle (:192 `sample_emitter_direction` has one target): no
 //     emitter pick and its sample reuse, no mesh tables, no 1 / n_emitters factors.
 //   kTrLeafPair: no triangle leaf of the 8-wide tree holds more than two triangles (the builder's target size; object-space
 //     leaves never do): the leaf test is one packed pass without a loop around it.
@@ -1952,15 +1978,24 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
         float dist = sqrtf(dot(rel, rel));
         f3 dd = rel / dist;
         float em_pdf = 0.0f;
+        // angulararea (never in a kTrOneRectEmitter scene): eval scales the radiance by the falloff of si.wi (angulararea.py:94-102),
+        // pdf_direction is zero where the falloff of -ds.d is (:130-144)
+        const bool ang = !kOneRect && E.angular != 0u;
         if (!prev_delta) {
             float dp = dot(dd, c.sn);                  // DirectionSample(scene, si, ref): ds.n = si.sh_frame.n
-            if (dp < 0.0f) {
+            if (dp < 0.0f && (!ang || angular_falloff(E, -dp) > 0.0f)) {
                 float adp = fabsf(dp);
                 em_pdf = E.inv_area * (adp != 0.0f ? (dist * dist) / adp : 0.0f);
                 if (n_emitters > 1) em_pdf *= rc.inv_n_emitters;
             }
         }
         float mis = mis_weight(p.prev_pdf, em_pdf);
+        if (ang) {
+            const float fall = angular_falloff(E, c.wi.z);
+            if (c.wi.z > 0.0f && fall > 0.0f)
+                pd.Le = mk((p.beta.x * mis) * (E.radiance[0] * fall), (p.beta.y * mis) * (E.radiance[1] * fall),
+                           (p.beta.z * mis) * (E.radiance[2] * fall));
+        } else
         if (c.wi.z > 0.0f)
             pd.Le = mk((p.beta.x * mis) * E.radiance[0], (p.beta.y * mis) * E.radiance[1],
                        (p.beta.z * mis) * E.radiance[2]);
@@ -1998,8 +2033,14 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
         float dp = dot(dd, en), adp = fabsf(dp);
         float x = dist2 / adp;
         float pdf_dir = E.inv_area * ((fabsf(x) <= 3.402823466e+38f) ? x : 0.0f);
-        if ((dp < 0.0f) & (pdf_dir != 0.0f)) {
-            f3 emw = ld3(E.radiance) / pdf_dir;
+        // angulararea sample_direction (angulararea.py:107-128): falloff of -ds.d in Frame3f(ds.n), the term dropped where it is
+        // zero, and radiance * (falloff * inv_dist^2) / ds.pdf — the reference's extra 1 / dist^2 on top of the solid-angle pdf
+        const bool ang = !kOneRect && E.angular != 0u;
+        const float fall = ang ? angular_falloff(E, -dp) : 1.0f;
+        if ((dp < 0.0f) & (pdf_dir != 0.0f) & (fall > 0.0f)) {
+            f3 emw;
+            if (ang) { const float inv_dist = 1.0f / dist; emw = (ld3(E.radiance) * (fall * (inv_dist * inv_dist))) / pdf_dir; }
+            else emw = ld3(E.radiance) / pdf_dir;
             float pdf = pdf_dir;
             if (n_emitters > 1) { pdf = pdf_dir * rc.inv_n_emitters; emw = emw * rc.n_emitters_f; }
             if (pdf != 0.0f) {

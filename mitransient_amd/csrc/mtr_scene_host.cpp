@@ -302,7 +302,13 @@ const char *derive_scene(const mtr_scene_desc &d, HostScene &s)
     for (uint32_t i = 0; i < d.n_emitters; ++i) {
         const mtr_emitter &e = d.emitters[i];
         Emitter &E = s.ems[i];
-        E.is_mesh = e.is_mesh; E.first_tri = e.first_tri; E.n_tris = e.n_tris; E.pad = 0;
+        E.is_mesh = e.is_mesh; E.first_tri = e.first_tri; E.n_tris = e.n_tris;
+        E.angular = e.angular ? 1u : 0u;
+        E.cutoff = E.cos_cutoff = E.cos_beam = E.inv_transition = 0.0f;
+        if (e.angular) {      // angulararea.py:55-72: the caller derives the constants; cutoff >= beam (the assert of :71)
+            if (!(e.cutoff >= 0.0f) || !(e.cos_beam >= e.cos_cutoff) || !(e.inv_transition > 0.0f)) return "angular emitter: bad cutoff / beam";
+            E.cutoff = e.cutoff; E.cos_cutoff = e.cos_cutoff; E.cos_beam = e.cos_beam; E.inv_transition = e.inv_transition;
+        }
         if (e.is_mesh) {
             if (e.n_tris == 0 || (uint64_t)e.first_tri + e.n_tris > d.n_tris) return "mesh emitter: bad triangle range";
             if (s.samp_tris.empty()) {

@@ -159,6 +159,12 @@ class Scene:
         idict = integ[0]
         self.integrator_ = idict if isinstance(idict, TransientADIntegrator) else \
             plugins.create_integrator(idict["type"], Properties(idict["type"], idict))
+        from .integrators.transientnlospath import TransientNLOSPath
+        if isinstance(self.integrator_, TransientNLOSPath) and any(
+                isinstance(e, dict) and e.get("type") == "angulararea"
+                for v in flat.values() if isinstance(v, dict) for e in v.values()):
+            # transientnlospath.py:256-260: the NLOS integrator takes exactly one emitter, a projector
+            raise ValueError("transient_nlos_path: an angulararea emitter cannot light a NLOS scene (one projector is required)")
         for k, v in flat.items():
             if isinstance(v, dict) and v.get("type") == "perspective":
                 self.sensors_.append(_make_sensor(v))
@@ -170,8 +176,15 @@ class Scene:
         if not self.sensors_:
             raise ValueError("load_dict(): at least one sensor is required")
         self._data = {}
+        self._data_ver = {}
         self._handles = {}
         self._nlos_fp = {}
+
+    def _drop_handles(self, sensor_key):
+        lib = _cabi.load_library()
+        for k in [k for k in self._handles if k[0] == sensor_key]:
+            lib.mtr_scene_destroy(self._handles.pop(k))
+            self._nlos_fp.pop(k, None)
 
     def sensors(self):
         return self.sensors_
@@ -190,6 +203,11 @@ class Scene:
         if isinstance(sensor, int):
             sensor = self.sensors_[sensor]
         key = id(sensor)
+        ver = getattr(sensor, "version_", 0)
+        if key in self._data and self._data_ver.get(key, 0) != ver:      # the camera moved (params["sensor.to_world"]): re-flatten
+            del self._data[key]
+            self._drop_handles(key)
+        self._data_ver[key] = ver
         if key not in self._data:
             self._data[key] = flatten_scene(self.dict_, sensor.film(), sensor.dict_, self.base_dir,
                                             self.relay_names_.get(key), self.approximate_materials, self.geometry_)
@@ -305,7 +323,8 @@ class _Params(dict):
 
 
 def traverse(obj):
-    """``mi.traverse`` for the film parameters the reference exports (transient_hdr_film.py:295-308)."""
+    """``mi.traverse`` for the film parameters the reference exports (transient_hdr_film.py:295-308) and a perspective
+    sensor's ``to_world`` (settable: ``update()`` re-flattens the camera)."""
     objs = {}
 
     class _CB:
@@ -319,6 +338,8 @@ def traverse(obj):
     if isinstance(obj, Scene):
         for i, s in enumerate(obj.sensors()):
             targets.append((f"sensor{'' if i == 0 else i}.film.", s.film()))
+            if isinstance(s, PerspectiveSensor):
+                targets.append((f"sensor{'' if i == 0 else i}.", s))
     elif hasattr(obj, "film") and callable(obj.film):               # a sensor: its own keys + "film.*"
         targets.append(("", obj))
         targets.append(("film.", obj.film()))

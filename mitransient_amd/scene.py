@@ -158,6 +158,11 @@ class _SceneBuilder:
         self.base_dir = base_dir
         self.approx = approximate_materials
         self.mesh_cache: Dict[str, np.ndarray] = {}
+        # the NLOS tier: a transient_nlos_path integrator (dictionary or object) or a nlos_capture_meter on a shape
+        self.nlos = any((isinstance(v, dict) and (v.get("type") == "transient_nlos_path" or any(
+                            (isinstance(w, dict) and w.get("type") == "nlos_capture_meter") or type(w).__name__ == "NLOSCaptureMeter"
+                            for w in v.values())))
+                        or type(v).__name__ == "TransientNLOSPath" for v in d.values())
         self.tri_verts: List[np.ndarray] = []
         self.tri_mat: List[np.ndarray] = []
         self.tri_em: List[np.ndarray] = []
@@ -430,10 +435,15 @@ class _SceneBuilder:
         mi_ = self.material_index(bsdf)
         em_index = -1
         if em is not None:
-            if em.get("type") != "area":
-                raise ValueError(f"failed to instantiate unknown plugin of type \"{em.get('type')}\" (supported emitters: area)")
+            et = em.get("type")
+            if et not in ("area", "angulararea"):
+                raise ValueError(f"failed to instantiate unknown plugin of type \"{et}\" (supported emitters: area, angulararea)")
             e = _cabi.mtr_emitter()
-            rad = _color3(em.get("radiance", 1.0), "area.radiance")
+            rad = _color3(em.get("radiance", 1.0), f"{et}.radiance")
+            if et == "angulararea":
+                if self.nlos:      # transientnlospath.py:256-260: the NLOS tier takes exactly one emitter, a projector
+                    raise ValueError("transient_nlos_path: an angulararea emitter cannot light a NLOS scene (one projector is required)")
+                _angular_constants(e, em)
             if t == "rectangle":
                 c = tw.transform_affine(np.zeros(3))
                 du = tw.transform_affine(np.array([1.0, 0, 0])) - c
@@ -474,6 +484,23 @@ class _SceneBuilder:
             for k in range(3):
                 sh.center[k], sh.du[k], sh.dv[k] = np.float32(c[k]), np.float32(du[k]), np.float32(dv[k])
         self.shapes.append(sh)
+
+
+def _angular_constants(e, em: Dict[str, Any]):
+    """mitransient's AngularAreaLight.__init__ (emitters/angulararea.py:55-72): the angles in radians, the cosines and the
+    inverse transition width.  The plugin computes them on Python floats (f64) and they meet the f32 arrays of
+    _fallof_curve rounded to f32, which is what is stored here."""
+    cutoff_deg = float(em.get("cutoff_angle", 10.0))
+    beam_deg = float(em.get("beam_width", cutoff_deg))
+    cutoff, beam = math.radians(cutoff_deg), math.radians(beam_deg)
+    if not cutoff >= beam:                              # assert dr.all(self.cutoff_angle >= self.beam_width)
+        raise ValueError(f"angulararea: cutoff_angle ({cutoff_deg}) must not be smaller than beam_width ({beam_deg})")
+    diff = cutoff - beam
+    e.angular = 1
+    e.cutoff = np.float32(cutoff)
+    e.cos_cutoff = np.float32(math.cos(cutoff))
+    e.cos_beam = np.float32(math.cos(beam))
+    e.inv_transition = np.float32(math.inf if diff == 0.0 else 1.0 / diff)
 
 
 def _cube_tris():

@@ -70,6 +70,22 @@ class PerspectiveSensor:
         self.dict_ = sensor_dict
         self.film_ = film
         self.sampler_ = sampler
+        self.version_ = 0            # bumped when a parameter the flattened camera depends on changes (Scene.data re-flattens)
+
+    @property
+    def to_world(self):
+        from ..transform import to_transform
+        return to_transform(self.dict_.get("to_world"))
+
+    @to_world.setter
+    def to_world(self, value):
+        from ..transform import to_transform
+        self.dict_ = dict(self.dict_, to_world=to_transform(value))
+        self.version_ += 1
+
+    def traverse(self, callback):
+        """[mitsuba3: Sensor::traverse] the camera-to-world transform"""
+        callback.put("to_world", self.to_world)
 
     def film(self):
         return self.film_
