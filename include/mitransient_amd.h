@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 13
+#define MTR_ABI_VERSION 14
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -255,6 +255,22 @@ enum { MTR_FLAG_CAMERA_UNWARP = 1u,        /* common.py:25, transientpath.py:133
                                               versions we know [upstream-unverified, SURVEY A.9].  Kept so that ONE real
                                               reference render decides the question without a code change
                                               (tests/test_reference_golden.py).                                */,
+       MTR_FLAG_POLARIZED = 256u,          /* (ABI 14) the *_mono_polarized variants: polarized transport (mitransient's transient_path with
+                                              mi.is_polarized, transientpath.py:140-318).  The path throughput is a Mueller matrix
+                                              (beta_init, utils.py:9-21; beta = beta * bsdf_weight, :233; BSDF values and weights through
+                                              si.to_world_mueller, :210, :222-226; Russian roulette on M00, :244-253) and every
+                                              emitter a depolarizer, so a contribution is column 0 of the Mueller value.  Channel 0 of
+                                              every colour is used (the monochromatic variant).  OUTPUT CONTRACT:
+                                              `transient_hwt4` (H, W, T, 4) receives (S0, S1, S2, S3) per bin — value[0..3, 0, 0] of
+                                              the splat (transient_image_block.py:93-95; channels "0123W" of transient_hdr_film.py:176-177
+                                              without the weight, which is 0 for every transient splat): the developed tensor IS the raw
+                                              one, mtr_film_develop must not be applied to it.  `steady_hw4` receives (S0, S1, S2, weight)
+                                              per pixel; the steady image is S0 / weight (unpolarized_spectrum(L), integrators/
+                                              common.py:108-112), which mtr_film_develop computes in channel 0.
+                                              Scenes: diffuse, conductor, roughconductor, dielectric (also two-sided) and `area`
+                                              emitters; anything else, the NLOS tier and a phasor film are MTR_ERR_UNSUPPORTED.
+                                              Wavefront organisation only: MTR_MODE_AUTO resolves to MTR_MODE_WAVEFRONT,
+                                              MTR_MODE_FUSED is MTR_ERR_UNSUPPORTED, and so are MTR_FLAG_DEVELOPED_ROWS and band words. */
        MTR_FLAG_PCG_TEA64 = 128u           /* a third reading of the same call site (round 5; a new flag bit, no ABI change): m_rng.seed(1, sample_tea_64(seed, idx),
                                               sample_tea_64(idx, seed)) — 64-bit state and stream words, each the two TEA
                                               outputs glued together (v0 + (v1 << 32)) — instead of the two halves of one

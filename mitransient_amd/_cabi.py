@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MITRANSIENT_AMD_LIB") or os.path.join(_HERE, "csrc", "libmitransient_amd.so")   # env override: kernel A/B experiments
 
-MTR_ABI_VERSION = 13
+MTR_ABI_VERSION = 14
 MTR_TRAIT_DIFFUSE, MTR_TRAIT_ONE_RECT_EMITTER, MTR_TRAIT_LEAF_PAIR, MTR_TRAIT_FLAT_TOP, MTR_TRAIT_FLAT_LEAVES, MTR_TRAIT_NO_LOBES, MTR_TRAIT_GREY = 1, 2, 4, 8, 16, 32, 64      # mtr_scene_traits
 MTR_SPLAT_FILM_ZERO = 0x100      # mtr_splat_add: OR into `variant` when the film is all-zero on entry
 
@@ -27,6 +27,7 @@ MTR_FLAG_PCG_TEA64 = 128
 MTR_FLAG_KEEP_COUNTERS = 16
 MTR_FLAG_DETERMINISTIC = 32
 MTR_FLAG_DEVELOPED_ROWS = 64
+MTR_FLAG_POLARIZED = 256           # (ABI 14) the *_mono_polarized variants: Stokes film (H, W, T, 4), S0 steady
 MTR_MODE_AUTO, MTR_MODE_FUSED, MTR_MODE_WAVEFRONT = 0, 1, 2
 MTR_RECT_ANALYTIC, MTR_RECT_FLIP_NORMALS = 1, 2
 

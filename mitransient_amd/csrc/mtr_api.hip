@@ -8,6 +8,7 @@
 #include "mtr_scene_host.h"
 #include "mtr_core.h"
 #include "mtr_kernels.h"
+#include "mtr_polar.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -41,6 +42,7 @@ struct mtr_ctx {
 struct WfWorkspace {            // MTR_MODE_WAVEFRONT buffers, sized for one tile, reused across renders
     void *planes = nullptr, *q_live = nullptr, *q_ray = nullptr, *q_mat = nullptr, *q_shadow = nullptr, *r_shadow = nullptr, *occ = nullptr, *counts = nullptr, *rec = nullptr, *rec_count = nullptr, *q_zombie = nullptr;
     uint32_t n_slots = 0, P = 0, rec_cap = 0, rows = 0;
+    bool polar = false;                  // `planes` also holds the polarized planes (wf_polar_planes_bytes) behind the ordinary ones
     uint32_t *host_count = nullptr;       // pinned: live counts read back between bounce chunks (two words, alternating)
     hipEvent_t poll_ev[2] = { nullptr, nullptr };     // ... and the events that say a word has landed
 };
@@ -60,6 +62,7 @@ struct mtr_scene {
     std::vector<float> tri_normals;          // ... and the vertex normals (empty without): Mesh::sample_position on hidden meshes
     float bb_lo[3] = { 0, 0, 0 }, bb_hi[3] = { 0, 0, 0 };   // bounds of the triangles (the grid of the wavefront organisation's trace order)
     uint32_t n_emitters_area = 0;
+    bool polar_ok = false;                                   // every material and emitter has a polarized form (mtr_polar.h)
     bool grey_scene = false;                                 // kTrGrey without the NLOS laser (mtr_scene_set_nlos decides with it)
     SceneDev dev{};
     Camera cam{};
@@ -221,6 +224,9 @@ int mtr_scene_create(mtr_ctx *c, const mtr_scene_desc *d, mtr_scene **out)
 #undef UP
     s->dev.n_nodes = (uint32_t)hs.nodes.size(); s->dev.n_slots = (uint32_t)hs.tshade.size();
     s->dev.n_mats = d->n_materials; s->dev.n_ems = d->n_emitters;
+    s->polar_ok = hs.texels.empty();
+    for (uint32_t i = 0; i < d->n_materials; ++i) if (!polar_bsdf_supported(d->materials[i].type)) s->polar_ok = false;
+    for (uint32_t i = 0; i < d->n_emitters; ++i) if (hs.ems[i].angular) s->polar_ok = false;
     s->dev.has_rough = 0u;
     for (uint32_t i = 0; i < d->n_materials; ++i)
         if (bsdf_is_rough(d->materials[i].type) || d->materials[i].type == MTR_BSDF_THINDIELECTRIC) s->dev.has_rough = 1u;
@@ -419,15 +425,16 @@ int mtr_scene_traits(const mtr_scene *s, uint32_t *traits)
 } // extern "C"
 
 // ---- MTR_MODE_WAVEFRONT: host loop over tiles and bounces ------------------------------------
-static int wf_alloc(mtr_scene *s, uint32_t n_slots, uint32_t P, uint32_t n_seg, uint32_t rec_cap)
+static int wf_alloc(mtr_scene *s, uint32_t n_slots, uint32_t P, uint32_t n_seg, uint32_t rec_cap, bool polar = false)
 {
     mtr_ctx *c = s->ctx;
     WfWorkspace &w = s->wf;
-    if (w.n_slots >= n_slots && w.P >= P && w.rec_cap == rec_cap && w.rows >= n_seg && w.planes) return MTR_OK;
+    if (w.n_slots >= n_slots && w.P >= P && w.rec_cap == rec_cap && w.rows >= n_seg && w.planes && (w.polar || !polar)) return MTR_OK;
     void **ptrs[] = { &w.planes, &w.q_live, &w.q_ray, &w.q_mat, &w.q_shadow, &w.r_shadow, &w.occ, &w.counts, &w.rec, &w.rec_count, &w.q_zombie };
     w.n_slots = 0; w.P = 0; w.rec_cap = 0; w.rows = 0;          // sizes are valid only once every buffer below exists
     for (void **p : ptrs) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    HIP_TRY(c, hipMalloc(&w.planes, wf_planes_bytes(n_slots)));
+    w.polar = false;
+    HIP_TRY(c, hipMalloc(&w.planes, wf_planes_bytes(n_slots) + (polar ? wf_polar_planes_bytes(n_slots) : 0)));
     HIP_TRY(c, hipMalloc(&w.q_live, (size_t)2 * n_slots * 4));
     HIP_TRY(c, hipMalloc(&w.q_ray, (size_t)2 * n_slots * 32));                       // rays of the live lists, in list order
     HIP_TRY(c, hipMalloc(&w.q_mat, (size_t)kWfKeys * n_slots * 4));
@@ -440,7 +447,7 @@ static int wf_alloc(mtr_scene *s, uint32_t n_slots, uint32_t P, uint32_t n_seg, 
     HIP_TRY(c, hipMalloc(&w.rec_count, (size_t)P * 4));
     if (!w.host_count) HIP_TRY(c, hipHostMalloc((void **)&w.host_count, 64));
     for (hipEvent_t &e : w.poll_ev) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    w.n_slots = n_slots; w.P = P; w.rec_cap = rec_cap; w.rows = n_seg;
+    w.n_slots = n_slots; w.P = P; w.rec_cap = rec_cap; w.rows = n_seg; w.polar = polar;
     return MTR_OK;
 }
 
@@ -450,6 +457,7 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
 {
     mtr_ctx *c = s->ctx;
     const Film &f = s->film;
+    const bool polar = (p->flags & MTR_FLAG_POLARIZED) != 0u;
     WfConfig cfg{};
     if (!wf_plan(s->dev, cfg)) return fail(c, MTR_ERR_UNSUPPORTED, "wavefront: BVH too deep for the LDS stack");
     const uint32_t n_pixels = p->pixel_end - p->pixel_begin;
@@ -468,7 +476,8 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
     uint32_t kTileSlots = 1u << 28; uint32_t kSegSlots = 8192u;
     {
         size_t free_b = 0, total_b = 0;
-        const size_t per_slot = 344;                                   // planes 128 + queues 52 + rays 96 + records 64 + occlusion 1, rounded up
+        const size_t per_slot = polar ? 488 : 344;                     // planes 128 + queues 52 + rays 96 + records 64 + occlusion 1, rounded up
+                                                                       // (polarized: + 80 B of Mueller / Stokes planes, + 64 B of records)
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             // half of what is free now (the workspace this scene already holds counts as free), and never more than a third of
             // the device: the caller's allocator (films, all-gather buffers, a second scene) needs room the driver cannot see
@@ -490,14 +499,14 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
     const uint32_t n_seg_max = (P + G - 1) / G;      // (of the first attempt; wf_alloc below may settle for a smaller tile)
     // time-bin records: per-pixel lists sized for 4 contributions per path; the rest (and rows that do not
     // fit LDS) fall back to f32 atomics on the film
-    const bool rows_fit = (size_t)f.bins * 12u <= 150u * 1024u;
-    const uint32_t rec_cap = rows_fit ? S * 4u : 0u;
-    int rc_ = wf_alloc(s, n_slots_max, P, n_seg_max, rec_cap);
+    const bool rows_fit = (size_t)f.bins * (polar ? 16u : 12u) <= 150u * 1024u;
+    const uint32_t rec_cap = rows_fit ? S * (polar ? 8u : 4u) : 0u;        // (polarized: two records per contribution)
+    int rc_ = wf_alloc(s, n_slots_max, P, n_seg_max, rec_cap, polar);
     // out of memory (someone else took it between hipMemGetInfo and here): halve the tile until the workspace fits
     while (rc_ == MTR_ERR_OOM && P > G && (size_t)P * S > (1u << 22)) {
         (void)hipGetLastError();                       // (the failed hipMalloc must not surface at the next launch check)
         P = std::max(G, ((P / 2 + G - 1) / G) * G);
-        rc_ = wf_alloc(s, P * S, P, (P + G - 1) / G, rec_cap);
+        rc_ = wf_alloc(s, P * S, P, (P + G - 1) / G, rec_cap, polar);
     }
     if (rc_) return rc_;
     WfWorkspace &w = s->wf;
@@ -604,8 +613,9 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
             while (depth < max_depth) {
                 if (unbounded) HIP_TRY(c, hipMemsetAsync(live_total, 0, 4, c->stream));
                 HIP_TRY(c, hipMemsetAsync(a.seg_list_n + (a.parity ^ 1u), 0, 4, c->stream));     // the list this bounce's survivors build
-                if (a.nlos_on) {          // NLOS tier: the whole loop iteration of transient_nlos_path in one launch per bounce
-                    HIP_TRY(c, launch_wf(a, cfg, 5, grid, c->stream)); a.ticket_cur ^= 1u;
+                if (a.nlos_on || polar) {       // NLOS tier / polarized transport: the whole loop iteration in one launch per bounce
+                    if (polar) a.first_bounce = depth == 0u ? 1u : 0u;            // (bounce 0 builds its paths: polar_begin)
+                    HIP_TRY(c, launch_wf(a, cfg, polar ? 6 : 5, grid, c->stream)); a.ticket_cur ^= 1u;
                     *n_trace += 1;
                     a.parity ^= 1u;
                     ++depth;
@@ -633,7 +643,7 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
                 HIP_TRY(c, hipEventCreate(&a0)); HIP_TRY(c, hipEventCreate(&a1));
                 HIP_TRY(c, hipEventRecord(a0, c->stream));
             }
-            HIP_TRY(c, launch_wf(a, cfg, 3, (int)std::min<uint32_t>(Pcur, (uint32_t)grid_full), c->stream));
+            HIP_TRY(c, launch_wf(a, cfg, polar ? 7 : 3, (int)std::min<uint32_t>(Pcur, (uint32_t)grid_full), c->stream));
             if (timed) { HIP_TRY(c, hipEventRecord(a1, c->stream)); scatter_ev.push_back({ a0, a1 }); }
             *n_scatter += 1;
         }
@@ -674,6 +684,17 @@ static int resolve_mode(mtr_scene *s, const mtr_render_params *p, uint32_t n_pix
     mtr_ctx *c = s->ctx;
     const Film &f = s->film;
     uint32_t mode = *mode_io;
+    if (p->flags & MTR_FLAG_POLARIZED) {  // polarized transport: the wavefront organisation alone (k_wf_polar_bounce)
+        if (s->nlos.on) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: polarized transport is not available for the NLOS tier");
+        if (f.n_freq) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: polarized transport is not available with a phasor_hdr_film");
+        if (!s->polar_ok)
+            return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: polarized transport supports diffuse, conductor, roughconductor and dielectric BSDFs without textures, and area emitters");
+        if (mode == MTR_MODE_FUSED)
+            return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: polarized transport (MTR_FLAG_POLARIZED) runs in the wavefront mode only");
+        *mode_io = MTR_MODE_WAVEFRONT;
+        if (developed_ok) *developed_ok = 0u;
+        return MTR_OK;
+    }
     if (s->nlos.on && mode == MTR_MODE_AUTO)                             // (wavefront = the second organisation: on request, and for
         mode = (s->dev.has_rough && (p->flags & MTR_FLAG_DETERMINISTIC)) ? MTR_MODE_WAVEFRONT : MTR_MODE_FUSED;      // deterministic rows with the extended shading)
     if (f.n_freq) {                      // phasor film: (opl, value) records -> wavefront pipeline by default; LDS (Re, Im) rows in the fused kernel on request

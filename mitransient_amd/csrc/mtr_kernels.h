@@ -137,13 +137,17 @@ struct WfArgs {
     SplatLog log;
     uint32_t nlos_on;                    // NLOS tier in the wavefront organisation: raygen = nlos_begin, one k_wf_nlos_bounce per bounce
     NlosConst nlos;
+    // (polarized transport keeps its Mueller / Stokes planes in the same allocation, behind the planes above: wf_polar_planes —
+    // WfArgs itself is not extended, so that the argument layout of every existing kernel stays what it was)
 };
 struct WfConfig { int stack; bool scene_lds; size_t lds_bytes; };
 
 size_t wf_planes_bytes(uint32_t n_slots);
+size_t wf_polar_planes_bytes(uint32_t n_slots);      // polarized transport: what follows wf_planes_bytes, rounded up to 16, in `planes`
 bool wf_plan(const SceneDev &sc, WfConfig &cfg);
 // which: 0 raygen, 1 trace (closest hit + material-sorted queues, or occlusion when a.trace_any), 2 shade,
-// 3 time-bin scatter-add, 5 one whole NLOS bounce (a.nlos_on)
+// 3 time-bin scatter-add, 5 one whole NLOS bounce (a.nlos_on), 6 one whole polarized bounce, 7 the Stokes scatter-add of
+// polarized transport
 hipError_t launch_wf(const WfArgs &a, const WfConfig &cfg, int which, int grid, hipStream_t stream);
 
 // scratch (variant 1): device buffer of >= 8 * (width * height + 2) bytes for the run table; NULL forces the atomics

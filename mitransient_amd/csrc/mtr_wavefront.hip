@@ -23,6 +23,7 @@
 //                 (coalesced 16 B/lane) into an LDS row histogram and adds the row to the
 //                 (H,W,T,4) film once.
 #include "mtr_kernels.h"
+#include "mtr_polar.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
@@ -1154,6 +1155,215 @@ __global__ void __launch_bounds__(kBlock) k_wf_phasor_scatter(const WfArgs a)
     }
 }
 
+// ---- polarized transport in the wavefront organisation (MTR_FLAG_POLARIZED) -------------------------------------
+// One launch per bounce runs the whole loop iteration of transient_path in the polarized variants (polar_bounce, mtr_polar.h)
+// for every slot of the segment's live list — k_wf_nlos_bounce's organisation.  The scalar path state (ray, eta, distance,
+// previous vertex, depth, sampler) lives in the ordinary planes (store_state / load_state); the Mueller throughput and the
+// Stokes radiance in five more planes of float4 (a.polar: beta rows 0..3, L).  Bounce 0 builds its paths from (pixel, sample)
+// (polar_begin) over the identity live list that k_wf_raygen leaves.  A contribution is TWO consecutive 16-byte records of its
+// pixel's list — (bin, S0, S1, S2) (bin, S3, 0, 0) — summed by k_wf_polar_scatter.
+enum PolarPlane { QP_B0 = 0, QP_B1, QP_B2, QP_B3, QP_L, QP_COUNT };
+// the polarized planes start behind the ordinary ones (and their 8-byte sampler plane), at a multiple of 16 bytes
+__host__ __device__ inline size_t wf_planes_bytes_d(uint32_t n_slots) { return (size_t)PL16_COUNT * n_slots * 16u + (size_t)n_slots * 8u; }
+__host__ __device__ inline size_t al16_z(size_t x) { return (x + 15u) & ~(size_t)15u; }
+
+struct PolarRecordSink {
+    uint4 *rec; uint32_t *s_rec_count; uint32_t rec_cap;    // rec_cap: records (two per contribution); s_rec_count: LDS
+    float *film; uint32_t film_w, bins;
+    uint32_t p_local, p_seg;
+    uint32_t n_splats, n_overflow;
+    __device__ __forceinline__ void splat4(uint32_t fx, uint32_t fy, uint32_t bin, float s0, float s1, float s2, float s3,
+                                           float, uint32_t, uint32_t)
+    {
+        // lanes of a wave that splat together mostly share 1..3 pixels: one LDS atomic per distinct pixel (RecordSink)
+        unsigned long long todo = __ballot(1);
+        const uint32_t lane_id = threadIdx.x & 63u;
+        uint32_t idx = 0;
+        while (todo) {
+            const int leader = __ffsll((long long)todo) - 1;
+            const uint32_t px = __shfl(p_seg, leader);
+            const unsigned long long same = __ballot(p_seg == px) & todo;
+            if (p_seg == px) {
+                const uint32_t n = (uint32_t)__popcll(same);
+                const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane_id) - 1ull));
+                uint32_t base = 0;
+                if ((int)lane_id == leader) base = atomicAdd(s_rec_count + px, 2u * n);
+                base = __shfl(base, leader);
+                idx = base + 2u * rank;
+            }
+            todo &= ~same;
+        }
+        ++n_splats;
+        if (idx + 1u < rec_cap) {                                // (rec_cap is even and idx is: the pair is whole)
+            uint4 *r = rec + (size_t)p_local * rec_cap + idx;
+            r[0] = make_uint4(bin, __float_as_uint(s0), __float_as_uint(s1), __float_as_uint(s2));
+            r[1] = make_uint4(bin, __float_as_uint(s3), 0u, 0u);
+        } else {
+            ++n_overflow;
+            float *dst = film + (((size_t)fy * film_w + fx) * bins + bin) * 4u;
+            unsafeAtomicAdd(dst, s0); unsafeAtomicAdd(dst + 1, s1); unsafeAtomicAdd(dst + 2, s2); unsafeAtomicAdd(dst + 3, s3);
+        }
+    }
+};
+
+template <int STACK, bool SCENE_LDS>
+__global__ void __launch_bounds__(kBlock, 2) k_wf_polar_bounce(const WfArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *s_next_p = (uint32_t *)smem;
+    const int tid = threadIdx.x;
+    SceneView sv; WStack<STACK> st; uint32_t off;
+    wf_setup<STACK, SCENE_LDS>(a.sc, smem, tid, sv, st, off);
+    uint32_t *s_rec = (uint32_t *)(smem + off);
+    float *s_steady = (float *)(smem + off + al16(a.G * 4u));
+    const PlanesT<!SCENE_LDS> P{ (float4 *)a.planes, a.n_slots };
+    const PlanesT<!SCENE_LDS> Q{ (float4 *)((unsigned char *)a.planes + al16_z(wf_planes_bytes_d(a.n_slots))), a.n_slots };
+    const uint32_t par = a.parity;
+    const bool unwarp = (a.rc.flags & MTR_FLAG_CAMERA_UNWARP) != 0u;
+    uint32_t n_closest = 0, n_shadow = 0, n_bounce = 0, n_splats = 0, n_over = 0, n_alive = 0;
+    wf_ticket_begin(a, tid);
+    for (uint32_t sg = wf_next_segment(a, smem, tid, true); sg < a.n_seg; sg = wf_next_segment(a, smem, tid, false)) {
+        const uint32_t pl0 = sg * a.G;
+        const uint32_t npx = min(a.G, a.P - pl0);
+        for (uint32_t t = tid; t < npx; t += kBlock) s_rec[t] = a.rec_count[pl0 + t];
+        for (uint32_t t = tid; t < 4 * npx; t += kBlock) s_steady[t] = 0.0f;
+        if (tid == 0) *s_next_p = 0u;
+        __syncthreads();
+        const uint32_t n_live = a.seg_live[(size_t)par * a.n_seg + sg];
+        const uint32_t *q = a.q_live + (size_t)par * a.n_slots + (size_t)sg * a.seg;
+        uint32_t *q_next = a.q_live + (size_t)(par ^ 1u) * a.n_slots + (size_t)sg * a.seg;
+        const uint32_t n_round = (n_live + 63u) & ~63u;
+        for (uint32_t i = tid; i < n_round; i += kBlock) {
+            bool alive = false;
+            uint32_t slot = 0;
+            if (i < n_live) {
+                slot = a.first_bounce ? sg * a.seg + i : q[i];          // bounce 0: the identity list of k_wf_raygen
+                uint32_t pixel, s, pl;
+                slot_to_lane(a, slot, pixel, s, pl);
+                PolarPath pp;
+                if (a.first_bounce) polar_begin(pp, a.cam, a.film, a.rc, pixel, s);
+                else {
+                    load_state(P, slot, pp.base);
+                    const uint32_t py = pixel / a.film.crop_w, px = pixel - a.film.crop_w * py;
+                    pp.base.px = px + a.film.crop_x; pp.base.py = py + a.film.crop_y; pp.base.lane = pixel * a.rc.spp_total + s;
+                    pp.base.rng.inc = rng_inc_of(a.rc.seed, pp.base.lane, a.rc.flags);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float4 v = Q.ld(QP_B0 + r, slot);
+                        pp.beta.m[4 * r] = v.x; pp.beta.m[4 * r + 1] = v.y; pp.beta.m[4 * r + 2] = v.z; pp.beta.m[4 * r + 3] = v.w;
+                    }
+                    const float4 l = Q.ld(QP_L, slot);
+                    pp.L[0] = l.x; pp.L[1] = l.y; pp.L[2] = l.z; pp.L[3] = l.w;
+                }
+                PolarRecordSink sink;
+                sink.rec = a.rec; sink.s_rec_count = s_rec; sink.rec_cap = a.rec_cap;
+                sink.film = a.film_out; sink.film_w = a.film.width; sink.bins = a.film.bins;
+                sink.p_local = pl; sink.p_seg = pl - pl0;
+                sink.n_splats = 0; sink.n_overflow = 0;
+                BounceStats bs; bs.closest = 0; bs.shadow = 0;
+                alive = polar_bounce(pp, sv, a.film, a.rc, st, sink, bs, unwarp);
+                n_closest += bs.closest; n_shadow += bs.shadow; ++n_bounce;
+                n_splats += sink.n_splats; n_over += sink.n_overflow;
+                if (alive) {
+                    ++n_alive;
+                    store_state(P, slot, pp.base, true);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        Q.st(QP_B0 + r, slot, make_float4(pp.beta.m[4 * r], pp.beta.m[4 * r + 1], pp.beta.m[4 * r + 2], pp.beta.m[4 * r + 3]));
+                    Q.st(QP_L, slot, make_float4(pp.L[0], pp.L[1], pp.L[2], pp.L[3]));
+                } else {
+                    // the steady film: (S0, S1, S2, weight 1) of the path (block.put(pos, [L, 1]), common.py:187-200)
+                    const uint32_t fx = pp.base.px - a.film.crop_x, fy = pp.base.py - a.film.crop_y;
+                    if (fx < a.film.width && fy < a.film.height) {
+                        float *sp = s_steady + 4 * (pl - pl0);
+                        __hip_atomic_fetch_add(sp, pp.L[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_add(sp + 1, pp.L[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_add(sp + 2, pp.L[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_add(sp + 3, 1.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                }
+            }
+            if (__ballot(alive) != 0ull) {
+                const uint32_t pos = wave_append(s_next_p, alive);
+                if (alive) q_next[pos] = slot;
+            }
+        }
+        __syncthreads();
+        if (tid == 0) wf_segment_survivors(a, sg, *s_next_p);
+        for (uint32_t t = tid; t < npx; t += kBlock) a.rec_count[pl0 + t] = s_rec[t];
+        for (uint32_t t = tid; t < 4 * npx; t += kBlock) {
+            const float v = s_steady[t];
+            if (v != 0.0f) {
+                const uint32_t pixel = a.pix0 + pl0 + (t >> 2);
+                const uint32_t cy = pixel / a.film.crop_w, cx = pixel - cy * a.film.crop_w;
+                if (cx < a.film.width && cy < a.film.height) a.steady_out[((size_t)cy * a.film.width + cx) * 4u + (t & 3u)] += v;
+            }
+        }
+        __syncthreads();
+    }
+    if (a.counters) {
+        const unsigned vals[5] = { n_closest, n_shadow, n_splats, n_bounce, n_over };
+        unsigned long long *dst[5] = { &a.counters->rays_closest, &a.counters->rays_shadow, &a.counters->splats_issued,
+                                       &a.counters->bounces, &a.counters->splats_overflow };
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            unsigned v = vals[k];
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+            if ((tid & 63) == 0 && v) atomicAdd(dst[k], (unsigned long long)v);
+        }
+    }
+    if (a.live_total) {
+        unsigned v = n_alive;
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+        if ((tid & 63) == 0 && v) atomicAdd(a.live_total, v);
+    }
+}
+
+// The Stokes scatter-add: one workgroup per pixel of the tile streams the pixel's record pairs into an LDS row of [4][T] f32
+// and adds the row to the (H, W, T, 4) film, whose fourth float of a bin holds S3 (the weight slot of the unpolarized film is
+// 0 for every transient splat, and the develop of a polarized film never divides by it).  f32 LDS atomics — the row form the
+// RANGE GUARD of k_wf_scatter falls back to — so 1e7, Inf and NaN arrive in the film as what they are.
+__global__ void __launch_bounds__(kBlock) k_wf_polar_scatter(const WfArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float *row = (float *)(smem + 64);                              // [4][T]
+    const uint32_t T = a.film.bins;
+    const int tid = threadIdx.x;
+    for (uint32_t t = tid; t < 4 * T; t += kBlock) row[t] = 0.0f;
+    __syncthreads();
+    for (uint32_t pl = blockIdx.x; pl < a.P; pl += gridDim.x) {
+        const uint32_t pixel = a.pix0 + pl;
+        const uint32_t cy = pixel / a.film.crop_w, cx = pixel - cy * a.film.crop_w;
+        const bool in_film = (cx < a.film.width) & (cy < a.film.height);
+        const uint32_t n_all = a.rec_count[pl];
+        const uint32_t n = min(n_all, a.rec_cap) & ~1u;                 // whole pairs
+        const bool store_only = a.film_zero && n_all <= a.rec_cap;      // no overflow atomics landed on this row
+        const uint4 *rec = a.rec + (size_t)pl * a.rec_cap;
+        for (uint32_t i = tid; 2u * i < n; i += kBlock) {
+            const uint4 r0 = nt_load(rec + 2u * i), r1 = nt_load(rec + 2u * i + 1u);
+            float *p = row + r0.x;
+            __hip_atomic_fetch_add(p, __uint_as_float(r0.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(p + T, __uint_as_float(r0.z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(p + 2 * T, __uint_as_float(r0.w), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(p + 3 * T, __uint_as_float(r1.y), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        __syncthreads();
+        float4 *dst = (float4 *)(a.film_out + ((size_t)cy * a.film.width + cx) * T * 4u);
+        for (uint32_t t = tid; t < T; t += kBlock) {
+            const float s0 = row[t], s1 = row[T + t], s2 = row[2 * T + t], s3 = row[3 * T + t];
+            const bool nz = s0 != 0.0f || s1 != 0.0f || s2 != 0.0f || s3 != 0.0f;
+            if (nz) { row[t] = 0.0f; row[T + t] = 0.0f; row[2 * T + t] = 0.0f; row[3 * T + t] = 0.0f; }
+            if ((nz || store_only) && in_film) {
+                float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (!store_only) v = dst[t];
+                v.x += s0; v.y += s1; v.z += s2; v.w += s3;
+                nt_store(dst + t, v);
+            }
+        }
+        __syncthreads();
+    }
+}
+
 template <int STACK, bool SL>
 hipError_t launch_set(const WfArgs &a, int which, int grid, size_t lds, hipStream_t stream)
 {
@@ -1171,6 +1381,14 @@ hipError_t launch_set(const WfArgs &a, int which, int grid, size_t lds, hipStrea
             return hipGetLastError();
         }
     }
+    if (which == 6) {            // polarized bounce: the LDS of k_wf_nlos_bounce (record-list tails, steady sums)
+        lds += al16(a.G * 4u) + al16(a.G * 16u) + al16(a.seg);
+        void (*kp)(const WfArgs) = k_wf_polar_bounce<STACK, SL>;
+        hipError_t e = hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kp, dim3(grid), dim3(kBlock), lds, stream, a);
+        return hipGetLastError();
+    }
     void (*k)(const WfArgs) = which == 0 ? k_wf_raygen<STACK, SL> : which == 1 ? (a.trace_any ? k_wf_trace<STACK, SL, true> : a.first_bounce ? k_wf_trace<STACK, SL, false, true> : k_wf_trace<STACK, SL, false>)
                             : which == 5 ? (ext ? k_wf_nlos_bounce<STACK, SL, true> : k_wf_nlos_bounce<STACK, SL, false>)
                             : a.first_bounce ? (ext ? k_wf_shade<STACK, SL, true, 0u, true> : k_wf_shade<STACK, SL, false, 0u, true>)
@@ -1186,6 +1404,7 @@ hipError_t launch_set(const WfArgs &a, int which, int grid, size_t lds, hipStrea
 } // namespace
 
 size_t wf_planes_bytes(uint32_t n_slots) { return (size_t)PL16_COUNT * n_slots * 16u + (size_t)n_slots * 8u; }
+size_t wf_polar_planes_bytes(uint32_t n_slots) { return al16_z(wf_planes_bytes_d(n_slots)) - wf_planes_bytes_d(n_slots) + (size_t)QP_COUNT * n_slots * 16u; }
 
 bool wf_plan(const SceneDev &sc, WfConfig &cfg)
 {
@@ -1204,6 +1423,14 @@ hipError_t launch_wf(const WfArgs &a, const WfConfig &cfg, int which, int grid, 
     if (which == 3 && a.film.n_freq) {
         const size_t lds = 64 + kPhasorChunk * 8u + kBlock * 8u;
         hipLaunchKernelGGL(k_wf_phasor_scatter, dim3(grid), dim3(kBlock), lds, stream, a);
+        return hipGetLastError();
+    }
+    if (which == 7) {            // polarized transport: the Stokes scatter-add
+        if (!a.rec_cap) return hipSuccess;                      // rows do not fit LDS: every contribution went to the film's atomics
+        const size_t lds = 64 + (size_t)a.film.bins * 16u;
+        hipError_t e = hipFuncSetAttribute((const void *)k_wf_polar_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_wf_polar_scatter, dim3(grid), dim3(kBlock), lds, stream, a);
         return hipGetLastError();
     }
     if (which == 3) {

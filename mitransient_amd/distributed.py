@@ -172,6 +172,10 @@ class DistributedRenderer:
         sens = scene.sensors()[sensor]
         film = sens.film()
         integ.check_transient_(scene, sens)
+        from . import variant as _variant
+        if _variant.is_polarized() and world > 1:
+            # the row reduction and develop of the sharded paths are written for the (R, G, B, weight) film
+            raise NotImplementedError(f"{_variant.get()}: multi-GPU sharding of polarized renders is not available; render on one GPU")
         if world == 1:
             self.last_path = "single"
             self.last_collectives = 0

@@ -258,6 +258,11 @@ class TransientHDRFilm:
                 return TensorXf(out[..., :1].contiguous() if variant.is_monochromatic() else out)
         if not self.transient_storage:
             raise RuntimeError("No transient storage allocated, was prepare_transient_() called first?")
+        if variant.is_polarized():
+            # (S0, S1, S2, S3) per bin, channels "0123" of the reference (transient_hdr_film.py:176-177): the raw sums ARE the
+            # developed values — the weight channel of a transient splat is 0, so the reference's develop divides by nothing
+            t = self.transient_storage.torch_tensor()
+            return TensorXf(t if raw else t.clone())
         if raw and variant.is_monochromatic():
             t = self.transient_storage.torch_tensor()
             return TensorXf(torch.stack((t[..., 0], t[..., 3]), dim=-1))          # "LW"

@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Tuple
 
-from .. import _cabi
+from .. import _cabi, variant
 from ..films.transient_hdr_film import TransientHDRFilm
 from ..runtime import get_context
 from ..scene import Properties
@@ -142,6 +142,8 @@ class TransientADIntegrator:
             f |= _cabi.MTR_FLAG_PCG_TEA64
         if self.deterministic:
             f |= _cabi.MTR_FLAG_DETERMINISTIC
+        if variant.is_polarized():
+            f |= _cabi.MTR_FLAG_POLARIZED         # Mueller throughput, Stokes film (wavefront organisation)
         return f
 
     def render_params(self, film, seed_value, spp_total, spp_begin=0, spp_end=None,

@@ -28,17 +28,32 @@ def variant():
     return _variant_mod.get()
 
 
+POLARIZED_VARIANTS = ("llvm_ad_mono_polarized", "cuda_ad_mono_polarized")
+
+
 def set_variant(*names):
     """The unpolarized ``*_ad_rgb`` variants, and ``*_ad_mono`` (needed by ``phasor_hdr_film``): monochromatic rendering
-    = every colour replaced by its luminance, one output channel."""
+    = every colour replaced by its luminance, one output channel.  ``llvm_ad_mono_polarized`` / ``cuda_ad_mono_polarized``:
+    the same, with polarization tracking (Mueller throughput, Stokes radiance; the wavefront organisation)."""
     for n in names:
+        if n in POLARIZED_VARIANTS:
+            _variant_mod.set(n)
+            return
         if (n.endswith("_rgb") or n.endswith("_mono")) and "polarized" not in n and not n.startswith("scalar"):
             _variant_mod.set(n)
             return
-    raise ValueError(f"unsupported variant(s) {names}: mitransient_amd implements the *_ad_rgb / *_ad_mono paths only")
+    raise ValueError(f"unsupported variant(s) {names}: mitransient_amd implements the *_ad_rgb / *_ad_mono paths and the "
+                     f"polarized {' / '.join(POLARIZED_VARIANTS)} only (no scalar_*, spectral or *_rgb_polarized variants)")
 
 
 is_monochromatic = _variant_mod.is_monochromatic
+
+
+def __getattr__(name):
+    # ``mi.is_polarized`` reads the variant that is active NOW (a module attribute would freeze it at import time)
+    if name == "is_polarized":
+        return _variant_mod.is_polarized()
+    raise AttributeError(name)
 
 
 __version__ = "3.7.0-mitransient_amd"       # the Mitsuba generation whose plugin semantics are mirrored (reference: >=3.6,<3.9)
@@ -218,6 +233,9 @@ class Scene:
         # examples/transient-nlos/nlos-z-*.xml — transient_nlos_path behind an ordinary perspective camera
         if key in self.relay_names_ or isinstance(self.integrator_, TransientNLOSPath):
             from .scene import nlos_desc_from
+            if _variant_mod.is_polarized():
+                raise ValueError(f"{_variant_mod.get()}: the polarized variants render with transient_path only "
+                                 "(transient_nlos_path is not available)")
             if len(self.emitters_) != 1:
                 raise AssertionError(f"You have defined multiple ({len(self.emitters_)}) emitters in the scene with a "
                                      "NLOS capture meter. You should have only 1.")

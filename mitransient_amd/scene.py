@@ -890,6 +890,35 @@ def load_geometry(path: str) -> Dict[str, Any]:
             "meta": json.loads(str(z["meta"]))}
 
 
+_POLARIZED_BSDFS = {_cabi.MTR_BSDF_DIFFUSE: "diffuse", _cabi.MTR_BSDF_CONDUCTOR: "conductor",
+                    _cabi.MTR_BSDF_ROUGHCONDUCTOR: "roughconductor", _cabi.MTR_BSDF_DIELECTRIC: "dielectric"}
+
+
+def _check_polarized(b, film, sd):
+    """The polarized variants implement diffuse, conductor, roughconductor and dielectric BSDFs (also inside twosided), area
+    emitters and the transient_path integrator with a transient_hdr_film (mtr_polar.h).  Anything else is refused here rather
+    than rendered as an unpolarized approximation."""
+    v = _variant.get()
+    names = {getattr(_cabi, k): k[len("MTR_BSDF_"):].lower() for k in dir(_cabi) if k.startswith("MTR_BSDF_")}
+    if b.nlos:
+        raise ValueError(f"{v}: the polarized variants render with transient_path only (transient_nlos_path is not available)")
+    if type(film).__name__ != "TransientHDRFilm":
+        raise ValueError(f"{v}: the polarized variants need a transient_hdr_film (not {type(film).__name__})")
+    if getattr(film, "exhaustive_scan", False):
+        raise ValueError(f"{v}: an exhaustive_scan film is not available with polarization")
+    for m in b.materials:
+        if m.type not in _POLARIZED_BSDFS:
+            raise ValueError(f"{v}: the {names.get(m.type, m.type)} BSDF is not available with polarization "
+                             f"(supported: {', '.join(_POLARIZED_BSDFS.values())}, and twosided of these)")
+        if m.albedo_texture:
+            raise ValueError(f"{v}: bitmap textures are not available with polarization")
+    for e in b.emitters:
+        if e.angular:
+            raise ValueError(f"{v}: the angulararea emitter is not available with polarization (supported emitters: area)")
+    if sd.textures:
+        raise ValueError(f"{v}: bitmap textures are not available with polarization")
+
+
 def flatten_scene(d: Dict[str, Any], film, sensor_dict: Dict[str, Any], base_dir: str = ".",
                   relay_shape_name: Optional[str] = None, approximate_materials: bool = False,
                   geometry: Optional[Dict[str, Any]] = None) -> SceneData:
@@ -948,6 +977,8 @@ def flatten_scene(d: Dict[str, Any], film, sensor_dict: Dict[str, Any], base_dir
         if any(u is not None for u in b.tri_uv):        # shapes without texture coordinates: a degenerate (all-zero) parameterisation
             sd.tri_uv = np.ascontiguousarray(np.concatenate(
                 [u if u is not None else np.zeros((v.shape[0], 6), np.float32) for u, v in zip(b.tri_uv, b.tri_verts)]))
+    if _variant.is_polarized():
+        _check_polarized(b, film, sd)
     sd.n_materials = len(b.materials)
     sd.materials = (_cabi.mtr_material * max(1, sd.n_materials))(*b.materials)
     sd.n_emitters = len(b.emitters)

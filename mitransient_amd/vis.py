@@ -155,3 +155,71 @@ def rainbow_visualization(steady_state, data_transient, modulo, min_modulo, max_
     else:
         raise NotImplementedError("Mode not implemented")
     return out
+
+
+# ---- the polarized variants (mitransient/polarized_visualization.py:193-290): Stokes arrays with S0..S3 on the last axis ----
+def _stokes_ratio(stokes, k, s0_minimum):
+    s = np.asarray(stokes)
+    return s[..., k] / np.maximum(s[..., 0], s0_minimum)
+
+
+def degree_of_polarization(stokes, s0_minimum=0.01):
+    """|(S1, S2, S3)| / max(S0, s0_minimum), clipped to [0, 1]"""
+    s = np.asarray(stokes)
+    return np.clip(np.sqrt(s[..., 1] ** 2 + s[..., 2] ** 2 + s[..., 3] ** 2) / np.maximum(s[..., 0], s0_minimum), 0.0, 1.0)
+
+
+def degree_of_linear_polarization(stokes, s0_minimum=0.01):
+    """|(S1, S2)| / max(S0, s0_minimum), clipped to [0, 1]"""
+    s = np.asarray(stokes)
+    return np.clip(np.sqrt(s[..., 1] ** 2 + s[..., 2] ** 2) / np.maximum(s[..., 0], s0_minimum), 0.0, 1.0)
+
+
+def degree_of_circular_polarization(stokes, s0_minimum=0.01):
+    """|S3| / max(S0, s0_minimum), clipped to [0, 1]"""
+    return np.clip(np.abs(_stokes_ratio(stokes, 3, s0_minimum)), 0.0, 1.0)
+
+
+def polarization_generate_false_color(stokes, aolp_intensity_scaling=1.0, s0_minimum=0.01):
+    """The false-colour maps of Wilkie and Weidlich, "A standardised polarisation visualisation for images" (2010), on a 0..255
+    scale: (degree of polarization in red, angle of linear polarization, the same scaled by the degree of linear polarization,
+    type of polarization, chirality).  The angle map encodes the signs of S1 / S0 (green positive, red negative) and S2 / S0
+    (yellow positive, blue negative)."""
+    dop, dolp, docp = (degree_of_polarization(stokes, s0_minimum), degree_of_linear_polarization(stokes, s0_minimum),
+                       degree_of_circular_polarization(stokes, s0_minimum))
+    pos = lambda x: np.maximum(x, 0.0)           # noqa: E731
+    s1, s2, s3 = (_stokes_ratio(stokes, k, s0_minimum) for k in (1, 2, 3))
+    dop_reds = dop[..., None] * np.array([255.0, 0.0, 0.0])
+    aolp = 255.0 * (np.stack([pos(-s1), pos(s1), np.zeros_like(s1)], axis=-1) + np.stack([pos(s2), pos(s2), pos(-s2)], axis=-1))
+    aolp_scaled = aolp * aolp_intensity_scaling * dolp[..., None]
+    top = dolp[..., None] * np.array([22.0, 247.0, 247.0]) + docp[..., None] * np.array([252.0, 251.0, 10.0])
+    chirality = 255.0 * np.stack([pos(s3), pos(s3), pos(-s3)], axis=-1) * docp[..., None]
+    return dop_reds, aolp, aolp_scaled, top, chirality
+
+
+class DisplayMethod:
+    """where show_video_polarized sends the frames (the reference's enum of the same name)"""
+    ShowVideo, SaveVideo, SaveFrames = 0, 1, 2
+
+
+def show_video_polarized(stokes, degree_of_polarization, angle_of_polarization, type_of_polarization, chirality, save_path=None,
+                         display_method=DisplayMethod.ShowVideo, fps=24, intensity_cutoff=0.9, gamma=1.1, show_false_color=True):
+    """the transient Stokes video: S0 (tonemapped to its ``intensity_cutoff`` quantile, then ``gamma``), next to the false-colour
+    maps when ``show_false_color``.  ShowVideo plays it inline as ``show_video`` does; SaveFrames writes one EXR per time bin
+    under ``save_path``.  (SaveVideo, the reference's mp4 through OpenCV, is not available.)"""
+    s = np.asarray(stokes, dtype=np.float64)
+    s0 = s[..., 0]
+    top = np.quantile(s0, intensity_cutoff) if s0.size else 1.0
+    inten = np.clip(s0 / (top if top > 0 else 1.0), 0.0, 1.0) ** (1.0 / gamma)
+    panels = [np.repeat(inten[..., None], 3, axis=-1)]
+    if show_false_color:
+        panels += [np.asarray(m, dtype=np.float64) / 255.0 for m in (degree_of_polarization, angle_of_polarization,
+                                                                     type_of_polarization, chirality)]
+    frames = np.concatenate(panels, axis=1)                     # (H, 5 W, T, 3): the panels side by side
+    if display_method == DisplayMethod.SaveFrames:
+        save_frames(frames.astype(np.float32), save_path, axis_video=2)
+        return None
+    if display_method == DisplayMethod.SaveVideo:
+        raise NotImplementedError("show_video_polarized: DisplayMethod.SaveVideo (mp4 through OpenCV) is not available; "
+                                  "use SaveFrames or ShowVideo")
+    return show_video(frames, axis_video=2, uint8_srgb=False)
