@@ -691,6 +691,8 @@ static int resolve_mode(mtr_scene *s, const mtr_render_params *p, uint32_t n_pix
             return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: polarized transport supports diffuse, conductor, roughconductor and dielectric BSDFs without textures, and area emitters");
         if (mode == MTR_MODE_FUSED)
             return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: polarized transport (MTR_FLAG_POLARIZED) runs in the wavefront mode only");
+        if (p->flags & MTR_FLAG_DETERMINISTIC)   // the Stokes rows, the steady image and overflow cells are f32 atomics
+            return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: polarized transport (MTR_FLAG_POLARIZED) has no deterministic rows (MTR_FLAG_DETERMINISTIC)");
         *mode_io = MTR_MODE_WAVEFRONT;
         if (developed_ok) *developed_ok = 0u;
         return MTR_OK;

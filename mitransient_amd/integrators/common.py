@@ -141,6 +141,9 @@ class TransientADIntegrator:
         if self.pcg_tea64:
             f |= _cabi.MTR_FLAG_PCG_TEA64
         if self.deterministic:
+            if variant.is_polarized():          # (the polarized kernels sum f32 Stokes rows: no fixed-point rows)
+                raise ValueError(f"{variant.get()}: amd_deterministic is not available with polarization "
+                                 "(the Stokes film is summed with f32 atomics; render without amd_deterministic)")
             f |= _cabi.MTR_FLAG_DETERMINISTIC
         if variant.is_polarized():
             f |= _cabi.MTR_FLAG_POLARIZED         # Mueller throughput, Stokes film (wavefront organisation)

@@ -1151,12 +1151,270 @@ void orc_bsdf_sample(const mtr_material *m, uint32_t n, const float *wi3, const 
 }
 
 /* ------------------------------------------------------------------ */
+/* Polarization algebra in f64  [mitsuba3: include/mitsuba/render/mueller.h, fresnel.h fresnel_polarized,
+ * SurfaceInteraction::to_world_mueller; mitransient utils.py:9-21 beta_init].  The path machinery above (sampler, rays, hits,
+ * BSDF directions / pdfs, lobe choice, emitter sampling, MIS, path lengths) stays f32 and is shared with the unpolarized
+ * path; only the Mueller throughput, the Stokes radiance and the matrices that feed them are f64 here.  Conventions
+ * (DESIGN.md §2 "Polarization"): Mueller matrices act on (S0, S1, S2, S3) measured in the Stokes basis
+ * coordinate_system(w).first of the propagation direction w; a basis change by theta is the rotator
+ *   (1 0 0 0; 0 cos2t sin2t 0; 0 -sin2t cos2t 0; 0 0 0 1),
+ * theta the signed angle from the current to the target basis about the propagation direction; a_p = (cos_t - eta cos_i) /
+ * (cos_t + eta cos_i).  Every product below is the general 4x4 one.                                                          */
+/* ------------------------------------------------------------------ */
+#include <complex.h>
+
+typedef struct { double e[4][4]; } mueller_d;
+typedef struct { double x, y, z; } dv3;
+
+static dv3 dv(v3 a) { dv3 r = { a.x, a.y, a.z }; return r; }
+static dv3 dv_make(double x, double y, double z) { dv3 r = { x, y, z }; return r; }
+static double dv_dot(dv3 a, dv3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+static dv3 dv_cross(dv3 a, dv3 b) { return dv_make(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+static dv3 dv_neg(dv3 a) { return dv_make(-a.x, -a.y, -a.z); }
+static dv3 dv_unit(dv3 a) { double n = sqrt(dv_dot(a, a)); return dv_make(a.x / n, a.y / n, a.z / n); }
+static int dv_is_zero(dv3 a) { return a.x == 0.0 && a.y == 0.0 && a.z == 0.0; }
+/* a local direction to world space through the shading frame (s, t, n) */
+static dv3 dv_frame(dv3 s, dv3 t, dv3 n, dv3 v)
+{
+    return dv_make(s.x * v.x + t.x * v.y + n.x * v.z, s.y * v.x + t.y * v.y + n.y * v.z, s.z * v.x + t.z * v.y + n.z * v.z);
+}
+
+static mueller_d md_zero(void) { mueller_d r; memset(&r, 0, sizeof r); return r; }
+static mueller_d md_diag(double a) { mueller_d r = md_zero(); r.e[0][0] = a; return r; }     /* depolarizer(a) */
+static mueller_d md_identity(void) { mueller_d r = md_zero(); for (int i = 0; i < 4; ++i) r.e[i][i] = 1.0; return r; }
+static mueller_d md_mul(const mueller_d *a, const mueller_d *b)
+{
+    mueller_d r = md_zero();
+    for (int i = 0; i < 4; ++i)
+        for (int k = 0; k < 4; ++k)
+            for (int j = 0; j < 4; ++j) r.e[i][j] += a->e[i][k] * b->e[k][j];
+    return r;
+}
+static mueller_d md_transpose(const mueller_d *a)
+{
+    mueller_d r;
+    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) r.e[i][j] = a->e[j][i];
+    return r;
+}
+static mueller_d md_scaled(mueller_d a, double s) { for (int i = 0; i < 16; ++i) a.e[i / 4][i % 4] *= s; return a; }
+
+/* [mueller.h: stokes_basis(w)] = coordinate_system(w).first (Duff et al. 2017), in f64 */
+static dv3 stokes_basis_d(dv3 w)
+{
+    const double sg = w.z >= 0.0 ? 1.0 : -1.0;
+    const double a = -1.0 / (sg + w.z), b = w.x * w.y * a;
+    return dv_make(1.0 + sg * w.x * w.x * a, sg * b, -sg * w.x);
+}
+/* [mueller.h: rotator(theta)] */
+static mueller_d rotator_d(double theta)
+{
+    mueller_d r = md_identity();
+    const double c = cos(2.0 * theta), s = sin(2.0 * theta);
+    r.e[1][1] = c; r.e[1][2] = s; r.e[2][1] = -s; r.e[2][2] = c;
+    return r;
+}
+/* [mueller.h: rotate_stokes_basis(forward, current, target)]: rotator(theta), theta the angle from `current` to `target`,
+ * positive about `forward` — formed explicitly with atan2 */
+static mueller_d rotate_stokes_basis_d(dv3 fwd, dv3 cur, dv3 tgt)
+{
+    const dv3 f = dv_unit(fwd), c = dv_unit(cur), t = dv_unit(tgt);
+    return rotator_d(atan2(dv_dot(f, dv_cross(c, t)), dv_dot(c, t)));
+}
+/* [mueller.h: rotate_mueller_basis]: R_out M R_in^T */
+static mueller_d rotate_mueller_basis_d(const mueller_d *M, dv3 in_fwd, dv3 in_cur, dv3 in_tgt, dv3 out_fwd, dv3 out_cur, dv3 out_tgt)
+{
+    const mueller_d Rin = rotate_stokes_basis_d(in_fwd, in_cur, in_tgt), Rout = rotate_stokes_basis_d(out_fwd, out_cur, out_tgt);
+    const mueller_d RinT = md_transpose(&Rin);
+    const mueller_d t = md_mul(&Rout, M);
+    return md_mul(&t, &RinT);
+}
+/* [SurfaceInteraction::to_world_mueller(M, wi_local, wo_local)]: the local matrix's bases are the Stokes bases of its local
+ * directions; carried to world space they are rotated onto the Stokes bases of the world directions */
+static mueller_d to_world_mueller_d(const mueller_d *M, dv3 s, dv3 t, dv3 n, dv3 wi_local, dv3 wo_local)
+{
+    const dv3 wi = dv_frame(s, t, n, wi_local), wo = dv_frame(s, t, n, wo_local);
+    return rotate_mueller_basis_d(M, wi, dv_frame(s, t, n, stokes_basis_d(wi_local)), stokes_basis_d(wi),
+                                  wo, dv_frame(s, t, n, stokes_basis_d(wo_local)), stokes_basis_d(wo));
+}
+
+/* The reflection amplitudes of an interface for light arriving at cos_i (>= 0: from outside) [fresnel.h: fresnel_polarized].
+ * eta complex (conductors) or real (dielectrics, whose inside sees 1 / eta; beyond the critical angle cos_t = +i q).
+ * Returns |cos_t| through *cos_t_abs (0 under total internal reflection) and the relative index seen from the incident side. */
+static void fresnel_amplitudes_d(double cos_i, double complex eta, double complex *a_s, double complex *a_p,
+                                 double *cos_t_abs, double complex *eta_inc)
+{
+    const double complex e = cos_i >= 0.0 ? eta : 1.0 / eta;
+    const double ci = fabs(cos_i), sin2 = 1.0 - ci * ci;
+    double complex ct;
+    if (cimag(e) == 0.0) {                      /* a real index: Snell, or the evanescent wave */
+        const double ct2 = 1.0 - sin2 / (creal(e) * creal(e));
+        ct = ct2 >= 0.0 ? sqrt(ct2) : I * sqrt(-ct2);
+    } else {
+        ct = csqrt(1.0 - sin2 / (e * e));
+    }
+    *a_s = (ci - e * ct) / (ci + e * ct);
+    *a_p = (ct - e * ci) / (ct + e * ci);
+    if (eta == 1.0) *a_s = *a_p = 0.0;          /* index matched: nothing is reflected */
+    *cos_t_abs = cimag(ct) == 0.0 ? creal(ct) : 0.0;
+    *eta_inc = e;
+}
+/* [mueller.h: specular_reflection(cos_i, eta)]: r_s = |a_s|^2, r_p = |a_p|^2, the phase delta = arg(a_s conj(a_p)) */
+static mueller_d reflection_mueller_d(double cos_i, double complex eta)
+{
+    double complex as, ap, ei; double ct;
+    fresnel_amplitudes_d(cos_i, eta, &as, &ap, &ct, &ei);
+    const double rs = creal(as * conj(as)), rp = creal(ap * conj(ap));
+    const double complex z = as * conj(ap);
+    const double c = sqrt(rs * rp), mag = cabs(z);
+    const double cd = (c > 0.0 && mag > 0.0) ? creal(z) / mag : 0.0, sd = (c > 0.0 && mag > 0.0) ? cimag(z) / mag : 0.0;
+    mueller_d M = md_zero();
+    M.e[0][0] = M.e[1][1] = 0.5 * (rs + rp);
+    M.e[0][1] = M.e[1][0] = 0.5 * (rs - rp);
+    M.e[2][2] = M.e[3][3] = c * cd;
+    M.e[2][3] = c * sd; M.e[3][2] = -c * sd;
+    return M;
+}
+/* [mueller.h: specular_transmission(cos_i, eta)], eta real: the transmitted amplitudes t_s = 2 cos_i / (cos_i + eta cos_t),
+ * t_p = 2 cos_i / (cos_t + eta cos_i) and the radiometric factor eta cos_t / cos_i; zero under total internal reflection and
+ * at |cos_i| <= 1e-8 */
+static mueller_d transmission_mueller_d(double cos_i, double eta)
+{
+    double complex as, ap, e; double ct;
+    fresnel_amplitudes_d(cos_i, eta, &as, &ap, &ct, &e);
+    mueller_d M = md_zero();
+    const double ci = fabs(cos_i), n = creal(e);
+    if (!(ci > 1e-8) || !(ct > 0.0)) return M;
+    const double ts = 2.0 * ci / (ci + n * ct), tp = 2.0 * ci / (ct + n * ci), k = n * ct / ci;
+    M.e[0][0] = M.e[1][1] = 0.5 * k * (ts * ts + tp * tp);
+    M.e[0][1] = M.e[1][0] = 0.5 * k * (ts * ts - tp * tp);
+    M.e[2][2] = M.e[3][3] = k * ts * tp;
+    return M;
+}
+/* A specular interface's matrix has its s axes perpendicular to the plane of incidence around the (micro)normal m: light
+ * arrives along -wo and leaves along wi (radiance transport), s_in = m x (-wo), s_out = m x wi, both (1, 0, 0) when the
+ * directions are collinear with m.  Re-expressed in the implicit Stokes bases of -wo and wi (conductor.cpp, roughconductor.cpp,
+ * dielectric.cpp, polarized branches). */
+static mueller_d interface_in_local_bases_d(const mueller_d *M, dv3 m, dv3 wo, dv3 wi)
+{
+    const dv3 fin = dv_neg(wo);
+    dv3 s_in = dv_cross(m, fin), s_out = dv_cross(m, wi);
+    if (dv_is_zero(s_in)) s_in = s_out = dv_make(1, 0, 0);
+    return rotate_mueller_basis_d(M, fin, s_in, stokes_basis_d(fin), wi, s_out, stokes_basis_d(wi));
+}
+/* [mitransient utils.py:9-21 beta_init]: the camera ray's Stokes basis turned onto cross(d, to_world * (0, 1, 0)) */
+static mueller_d beta_init_d(const mtr_camera *c, v3 d)
+{
+    const dv3 dd = dv(d), up = dv_make(c->to_world[1], c->to_world[5], c->to_world[9]);
+    return rotate_stokes_basis_d(dv_neg(dd), stokes_basis_d(dv_neg(dd)), dv_cross(dd, up));
+}
+static dv3 sh_s(const sinter *si) { return dv(si->s); }
+static dv3 sh_t(const sinter *si) { return dv(si->tt); }
+static dv3 sh_n(const sinter *si) { return dv(si->n); }
+
+/* BSDF::eval for the emitter-sampling term in the polarized variants (diffuse, roughconductor), world-frame Mueller matrix
+ * (si.to_world_mueller(value, -wo, si.wi), transientpath.py:210).  wi, wo local (f32, as the path has them). */
+static mueller_d polar_eval_d(const mtr_material *m, const sinter *si, v3 wi, v3 wo)
+{
+    mueller_d val = md_zero();
+    v3 fi = wi, fo = wo;
+    if ((m->flags & MTR_MAT_TWOSIDED) && fi.z < 0.0f) { fi.z = -fi.z; fo.z = -fo.z; }     /* [twosided.cpp] */
+    if (fi.z > 0.0f && fo.z > 0.0f) {
+        if (m->type == MTR_BSDF_DIFFUSE) val = md_diag((double)m->a[0] * (1.0 / 3.14159265358979323846) * fo.z);
+        else if (m->type == MTR_BSDF_ROUGHCONDUCTOR) {
+            const v3 H = vnormalize(V(fo.x + fi.x, fo.y + fi.y, fo.z + fi.z));       /* the half vector, as the pdf has it */
+            const int beck = (m->flags & MTR_MAT_BECKMANN) != 0u;
+            const float au = m->alpha, av = rough_alpha_v(m);
+            const double D = mf_eval(H, au, av, beck);
+            if (D != 0.0) {
+                const double G = (double)mf_smith_g1(fi, H, au, av, beck) * mf_smith_g1(fo, H, au, av, beck);
+                const dv3 h = dv(H);
+                const mueller_d F = reflection_mueller_d(dv_dot(dv(fo), h), CMPLX(m->a[0], m->b[0]));
+                val = md_scaled(interface_in_local_bases_d(&F, h, dv(fo), dv(fi)), D * G / (4.0 * fi.z) * m->c[0]);
+            }
+        }
+    }
+    return to_world_mueller_d(&val, sh_s(si), sh_t(si), sh_n(si), dv_neg(dv(wo)), dv(si->wi));
+}
+/* BSDF::sample's weight in the polarized variants, world frame (si.to_world_mueller(weight, -bs.wo, si.wi), :226).  bs is the
+ * f32 sample the path follows (bsdf_sample with the same draws); the matrix is rebuilt for it. */
+static mueller_d polar_sample_weight_d(const mtr_material *m, const sinter *si, float u1, float ua, float ub, const bsample *bs)
+{
+    mueller_d w = md_zero();
+    v3 wi = si->wi, wo = bs->wo;
+    if ((m->flags & MTR_MAT_TWOSIDED) && wi.z < 0.0f) { wi.z = -wi.z; wo.z = -wo.z; }   /* the lobe's own (flipped) frame */
+    const dv3 n = dv_make(0, 0, 1);
+    switch (m->type) {
+    case MTR_BSDF_DIFFUSE:
+        if (bs->w[0] != 0.0f) w = md_diag(m->a[0]);
+        break;
+    case MTR_BSDF_CONDUCTOR:
+        if (wi.z > 0.0f) {
+            const mueller_d F = reflection_mueller_d(wo.z, CMPLX(m->a[0], m->b[0]));
+            w = md_scaled(interface_in_local_bases_d(&F, n, dv(wo), dv(wi)), m->c[0]);
+        }
+        break;
+    case MTR_BSDF_DIELECTRIC: {
+        if (!(bs->pdf > 0.0f)) break;
+        float r, ct, eit, eti;
+        fresnel_dielectric(wi.z, m->int_ior / m->ext_ior, &r, &ct, &eit, &eti);
+        const int refl = u1 <= r;                                     /* the lobe bsdf_sample chose */
+        const double eta = (double)(m->int_ior / m->ext_ior);
+        const mueller_d F = refl ? reflection_mueller_d(wo.z, eta) : transmission_mueller_d(wo.z, eta);
+        const double k = refl ? (double)m->c[0] : (double)m->c2[0] * ((double)eti * eti);   /* (radiance: eta^2 compression) */
+        w = md_scaled(interface_in_local_bases_d(&F, n, dv(wo), dv(wi)), k / bs->pdf);
+        break; }
+    case MTR_BSDF_ROUGHCONDUCTOR:
+        if (wi.z > 0.0f && wo.z > 0.0f) {
+            float pdf;
+            const int beck = (m->flags & MTR_MAT_BECKMANN) != 0u;
+            const float au = m->alpha, av = rough_alpha_v(m);
+            const v3 mm = ggx_sample(wi, au, av, ua, ub, &pdf, beck);          /* the microfacet bsdf_sample reflected about */
+            if (pdf == 0.0f) break;
+            const dv3 h = dv(mm);
+            const mueller_d F = reflection_mueller_d(dv_dot(dv(wo), h), CMPLX(m->a[0], m->b[0]));
+            w = md_scaled(interface_in_local_bases_d(&F, h, dv(wo), dv(wi)), (double)mf_smith_g1(wo, mm, au, av, beck) * m->c[0]);
+        }
+        break;
+    default: break;
+    }
+    return to_world_mueller_d(&w, sh_s(si), sh_t(si), sh_n(si), dv_neg(dv(bs->wo)), dv(si->wi));
+}
+
+/* test hooks: the f64 building blocks, row-major 4x4 */
+static void md_put(const mueller_d *M, double *out16) { for (int i = 0; i < 16; ++i) out16[i] = M->e[i / 4][i % 4]; }
+static dv3 dv_get(const double *p) { return dv_make(p[0], p[1], p[2]); }
+void orc_polar_reflection(double cos_i, double eta_r, double eta_i, double *out16)
+{
+    const mueller_d M = reflection_mueller_d(cos_i, CMPLX(eta_r, eta_i)); md_put(&M, out16);
+}
+void orc_polar_transmission(double cos_i, double eta, double *out16)
+{
+    const mueller_d M = transmission_mueller_d(cos_i, eta); md_put(&M, out16);
+}
+void orc_polar_rotate_basis(const double *fwd3, const double *cur3, const double *tgt3, double *out16)
+{
+    const mueller_d M = rotate_stokes_basis_d(dv_get(fwd3), dv_get(cur3), dv_get(tgt3)); md_put(&M, out16);
+}
+void orc_polar_stokes_basis(const double *w3, double *out3)
+{
+    const dv3 b = stokes_basis_d(dv_get(w3)); out3[0] = b.x; out3[1] = b.y; out3[2] = b.z;
+}
+void orc_polar_to_world_mueller(const double *M16, const double *stn9, const double *wi3, const double *wo3, double *out16)
+{
+    mueller_d M;
+    for (int i = 0; i < 16; ++i) M.e[i / 4][i % 4] = M16[i];
+    const mueller_d R = to_world_mueller_d(&M, dv_get(stn9), dv_get(stn9 + 3), dv_get(stn9 + 6), dv_get(wi3), dv_get(wo3));
+    md_put(&R, out16);
+}
+
+/* ------------------------------------------------------------------ */
 /* Film  (transient_hdr_film.py:250-276, transient_image_block.py:103-151) */
 /* ------------------------------------------------------------------ */
 typedef struct { uint64_t closest, shadow, bounces, splats; } lane_counters;
 typedef struct {
     const mtr_film_desc *f; float *transient; float *steady;
     orc_splat_rec *log; uint64_t log_cap; uint64_t *log_n;
+    uint8_t *rr_near;            /* polarized renders: per film pixel, 1 where a roulette draw lay within 1e-5 of rr_prob */
 } film_t;
 
 int orc_bin_index(float distance, float start_opl, float bin_width_opl, uint32_t T)
@@ -1242,6 +1500,26 @@ static void add_transient_l(film_t *F, uint32_t px, uint32_t py, float distance,
     }
 }
 
+/* the polarized film (MTR_FLAG_POLARIZED): S0..S3 in the four channels of a bin; the f64 Stokes vector times sample_scale is
+ * rounded to f32 once.  Counted as add_transient counts: nonzero, a valid bin, inside the film */
+static void add_stokes(film_t *F, uint32_t px, uint32_t py, float distance, const double S[4], float sample_scale, lane_counters *C)
+{
+    const mtr_film_desc *f = F->f;
+    float val[4];
+    for (int k = 0; k < 4; ++k) val[k] = (float)(S[k] * (double)sample_scale);
+    if (val[0] == 0.0f && val[1] == 0.0f && val[2] == 0.0f && val[3] == 0.0f) return;
+    int bin = orc_bin_index(distance, f->start_opl, f->bin_width_opl, f->temporal_bins);
+    if (bin < 0) return;
+    uint32_t x = px - f->crop_offset_x, y = py - f->crop_offset_y;
+    if (!(x < f->width && y < f->height)) return;
+    size_t index = film_cell(f, x, y, 0, 0, (uint32_t)bin) * 4u;
+    for (int k = 0; k < 4; ++k) {
+#pragma omp atomic
+        F->transient[index + k] += val[k];
+    }
+    C->splats += 1;
+}
+
 /* ------------------------------------------------------------------ */
 /* Sensor  [mitsuba3: ADIntegrator.sample_rays (python/ad/integrators/common.py),
  *          src/sensors/perspective.cpp sample_ray]                    */
@@ -1307,6 +1585,10 @@ static void trace_lane(const orc_scene *sc, const mtr_render_params *P, film_t *
     uint32_t depth = 0; float L[3] = { 0, 0, 0 }, beta[3] = { 1, 1, 1 };   /* β_init == 1, utils.py:9-21 */
     float eta = 1.0f, distance = 0.0f;
     int active = 1, prev_delta = 1; v3 prev_p = V(0, 0, 0); float prev_pdf = 1.0f;
+    /* polarized variants: the Mueller throughput and the Stokes radiance (f64), beside the f32 path state above */
+    const int polar = (P->flags & MTR_FLAG_POLARIZED) != 0u;
+    mueller_d B = md_identity(); double LS[4] = { 0, 0, 0, 0 };
+    if (polar) B = beta_init_d(&d->camera, ray.d);
 
     if (P->flags & MTR_FLAG_CAMERA_UNWARP) {                             /* :133-138 */
         hit_t h = intersect(sc, &ray, use_bvh); C->closest++;
@@ -1325,6 +1607,7 @@ static void trace_lane(const orc_scene *sc, const mtr_render_params *P, film_t *
 
         /* ---- direct emission :166-176 ---- */
         float Le[3] = { 0, 0, 0 };
+        double LeS[4] = { 0, 0, 0, 0 }, LrS[4] = { 0, 0, 0, 0 };
         if (em >= 0 && !(P->flags & MTR_FLAG_DISCARD_DIRECT_LIGHT)) {
             /* ds = DirectionSample3f(scene, si, ref=prev_si) */
             v3 rel = vsub(si.p, prev_p);
@@ -1344,8 +1627,12 @@ static void trace_lane(const orc_scene *sc, const mtr_render_params *P, film_t *
             /* emitter.eval(si): radiance where cos_theta(si.wi) > 0 [AreaLight::eval] */
             if (si.wi.z > 0.0f)
                 for (int k = 0; k < 3; ++k) Le[k] = (beta[k] * mis) * d->emitters[em].radiance[k];
+            /* polarized: beta * Spectrum(mis) * depolarizer(radiance) applied to (1, 0, 0, 0) — column 0 of beta */
+            if (polar && si.wi.z > 0.0f)
+                for (int k = 0; k < 4; ++k) LeS[k] = B.e[k][0] * (double)mis * d->emitters[em].radiance[0];
         }
-        add_transient(F, px, py, distance, Le, sample_scale, lane, depth, 0, C);   /* :179-180 */
+        if (polar) add_stokes(F, px, py, distance, LeS, sample_scale, C);
+        else add_transient(F, px, py, distance, Le, sample_scale, lane, depth, 0, C);   /* :179-180 */
 
         /* ---- emitter sampling :185-218 ---- */
         active_next &= (depth + 1 < max_depth) && si.valid;
@@ -1417,9 +1704,15 @@ static void trace_lane(const orc_scene *sc, const mtr_render_params *P, film_t *
                 float bv[3], bpdf; bsdf_eval_pdf(mat, si.wi, wo, bv, &bpdf);
                 float mis_em = mis_weight(pdf, bpdf);                   /* ds.delta == false for area lights */
                 for (int k = 0; k < 3; ++k) Lr[k] = ((beta[k] * mis_em) * bv[k]) * emw[k];
+                if (polar) {            /* beta * Spectrum(mis_em) * to_world_mueller(bsdf value) * depolarizer(em_weight) */
+                    const mueller_d V = polar_eval_d(mat, &si, si.wi, wo);
+                    const mueller_d BV = md_mul(&B, &V);
+                    for (int k = 0; k < 4; ++k) LrS[k] = BV.e[k][0] * (double)mis_em * emw[0];
+                }
             }
         }
-        add_transient(F, px, py, distance + ds_dist * eta, Lr, sample_scale, lane, depth, 1, C);   /* :216-218 */
+        if (polar) add_stokes(F, px, py, distance + ds_dist * eta, LrS, sample_scale, C);
+        else add_transient(F, px, py, distance + ds_dist * eta, Lr, sample_scale, lane, depth, 1, C);   /* :216-218 */
 
         /* ---- BSDF sampling :222-233 ---- */
         float s1 = pcg32_next_f32(&rng);
@@ -1427,12 +1720,17 @@ static void trace_lane(const orc_scene *sc, const mtr_render_params *P, film_t *
         bsample bs; memset(&bs, 0, sizeof bs); bs.eta = 1.0f;
         if (active_next) bsdf_sample(mat, si.wi, s1, s2a, s2b, &bs);
         for (int k = 0; k < 3; ++k) L[k] = (L[k] + Le[k]) + Lr[k];      /* :230 */
+        for (int k = 0; k < 4; ++k) LS[k] += LeS[k] + LrS[k];
         if (active_next) {
             v3 wo_w = to_world(&si, bs.wo);
             ray.o = offset_p(&si, wo_w); ray.d = wo_w; ray.maxt = INFINITY;   /* si.spawn_ray :231 */
         }
         eta *= bs.eta;                                                   /* :232 */
         for (int k = 0; k < 3; ++k) beta[k] *= bs.w[k];                  /* :233 */
+        if (polar) {                                                     /* beta = beta * to_world_mueller(bsdf_weight) */
+            const mueller_d W = active_next ? polar_sample_weight_d(mat, &si, s1, s2a, s2b, &bs) : md_zero();
+            B = md_mul(&B, &W);
+        }
         prev_p = si.p; prev_pdf = bs.pdf; prev_delta = bs.delta;   /* :237-240 */
 
         /* ---- stopping criterion :245-257 ---- */
@@ -1447,19 +1745,31 @@ static void trace_lane(const orc_scene *sc, const mtr_render_params *P, film_t *
         }
         float rr_u = pcg32_next_f32(&rng);                               /* :256 */
         int rr_continue = rr_u < rr_prob;
+        if (polar) {             /* the same criterion on unpolarized_spectrum(beta) = M00, in f64 (the f32 beta above is unused) */
+            const double m00 = B.e[0][0], p_rr = fmin(m00 * ((double)eta * eta), (double)0.95f);
+            active_next = (depth + 1 < max_depth) && si.valid && m00 != 0.0 && p_rr > 0.0;
+            if (rr_active) B = md_scaled(B, p_rr > 0.0 ? 1.0 / p_rr : 0.0);
+            rr_continue = rr_u < p_rr;
+            /* a decision the product takes on f32 M00 may go the other way within its rounding: report the pixel */
+            if (rr_active && active_next && F->rr_near && fabs((double)rr_u - p_rr) <= 1e-5 * p_rr) {
+                uint32_t x = px - f->crop_offset_x, y = py - f->crop_offset_y;
+                if (x < f->width && y < f->height) F->rr_near[(size_t)y * f->width + x] = 1;
+            }
+        }
         active_next &= (!rr_active) || rr_continue;
 
         if (si.valid) depth += 1;                                        /* :318 */
         active = active_next;                                            /* :319 */
     }
-    /* steady splat: block.put(pos, [L.r, L.g, L.b, 1]) common.py:187-200 */
+    /* steady splat: block.put(pos, [L.r, L.g, L.b, 1]) common.py:187-200; polarized: (S0, S1, S2, 1) */
     if (F->steady) {
         uint32_t x = px - f->crop_offset_x, y = py - f->crop_offset_y;
         if (x < f->width && y < f->height) {
             size_t i = ((size_t)y * f->width + x) * 4u;
             for (int k = 0; k < 3; ++k) {
+                const float v = polar ? (float)LS[k] : L[k];
 #pragma omp atomic
-                F->steady[i + k] += L[k];
+                F->steady[i + k] += v;
             }
 #pragma omp atomic
             F->steady[i + 3] += 1.0f;
@@ -1887,11 +2197,12 @@ static void trace_lane_nlos(const orc_scene *sc, const nlos_scene *N, const mtr_
 /* Public entry points                                                 */
 /* ------------------------------------------------------------------ */
 static int g_default_threads = 0;
-int orc_render(const mtr_scene_desc *d, const mtr_render_params *P, float *transient_hwt4, float *steady_hw4,
-               mtr_counters *out, int n_threads, int use_bvh,
-               orc_splat_rec *log, uint64_t log_cap, uint64_t *log_n)
+static int render_impl(const mtr_scene_desc *d, const mtr_render_params *P, float *transient_hwt4, float *steady_hw4,
+                       mtr_counters *out, int n_threads, int use_bvh,
+                       orc_splat_rec *log, uint64_t log_cap, uint64_t *log_n, uint8_t *rr_near)
 {
     if (!d || !P || !transient_hwt4) return -1;
+    if ((P->flags & MTR_FLAG_POLARIZED) && (d->nlos || d->film.n_frequencies || d->film.laser_scan_width)) return -1;
     if (P->spp_total == 0 || P->spp_end > P->spp_total || P->spp_begin > P->spp_end) return -1;
     if ((uint64_t)d->film.crop_width * d->film.crop_height * P->spp_total > (1ull << 32)) return -2;   /* common.py:51 */
     if (P->pixel_end > d->film.crop_width * d->film.crop_height || P->pixel_begin > P->pixel_end) return -1;
@@ -1901,6 +2212,7 @@ int orc_render(const mtr_scene_desc *d, const mtr_render_params *P, float *trans
     film_t F; memset(&F, 0, sizeof F);
     F.f = &d->film; F.transient = transient_hwt4; F.steady = steady_hw4;
     uint64_t zero = 0; F.log = log; F.log_cap = log_cap; F.log_n = log_n ? log_n : &zero;
+    F.rr_near = rr_near;
     if (log_n) *log_n = 0;
     nlos_scene NS; memset(&NS, 0, sizeof NS);
     if (d->nlos) nlos_build(&NS, &sc, use_bvh);
@@ -1934,6 +2246,22 @@ int orc_render(const mtr_scene_desc *d, const mtr_render_params *P, float *trans
     if (d->nlos) nlos_free(&NS);
     free_scene(&sc);
     return 0;
+}
+int orc_render(const mtr_scene_desc *d, const mtr_render_params *P, float *transient_hwt4, float *steady_hw4,
+               mtr_counters *out, int n_threads, int use_bvh,
+               orc_splat_rec *log, uint64_t log_cap, uint64_t *log_n)
+{
+    return render_impl(d, P, transient_hwt4, steady_hw4, out, n_threads, use_bvh, log, log_cap, log_n, NULL);
+}
+/* the polarized render (MTR_FLAG_POLARIZED whatever P->flags says): transient (H, W, T, 4) = S0..S3, steady (H, W, 4) =
+ * (S0, S1, S2, weight), and rr_near (H, W) bytes, set where a roulette draw lay within 1e-5 (relative) of rr_prob */
+int orc_render_polarized(const mtr_scene_desc *d, const mtr_render_params *P, float *transient_hwt4, float *steady_hw4,
+                         mtr_counters *out, int n_threads, int use_bvh, uint8_t *rr_near)
+{
+    if (!P) return -1;
+    mtr_render_params Q = *P;
+    Q.flags |= MTR_FLAG_POLARIZED;
+    return render_impl(d, &Q, transient_hwt4, steady_hw4, out, n_threads, use_bvh, NULL, 0, NULL, rr_near);
 }
 
 /* develop (transient_hdr_film.py:220-248; steady hdrfilm: sum / weight) */

@@ -40,6 +40,17 @@ def lib():
                                  C.POINTER(_cabi.mtr_counters), C.c_int, C.c_int,
                                  C.POINTER(orc_splat_rec), C.c_uint64, C.POINTER(C.c_uint64)]
         L.orc_render.restype = C.c_int
+        L.orc_render_polarized.argtypes = [C.POINTER(_cabi.mtr_scene_desc), C.POINTER(_cabi.mtr_render_params), fp, fp,
+                                           C.POINTER(_cabi.mtr_counters), C.c_int, C.c_int, C.POINTER(C.c_uint8)]
+        L.orc_render_polarized.restype = C.c_int
+        dp = C.POINTER(C.c_double)
+        L.orc_polar_reflection.argtypes = [C.c_double, C.c_double, C.c_double, dp]
+        L.orc_polar_transmission.argtypes = [C.c_double, C.c_double, dp]
+        L.orc_polar_rotate_basis.argtypes = [dp, dp, dp, dp]
+        L.orc_polar_stokes_basis.argtypes = [dp, dp]
+        L.orc_polar_to_world_mueller.argtypes = [dp, dp, dp, dp, dp]
+        for n in ("reflection", "transmission", "rotate_basis", "stokes_basis", "to_world_mueller"):
+            getattr(L, "orc_polar_" + n).restype = None
         L.orc_develop.argtypes = [C.POINTER(_cabi.mtr_film_desc), fp, fp, fp, fp]
         L.orc_develop.restype = None
         L.orc_splat_add.argtypes = [C.POINTER(_cabi.mtr_film_desc), C.c_uint64, u32p, fp, fp, fp, fp, fp, u32p, u32p]
@@ -112,6 +123,67 @@ def render(scene_data, params: _cabi.mtr_render_params, n_threads=0, use_bvh=Fal
                                                   ("r", "f4"), ("g", "f4"), ("b", "f4"), ("opl", "f4")]))[:n].copy()
         return t4, s4, cnt.as_dict(), arr
     return t4, s4, cnt.as_dict()
+
+
+def render_polarized(scene_data, params: _cabi.mtr_render_params, n_threads=0, use_bvh=False, out=None):
+    """The polarized render (f64 Mueller algebra over the f32 path): (transient (H,W,T,4) = S0..S3, steady (H,W,4) = (S0, S1,
+    S2, weight), counters dict, rr_near (H,W) bool — the pixels where a Russian-roulette draw lay within 1e-5 of rr_prob, whose
+    f32 decision may differ).  ``out=(t4, s4)`` accumulates into existing buffers."""
+    f = scene_data.film
+    t4, s4 = out if out is not None else alloc_film(f)
+    cnt = _cabi.mtr_counters()
+    near = np.zeros((f.height, f.width), np.uint8)
+    d = scene_data.desc()
+    rc = lib().orc_render_polarized(C.byref(d), C.byref(params), _fp(t4), _fp(s4), C.byref(cnt), n_threads, int(use_bvh),
+                                    near.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise RuntimeError(f"orc_render_polarized failed ({rc})")
+    return t4, s4, cnt.as_dict(), near.astype(bool)
+
+
+def _d(a, n):
+    a = np.ascontiguousarray(a, np.float64).reshape(n)
+    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _out(n):
+    a = np.zeros(n, np.float64)
+    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def polar_reflection(cos_i, eta):
+    """f64 Mueller matrix of specular reflection; eta complex (conductor) or real (dielectric, cos_i < 0 inside)"""
+    eta = complex(eta)
+    o, op = _out(16)
+    lib().orc_polar_reflection(float(cos_i), eta.real, eta.imag, op)
+    return o.reshape(4, 4)
+
+
+def polar_transmission(cos_i, eta):
+    o, op = _out(16)
+    lib().orc_polar_transmission(float(cos_i), float(eta), op)
+    return o.reshape(4, 4)
+
+
+def polar_rotate_basis(fwd, cur, tgt):
+    (f, fp_), (c, cp), (t, tp) = _d(fwd, 3), _d(cur, 3), _d(tgt, 3)
+    o, op = _out(16)
+    lib().orc_polar_rotate_basis(fp_, cp, tp, op)
+    return o.reshape(4, 4)
+
+
+def polar_stokes_basis(w):
+    a, ap = _d(w, 3)
+    o, op = _out(3)
+    lib().orc_polar_stokes_basis(ap, op)
+    return o
+
+
+def polar_to_world_mueller(M, frame_stn, wi, wo):
+    (m, mp), (f, fp_), (a, ap), (b, bp) = _d(M, 16), _d(frame_stn, 9), _d(wi, 3), _d(wo, 3)
+    o, op = _out(16)
+    lib().orc_polar_to_world_mueller(mp, fp_, ap, bp, op)
+    return o.reshape(4, 4)
 
 
 def develop(film_desc, t4=None, s4=None):

@@ -1,14 +1,18 @@
-"""The *_mono_polarized variants on the MI355X: k_wf_polar_bounce + k_wf_polar_scatter against the host build of the same
-arithmetic (tests/host_polarized.cpp over mtr_polar.h) at identical (seed, lane); the mode rules; values outside the
-fixed-point range through the Stokes scatter; the reference notebook's cells (cornell-box/cbox_polarized.xml, `Au`
-substituted as in tests/test_polarized.py)."""
+"""The *_mono_polarized variants on the MI355X: k_wf_polar_bounce + k_wf_polar_scatter against the CPU oracle's f64 polarized
+path (oracle/mtr_oracle.c) and the host build of the same arithmetic (tests/host_polarized.cpp over mtr_polar.h) at identical
+(seed, lane) — per polarized lobe and at the wavefront path's edges: crop windows and ragged films, the depth / roulette
+matrix, camera_unwarp and discard_direct_light, the three seedings, sample chunks, one sample per pixel, record-list overflow,
+rows too long for LDS, a workspace reallocated between renders, a scene in HBM, sample and pixel shards; the mode rules;
+values outside the fixed-point range through the Stokes scatter; the reference notebook's cells
+(cornell-box/cbox_polarized.xml, `Au` substituted as in tests/test_polarized.py)."""
 import math
 
 import numpy as np
 import pytest
 
 from conftest import rel_l2
-from test_polarized import build_host_polarized, figure, hp_render, load_cbox_polarized, sign_agreement
+from test_polarized import (BSDF_KINDS, GOLD_ETA, GOLD_K, assert_matches_oracle, bsdf_scene, build_host_polarized, figure,
+                            hp_render, load_cbox_polarized, oracle_render, sign_agreement)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5          # the bar of every GPU / CPU parity test here: the GPU adds a pixel's samples in another order
@@ -52,6 +56,7 @@ def test_gpu_matches_the_host_build(hp, res, spp, seed):
     assert np.abs(t[..., 1:]).max() > 0
     for k in COUNTERS:
         assert c[k] == hc[k], k
+    assert_matches_oracle(t, s, c, oracle_render(scene, seed=seed, spp=spp))
 
 
 def test_gpu_diffuse_box_is_the_unpolarized_render():
@@ -79,6 +84,36 @@ def test_modes():
     integ.amd_mode = "fused"
     with pytest.raises(Exception, match="wavefront"):
         integ.render(scene, spp=4)
+    # deterministic rows do not exist for the Stokes film: refused, not ignored — by the integrator and by the C-ABI
+    import ctypes as C
+    import torch
+    import mitransient_amd.mi as mi
+    from mitransient_amd import _cabi
+    integ.amd_mode = "wavefront"
+    integ.deterministic = True
+    with pytest.raises(ValueError, match="amd_deterministic"):
+        mi.render(scene, spp=4)
+    integ.deterministic = False
+    p = integ.render_params(scene.sensors()[0].film(), 0, 4)
+    p.flags |= _cabi.MTR_FLAG_DETERMINISTIC
+    t4 = torch.zeros((8, 8, 400, 4), dtype=torch.float32, device="cuda")
+    s4 = torch.zeros((8, 8, 4), dtype=torch.float32, device="cuda")
+    lib = _cabi.load_library()
+    ctx, sc = C.c_void_p(), C.c_void_p()
+    assert lib.mtr_ctx_create(torch.cuda.current_device(), C.byref(ctx)) == 0
+    try:
+        d = scene.data().desc()
+        assert lib.mtr_scene_create(ctx, C.byref(d), C.byref(sc)) == 0
+        try:
+            r = lib.mtr_render(sc, C.byref(p), C.c_void_p(t4.data_ptr()), C.c_void_p(s4.data_ptr()), None, None)
+            assert r == -5, r                    # MTR_ERR_UNSUPPORTED
+            assert b"MTR_FLAG_DETERMINISTIC" in lib.mtr_last_error(ctx)
+        finally:
+            lib.mtr_scene_destroy(sc)
+    finally:
+        torch.cuda.synchronize()
+        lib.mtr_ctx_destroy(ctx)
+    assert not t4.any()
 
 
 def test_steady_is_the_sum_of_the_transient_s0():
@@ -166,3 +201,123 @@ def ncc(a, b):
 def blocks(a, k=4):
     H, W, C = a.shape
     return a.reshape(H // k, k, W // k, k, C).mean(axis=(1, 3))
+
+
+# ---------------------------------------------------------------- against the oracle's f64 polarized path
+def _vs_oracle(scene, spp, seed=0, **kw):
+    s, t, c = _gpu(scene, spp, seed)
+    assert_matches_oracle(t, s, c, oracle_render(scene, seed=seed, spp=spp), **kw)
+    return s, t, c
+
+
+GOLD = {"type": "conductor", "eta": GOLD_ETA, "k": GOLD_K}
+
+
+@pytest.mark.parametrize("kind", BSDF_KINDS)
+def test_gpu_matches_the_oracle_per_bsdf(kind):
+    _vs_oracle(bsdf_scene(kind), 32, 1)
+
+
+def test_gpu_ragged_film_with_crop_window():
+    """13 x 7 film, 5 spp, a crop window with offsets: pixel -> crop mapping in polar_begin, load_state and the steady write"""
+    scene = bsdf_scene("glass", film={"width": 13, "height": 7, "crop_width": 9, "crop_height": 5, "crop_offset_x": 3,
+                                      "crop_offset_y": 1, "temporal_bins": 37})
+    s, t, _ = _vs_oracle(scene, 5, 4)
+    assert t.shape == (7, 13, 37, 4) and s.shape == (5, 9, 1)
+    assert np.all(t[5:] == 0) and np.all(t[:, 9:] == 0)          # only the crop_size corner is written
+
+
+@pytest.mark.parametrize("max_depth,rr_depth", [(0, 5), (1, 5), (2, 5), (3, 1), (12, 2), (-1, 3)])
+def test_gpu_depths_on_a_conductor_and_dielectric_scene(max_depth, rr_depth):
+    """the first-bounce special case, roulette on a Mueller M00, the live-count polling loop of max_depth -1"""
+    _vs_oracle(bsdf_scene("glass", max_depth=max_depth, rr_depth=rr_depth, back_bsdf=GOLD), 16, 2)
+
+
+@pytest.mark.parametrize("flag", ["camera_unwarp", "discard_direct_light"])
+def test_gpu_unwarp_and_discard_direct(flag):
+    _vs_oracle(bsdf_scene("roughconductor_ggx", back_bsdf=GOLD, **{flag: True}), 16, 5)
+
+
+@pytest.mark.parametrize("seeding", [{}, {"amd_pcg_initseq_plus_lane": True}, {"amd_pcg_tea64": True}],
+                         ids=["tea", "tea+lane", "tea64"])
+def test_gpu_seedings(seeding):
+    """k_wf_polar_bounce recomputes the sampler's stream from rc.flags on every reloaded path"""
+    _vs_oracle(bsdf_scene("glass", back_bsdf=GOLD, max_depth=10, **seeding), 16, 6)
+
+
+def test_gpu_sample_chunks():
+    """2 x 2 pixels at 4100 spp: two sample chunks (4096, then 4), two pixels per segment"""
+    _vs_oracle(bsdf_scene("conductor", res=2), 4100, 7)
+
+
+def test_gpu_one_sample_per_pixel():
+    """128 x 96 at 1 spp: segments cut by pixel count (1024 per segment)"""
+    _vs_oracle(bsdf_scene("roughconductor_beckmann_aniso", film={"width": 128, "height": 96}), 1, 8)
+
+
+def test_gpu_record_overflow():
+    """a closed box with a glass cube and a gold wall, paths of ~9 contributions: the per-pixel record lists (4 contributions per
+    path) overflow into the film's atomics, S3 included"""
+    scene = bsdf_scene("glass", res=8, closed=True, back_bsdf=GOLD, max_depth=-1, rr_depth=40,
+                       film={"start_opl": 0.0, "bin_width_opl": 400.0 / 64})
+    s, t, c = _vs_oracle(scene, 8, 9)
+    assert c["splats_overflow"] > 0
+    assert np.abs(t[..., 3]).max() > 0
+
+
+@pytest.mark.parametrize("bins", [9600, 9601])
+def test_gpu_rows_at_the_lds_limit(bins):
+    """9600 bins: the last count whose Stokes rows fit LDS; 9601: no record lists, every contribution a film atomic"""
+    _vs_oracle(bsdf_scene("glass", res=6, back_bsdf=GOLD, film={"temporal_bins": bins, "bin_width_opl": 16.0 / bins}), 8, 10)
+
+
+def test_gpu_workspace_follows_the_bin_count():
+    """one scene rendered with 400 -> 9601 -> 400 bins: the workspace is reallocated when the record capacity changes"""
+    import mitransient_amd.mi as mi
+    scene = bsdf_scene("glass", res=8, back_bsdf=GOLD, film={"temporal_bins": 400, "bin_width_opl": 0.04})
+    for bins in (400, 9601, 400):
+        params = mi.traverse(scene)
+        params["sensor.film.temporal_bins"] = bins
+        params["sensor.film.bin_width_opl"] = 16.0 / bins
+        params.update()
+        s, t, _ = _vs_oracle(scene, 8, 11)
+        assert t.shape == (8, 8, bins, 4)
+
+
+def test_gpu_staircase_in_hbm():
+    """staircase_like(tiles=6) polarized: k_wf_polar_bounce with the scene in HBM, cubes, a thin glass pane, twosided brass"""
+    import mitransient_amd.mi as mi
+    from mitransient_amd.scenes import staircase_like
+    mi.set_variant("llvm_ad_mono_polarized")
+    scene = mi.load_dict(staircase_like(n_steps=12, balusters=2, tiles=6, width=24, height=24, temporal_bins=64, spp=8))
+    _vs_oracle(scene, 8, 12)
+
+
+def test_gpu_sample_and_pixel_shards():
+    """sample shards and pixel shards accumulated through integ.accumulate sum to the whole render; each shard is the oracle's"""
+    import torch
+    scene = bsdf_scene("glass", res=16, back_bsdf=GOLD)
+    spp = 12
+    s_full, t_full, _ = _gpu(scene, spp, 13)
+    integ = scene.integrator()
+    sens = scene.sensors()[0]
+    film = sens.film()
+    for kw in ({"spp_range": (0, 5)}, {"spp_range": (5, 12)}, {"pixel_range": (0, 100)}, {"pixel_range": (100, 256)}):
+        passes = integ.prepare(scene, sens, 13, spp, [])
+        integ.accumulate(scene, sens, passes, spp, **kw)
+        torch.cuda.synchronize()
+        t1 = np.array(film.develop()[1])
+        p = {"spp_begin": kw["spp_range"][0], "spp_end": kw["spp_range"][1]} if "spp_range" in kw else \
+            {"pixel_begin": kw["pixel_range"][0], "pixel_end": kw["pixel_range"][1]}
+        ot = oracle_render(scene, seed=13, spp=spp, **p)[0]
+        assert rel_l2(t1, ot) <= TOL, kw
+    passes = integ.prepare(scene, sens, 13, spp, [])
+    for rng in ((0, 5), (5, 12)):
+        integ.accumulate(scene, sens, passes, spp, spp_range=rng)
+    s_a, t_a = film.develop()
+    passes = integ.prepare(scene, sens, 13, spp, [])
+    for rng in ((0, 100), (100, 256)):
+        integ.accumulate(scene, sens, passes, spp, pixel_range=rng)
+    s_b, t_b = film.develop()
+    for s_, t_ in ((s_a, t_a), (s_b, t_b)):
+        assert rel_l2(np.array(t_), t_full) <= 1e-6 and rel_l2(np.array(s_), s_full) <= 1e-6

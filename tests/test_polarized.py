@@ -1,7 +1,8 @@
 """The *_mono_polarized variants (mitransient's polarization tracking) on the CPU: the variant and ingestion surface, the
-Mueller / Fresnel building blocks of mtr_polar.h against f64 numpy, and whole renders of the host build of the same
-arithmetic (tests/host_polarized.cpp) — the diffuse Cornell box against the unpolarized host build, Brewster's angle,
-two conductor reflections against Jones calculus, and a rolled camera."""
+Mueller / Fresnel building blocks of mtr_polar.h and of the CPU oracle's f64 polarized path against f64 numpy, whole renders
+of the host build of the same arithmetic (tests/host_polarized.cpp) against the oracle (oracle/mtr_oracle.c, f64 Mueller
+algebra written apart from mtr_polar.h) on a scene per polarized BSDF — and, for both implementations, the diffuse Cornell
+box against the unpolarized render, Brewster's angle, two conductor reflections against Jones calculus, and a rolled camera."""
 import ctypes as C
 import math
 import os
@@ -10,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import hh_render
+from conftest import hh_render, rel_l2
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CBOX = os.path.join(ROOT, "tests", "golden", "reference_scenes", "transient", "cornell-box")
@@ -54,6 +55,47 @@ def hp_render(lib, scene, seed=0, spp=4):
     d = sd.desc()
     assert lib.hp_render(C.byref(d), C.byref(p), t4.ctypes.data_as(FP), s4.ctypes.data_as(FP), C.byref(cnt)) == 0
     return t4, s4, cnt.as_dict()
+
+
+def oracle_render(scene, seed=0, spp=4, **params):
+    """the CPU oracle's polarized render: (H, W, T, 4) S0..S3, (H, W, 4) = (S0, S1, S2, weight), counters, and the (H, W)
+    pixels where a Russian-roulette decision lay within 1e-5 of its threshold.  ``params``: render_params' keyword arguments"""
+    from oracle import oracle
+    p = scene.integrator().render_params(scene.sensors()[0].film(), seed, spp, **params)
+    return oracle.render_polarized(scene.data(), p, use_bvh=True)
+
+
+# the parity bar of every polarized comparison with the oracle (the GPU's against the host build too)
+TOL, TOL_CHANNEL = 1e-5, 1e-4
+COUNTERS = ("paths", "rays_closest", "rays_shadow", "splats_issued", "bounces")
+
+
+def steady_s0(s4):
+    """the developed steady image (H, W, 1): S0 / weight"""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(s4[..., 3:] > 0, s4[..., :1] / s4[..., 3:], 0.0).astype(np.float32)
+
+
+def assert_matches_oracle(t, s, counters, ref, max_near=0.01):
+    """a polarized render against the oracle's `ref` = oracle_render(...): rel-L2 <= TOL on the transient (H, W, T, 4) and the
+    steady image — (H, W, 1) developed S0 or the (H, W, 4) accumulator — and <= TOL_CHANNEL on each Stokes channel, outside the
+    pixels whose roulette decision sat on its threshold (under max_near of the film); the counters equal where none did"""
+    ot, os4, oc, near = ref
+    assert t.shape == ot.shape
+    assert near.mean() < max_near, near.mean()
+    keep = ~near
+    os_ = steady_s0(os4) if s.shape[-1] == 1 else os4
+    # (a developed steady image with a crop window is (crop_h, crop_w, 1): the accumulator's top-left corner)
+    os_, skeep = os_[:s.shape[0], :s.shape[1]], keep[:s.shape[0], :s.shape[1]]
+    assert np.abs(ot[..., 0]).max() > 0
+    assert rel_l2(t[keep], ot[keep]) <= TOL, rel_l2(t[keep], ot[keep])
+    assert rel_l2(s[skeep], os_[skeep]) <= TOL, rel_l2(s[skeep], os_[skeep])
+    for k in range(4):
+        e = rel_l2(t[keep][..., k], ot[keep][..., k])
+        assert e <= TOL_CHANNEL, (k, e)
+    if not near.any():
+        for k in COUNTERS:
+            assert counters[k] == oc[k], (k, counters[k], oc[k])
 
 
 def cbox_polarized_dict(**params):
@@ -201,6 +243,25 @@ def test_other_plugins_out_of_scope_are_refused():
         scene.data()
 
 
+def test_deterministic_rows_are_refused():
+    """amd_deterministic asks for fixed-point rows, which the Stokes film does not have: an error naming the key, not a
+    render that quietly sums f32 atomics (the C-ABI refuses MTR_FLAG_DETERMINISTIC too: tests/test_gpu_polarized.py)"""
+    import mitransient_amd.mi as mi
+    from mitransient_amd import _cabi
+    from mitransient_amd.transform import ScalarTransform4f as T
+    d = {"type": "scene", "integrator": {"type": "transient_path", "amd_deterministic": True},
+         "sensor": {"type": "perspective", "to_world": T().look_at([0, 0, 4], [0, 0, 0], [0, 1, 0]),
+                    "film": {"type": "transient_hdr_film", "width": 4, "height": 4, "temporal_bins": 8, "rfilter": {"type": "box"}}},
+         "floor": {"type": "rectangle", "bsdf": {"type": "diffuse"}}}
+    mi.set_variant("llvm_ad_mono_polarized")
+    scene = mi.load_dict(d)
+    with pytest.raises(ValueError, match="amd_deterministic"):
+        scene.integrator().render_params(scene.sensors()[0].film(), 0, 4)
+    mi.set_variant("llvm_ad_mono")                 # (the unpolarized variants keep their deterministic rows)
+    scene = mi.load_dict(d)
+    assert scene.integrator().render_params(scene.sensors()[0].film(), 0, 4).flags & _cabi.MTR_FLAG_DETERMINISTIC
+
+
 def test_multi_gpu_sharding_is_refused():
     import torch.distributed as dist
     from mitransient_amd.distributed import DistributedRenderer
@@ -318,22 +379,43 @@ def test_total_internal_reflection_has_a_phase(hp):
 
 
 # ---------------------------------------------------------------- 3. the diffuse Cornell box
+def host_renderer(lib):
+    return lambda scene, seed=0, spp=4: hp_render(lib, scene, seed=seed, spp=spp)
+
+
+def oracle_renderer(scene, seed=0, spp=4):
+    return oracle_render(scene, seed=seed, spp=spp)[:3]
+
+
 def test_diffuse_cornell_box_matches_the_unpolarized_render(hp, host_harness):
     """S0 of the polarized path IS the unpolarized render on a scene of depolarizers: every Mueller product's M00 is the
     scalar product (its other terms are exact zeros) and the sampler is consumed in the same order — bit equality"""
+    _check_diffuse_box(host_renderer(hp), lambda sd, p: hh_render(host_harness, sd, p), exact=True)
+
+
+def test_diffuse_cornell_box_matches_the_unpolarized_render_in_the_oracle():
+    """the same for the oracle, whose polarized S0 is f64 arithmetic against its own f32 unpolarized render: within 1e-6"""
+    from oracle import oracle
+    _check_diffuse_box(oracle_renderer, lambda sd, p: oracle.render(sd, p, use_bvh=True), exact=False)
+
+
+def _check_diffuse_box(render, render_unpolarized, exact):
     import mitransient_amd.mi as mi
     path = os.path.join(CBOX, "cbox_diffuse.xml")
     mi.set_variant("llvm_ad_mono")
     su = mi.load_file(path, res=16, spp=8)
     p = su.integrator().render_params(su.sensors()[0].film(), 5, 8)
-    tu, s4u, cu = hh_render(host_harness, su.data(), p)
+    tu, s4u, cu = render_unpolarized(su.data(), p)
     mi.set_variant("llvm_ad_mono_polarized")
     sp = mi.load_file(path, res=16, spp=8)
-    tp, s4p, cp = hp_render(hp, sp, seed=5, spp=8)
+    tp, s4p, cp = render(sp, seed=5, spp=8)
     assert tu.shape == tp.shape
-    np.testing.assert_array_equal(tp[..., 0], tu[..., 0])
     assert not np.any(tp[..., 1:])
-    np.testing.assert_array_equal(s4p[..., 0], s4u[..., 0])
+    if exact:
+        np.testing.assert_array_equal(tp[..., 0], tu[..., 0])
+        np.testing.assert_array_equal(s4p[..., 0], s4u[..., 0])
+    else:
+        assert rel_l2(tp[..., 0], tu[..., 0]) <= 1e-6 and rel_l2(s4p[..., 0], s4u[..., 0]) <= 1e-6
     np.testing.assert_array_equal(s4p[..., 3], s4u[..., 3])
     np.testing.assert_array_equal(tp[..., 0] != 0, tu[..., 0] != 0)
     for k in ("paths", "rays_closest", "rays_shadow", "splats_issued", "bounces"):
@@ -380,8 +462,16 @@ def _dolp(S):
 
 
 def test_brewster_reflection_is_linearly_polarized(hp):
+    _check_brewster(host_renderer(hp))
+
+
+def test_brewster_reflection_is_linearly_polarized_in_the_oracle():
+    _check_brewster(oracle_renderer)
+
+
+def _check_brewster(render):
     scene, cam, d, up = _brewster_scene()
-    t4, s4, _ = hp_render(hp, scene, spp=64)
+    t4, s4, _ = render(scene, spp=64)
     # all of it in the analytically known bin: (D_CAM - near) + D_LIGHT lies in the middle of bin 2
     per_bin = np.abs(t4[..., 0]).sum(axis=(0, 1))
     assert per_bin[2] > 0 and per_bin.sum() == per_bin[2]
@@ -416,15 +506,27 @@ def test_away_from_brewster_the_reflection_is_partly_polarized(hp):
     assert abs(S[1] / S[0] - (rs - rp) / (rs + rp)) < 2e-3
 
 
-@pytest.mark.parametrize("roll", [15.0, 30.0, -40.0, 90.0])
+ROLLS = [15.0, 30.0, -40.0, 90.0]
+
+
+@pytest.mark.parametrize("roll", ROLLS)
 def test_camera_roll_rotates_the_linear_components(hp, roll):
     """rolling the camera by alpha about its axis rotates (S1, S2) by 2 alpha; S0 and S3 stay.  The sense is the one beta_init
     implies: psi = the angle from the camera's basis cross(d, up) to the polarization direction x, positive about the
     propagation direction -d (mueller.h rotate_stokes_basis), S = S0 DoLP (cos 2 psi, sin 2 psi)"""
+    _check_camera_roll(host_renderer(hp), roll)
+
+
+@pytest.mark.parametrize("roll", ROLLS)
+def test_camera_roll_rotates_the_linear_components_in_the_oracle(roll):
+    _check_camera_roll(oracle_renderer, roll)
+
+
+def _check_camera_roll(render, roll):
     s0, *_ = _brewster_scene(0.0)
     s1, cam, d, up = _brewster_scene(roll)
-    t0, _, _ = hp_render(hp, s0, spp=64)
-    t1, _, _ = hp_render(hp, s1, spp=64)
+    t0, _, _ = render(s0, spp=64)
+    t1, _, _ = render(s1, spp=64)
     A = t0.sum(axis=(0, 1, 2)).astype(np.float64)
     B = t1.sum(axis=(0, 1, 2)).astype(np.float64)
     assert abs(B[0] - A[0]) <= 1e-3 * A[0] and abs(B[3] - A[3]) <= 1e-6 * A[0]
@@ -448,6 +550,14 @@ def _jones_reflect(E, fwd_in, n, fwd_out, eta):
 
 
 def test_two_conductor_reflections_against_jones_calculus(hp):
+    _check_two_conductors(host_renderer(hp))
+
+
+def test_two_conductor_reflections_against_jones_calculus_in_the_oracle():
+    _check_two_conductors(oracle_renderer)
+
+
+def _check_two_conductors(render):
     """camera -> gold mirror 1 -> gold mirror 2 -> area light, the two planes of incidence not coplanar (and not the symmetric
     45 / 45 degree crossing, whose polarizations cancel exactly).  Unpolarized light picks up linear and circular polarization;
     the f64 Jones prediction in the camera's Stokes frame (x = cross(d, up), y = fwd x x, fwd = -d; S3 = -2 Im(Ex conj(Ey)), the
@@ -471,7 +581,7 @@ def test_two_conductor_reflections_against_jones_calculus(hp):
         "m2": {"type": "rectangle", "to_world": T().look_at(list(P2), list(P2 + n2), [0, 0, 1]).scale(0.3), "bsdf": gold},
         "light": {"type": "rectangle", "to_world": T().look_at(list(P3), list(P2), [1, 0, 0]), "emitter": {"type": "area", "radiance": 1.0}},
     })
-    t4, s4, _ = hp_render(hp, scene, spp=16)
+    t4, s4, _ = render(scene, spp=16)
     per_bin = t4[..., 0].sum(axis=(0, 1))
     assert per_bin[5] > 0 and per_bin.sum() == per_bin[5]                 # opl 6 - near clip
     S = t4.sum(axis=(0, 1, 2)).astype(np.float64)
@@ -530,3 +640,152 @@ def test_steady_figure_signs(hp):
     (a1, a2), (n1, n2) = sign_agreement(S, figure("steady"))
     assert n1 > 4000 and n2 > 9000
     assert a1 >= 0.92 and a2 >= 0.92, (a1, a2)
+
+
+# ---------------------------------------------------------------- 8. the host build against the oracle's f64 polarized path
+def bsdf_scene(kind, res=16, bins=64, max_depth=8, rr_depth=5, back_bsdf=None, closed=False, film=None, **integrator):
+    """a small box for one polarized lobe: a diffuse floor and back wall, two area lights (one overhead, one to the side, seen
+    by the camera) and the lobe on a tilted cube — or, for 'twosided_back', on a tilted mirror whose front faces away from the
+    camera.  back_bsdf replaces the back wall's; closed adds a ceiling and three walls around the camera; film: film keys"""
+    import mitransient_amd.mi as mi
+    from mitransient_amd.transform import ScalarTransform4f as T
+    mi.set_variant("llvm_ad_mono_polarized")
+    bsdfs = {
+        "conductor": {"type": "conductor", "eta": GOLD_ETA, "k": GOLD_K},
+        "roughconductor_ggx": {"type": "roughconductor", "alpha": 0.2, "distribution": "ggx", "eta": 0.2, "k": 3.0},
+        "roughconductor_beckmann_aniso": {"type": "roughconductor", "alpha_u": 0.08, "alpha_v": 0.35,
+                                          "distribution": "beckmann", "eta": 1.1, "k": 2.6},
+        "glass": {"type": "dielectric", "int_ior": 1.5},
+        "twosided_back": {"type": "twosided", "bsdf": {"type": "conductor", "eta": 0.44, "k": 3.7}},
+    }
+    if kind == "twosided_back":      # the normal (0, 0, 1) turned away from the camera, then tilted towards the floor
+        obj = {"type": "rectangle", "to_world": T().translate([0, 0.8, 0]).rotate([1, 0, 0], 150).scale(0.7)}
+    else:
+        obj = {"type": "cube", "to_world": T().translate([0, 0.6, 0]).rotate([0, 1, 0], 35).rotate([1, 0, 0], 20).scale(0.5)}
+    obj["bsdf"] = bsdfs[kind]
+    integ = {"type": "transient_path", "max_depth": max_depth, "rr_depth": rr_depth}
+    integ.update(integrator)
+    film_d = {"type": "transient_hdr_film", "width": res, "height": res, "temporal_bins": bins, "start_opl": 2.0,
+              "bin_width_opl": 16.0 / bins, "rfilter": {"type": "box"}}
+    film_d.update(film or {})
+    walls = {}
+    if closed:
+        grey = {"type": "diffuse", "reflectance": 0.8}
+        walls = {"ceiling": {"type": "rectangle", "to_world": T().translate([0, 3.2, 1]).rotate([1, 0, 0], 90).scale([3, 4, 1]), "bsdf": grey},
+                 "left": {"type": "rectangle", "to_world": T().translate([-3, 1.6, 1]).rotate([0, 1, 0], 90).scale([4, 1.6, 1]), "bsdf": grey},
+                 "right": {"type": "rectangle", "to_world": T().translate([3, 1.6, 1]).rotate([0, 1, 0], -90).scale([4, 1.6, 1]), "bsdf": grey},
+                 "front": {"type": "rectangle", "to_world": T().translate([0, 1.6, 5]).rotate([0, 1, 0], 180).scale([3, 1.6, 1]), "bsdf": grey}}
+    return mi.load_dict({**walls,
+        "type": "scene",
+        "integrator": integ,
+        "sensor": {"type": "perspective", "fov": 45, "to_world": T().look_at([0, 1.2, 4], [0, 0.6, 0], [0, 1, 0]), "film": film_d},
+        "floor": {"type": "rectangle", "to_world": T().rotate([1, 0, 0], -90).scale(3), "bsdf": {"type": "diffuse", "reflectance": 0.6}},
+        "back": {"type": "rectangle", "to_world": T().translate([0, 1.5, -2]).scale([3, 1.5, 1]),
+                 "bsdf": back_bsdf or {"type": "diffuse", "reflectance": 0.4}},
+        "object": obj,
+        "light": {"type": "rectangle", "to_world": T().translate([0, 3, 0.5]).rotate([1, 0, 0], 90).scale(0.6),
+                  "emitter": {"type": "area", "radiance": 6.0}},
+        "side_light": {"type": "rectangle", "to_world": T().translate([-1.3, 1.4, 0.0]).rotate([0, 1, 0], 60).scale(0.3),
+                       "emitter": {"type": "area", "radiance": 3.0}},
+    })
+
+
+BSDF_KINDS = ["conductor", "roughconductor_ggx", "roughconductor_beckmann_aniso", "glass", "twosided_back"]
+
+
+def test_cbox_host_build_matches_the_oracle(hp):
+    scene = load_cbox_polarized(res=16)
+    t, s4, c = hp_render(hp, scene, seed=3, spp=16)
+    assert_matches_oracle(t, s4, c, oracle_render(scene, seed=3, spp=16))
+    assert np.abs(t[..., 1:3]).max() > 1e-4 * np.abs(t[..., 0]).max()
+
+
+@pytest.mark.parametrize("kind", BSDF_KINDS)
+def test_host_build_matches_the_oracle_per_bsdf(hp, kind):
+    scene = bsdf_scene(kind)
+    t, s4, c = hp_render(hp, scene, seed=1, spp=32)
+    ref = oracle_render(scene, seed=1, spp=32)
+    assert_matches_oracle(t, s4, c, ref)
+    ot = ref[0]
+    # the lobe polarizes what it reflects; circularly too where two interfaces follow each other (inside the glass cube)
+    assert np.abs(ot[..., 1:3]).max() > 1e-3 * np.abs(ot[..., 0]).max()
+    if kind == "glass":
+        assert np.abs(ot[..., 3]).max() > 1e-4 * np.abs(ot[..., 0]).max()
+
+
+def test_glass_cube_reaches_total_internal_reflection():
+    """the glass scene's paths do meet total internal reflection: at max_depth 3 the cube's inside is seen at most once
+    through; deeper paths add light that only TIR bounces inside the cube carry (a property of the scene the parity test needs)"""
+    shallow = oracle_render(bsdf_scene("glass", max_depth=4), seed=1, spp=16)[0]
+    deep = oracle_render(bsdf_scene("glass", max_depth=10), seed=1, spp=16)[0]
+    assert np.abs(deep[..., 0]).sum() > np.abs(shallow[..., 0]).sum()
+
+
+# the f64 building blocks of the oracle against the numpy helpers above (two f64 implementations: about 1e-12)
+def test_oracle_conductor_and_dielectric_reflection_against_numpy():
+    from oracle import oracle
+    for eta in (complex(GOLD_ETA, GOLD_K), complex(0.2, 3.0), complex(2.0, 5.0), 1.5, 1.33):
+        for ci in np.linspace(0.0, 1.0, 41)[1:]:
+            assert np.abs(oracle.polar_reflection(ci, eta) - reflection_mueller64(ci, eta)).max() < 1e-12, (eta, ci)
+    for ci in (-0.3, -0.5, -0.9):                     # inside glass: 1 / eta, total internal reflection below the critical angle
+        assert np.abs(oracle.polar_reflection(ci, 1.5) - reflection_mueller64(-ci, 1 / 1.5)).max() < 1e-12, ci
+
+
+def transmission_mueller64(ci, eta):
+    """f64 specular transmission (mueller.h specular_transmission): (1 + a_s)^2 and ((1 - a_p) / eta)^2 times eta cos_t / cos_i"""
+    e = eta if ci >= 0 else 1.0 / eta
+    ci = abs(ci)
+    ct2 = 1.0 - (1.0 - ci * ci) / (e * e)
+    if ct2 <= 0:
+        return np.zeros((4, 4))
+    a_s, a_p = fresnel_amplitudes64(ci, e)
+    k = e * math.sqrt(ct2) / ci
+    ts, tp = abs(1 + a_s) ** 2, abs((1 - a_p) / e) ** 2
+    a, b, c = 0.5 * k * (ts + tp), 0.5 * k * (ts - tp), k * math.sqrt(ts * tp)
+    return np.array([[a, b, 0, 0], [b, a, 0, 0], [0, 0, c, 0], [0, 0, 0, c]])
+
+
+def test_oracle_dielectric_transmission_against_numpy():
+    from oracle import oracle
+    for eta in (1.5, 1.33):
+        for ci in np.concatenate([np.linspace(-1, 0, 21)[:-1], np.linspace(0, 1, 21)[1:]]):
+            T = oracle.polar_transmission(ci, eta)
+            assert np.abs(T - transmission_mueller64(ci, eta)).max() < 1e-12, (eta, ci)
+            R = oracle.polar_reflection(ci, eta)
+            assert abs(R[0, 0] + T[0, 0] - 1.0) < 1e-12 or T[0, 0] == 0       # energy: r + t = 1 outside TIR
+
+
+def test_oracle_basis_rotation_against_numpy():
+    from oracle import oracle
+    rng = np.random.default_rng(7)
+    for _ in range(50):
+        fwd = rng.normal(size=3); fwd /= np.linalg.norm(fwd)
+        a, b = (v - fwd * (v @ fwd) for v in rng.normal(size=(2, 3)))
+        theta = math.atan2(fwd @ np.cross(a / np.linalg.norm(a), b / np.linalg.norm(b)),
+                           (a / np.linalg.norm(a)) @ (b / np.linalg.norm(b)))
+        assert np.abs(oracle.polar_rotate_basis(fwd, a, b) - rotator64(theta)).max() < 1e-12
+        sb = oracle.polar_stokes_basis(fwd)
+        assert abs(np.linalg.norm(sb) - 1) < 1e-12 and abs(sb @ fwd) < 1e-12
+
+
+def test_oracle_to_world_mueller_in_the_identity_frame_is_the_basis_change():
+    """in the frame (x, y, z) the local Stokes bases ARE the world ones: to_world_mueller is the identity; in a rotated frame it
+    is R_out M R_in^T with the angles between the carried bases and the world's (numpy, f64)"""
+    from oracle import oracle
+    rng = np.random.default_rng(8)
+    M = rng.normal(size=(4, 4))
+    wi = rng.normal(size=3); wi /= np.linalg.norm(wi)
+    wo = rng.normal(size=3); wo /= np.linalg.norm(wo)
+    assert np.abs(oracle.polar_to_world_mueller(M, np.eye(3), wi, wo) - M).max() < 1e-12
+    q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+    frame = q.T                                     # rows s, t, n
+    def basis(w):
+        s = 1.0 if w[2] >= 0 else -1.0
+        a = -1.0 / (s + w[2]); b = w[0] * w[1] * a
+        return np.array([1 + s * w[0] * w[0] * a, s * b, -s * w[0]])
+    def angle(f, c, t):
+        return math.atan2(f @ np.cross(c, t), c @ t)
+    wiw, wow = frame.T @ wi, frame.T @ wo
+    Ri = rotator64(angle(wiw, frame.T @ basis(wi), basis(wiw)))
+    Ro = rotator64(angle(wow, frame.T @ basis(wo), basis(wow)))
+    assert np.abs(oracle.polar_to_world_mueller(M, frame.reshape(-1), wi, wo) - Ro @ M @ Ri.T).max() < 1e-12
