@@ -345,6 +345,17 @@ MTR_HD float angular_falloff(const Emitter &E, float c)
     const float beam = (c >= E.cos_beam) ? 1.0f : (E.cutoff - acos_f32(c)) * E.inv_transition;
     return (c > E.cos_cutoff) ? beam : 0.0f;
 }
+// the cosine _fallof_curve takes: dr.normalize(d).z of a local direction d (:75-76).  A direction in f32 is unit only to an ulp or
+// two, and near a narrow cone's transition one ulp of the cosine moves the falloff by ~1e-4.
+MTR_HD float unit_z(f3 l) { return l.z * (1.0f / sqrtf(dot(l, l))); }
+// Frame3f(n).to_local(v) [mitsuba3: coordinate_system(n) (Duff et al. 2017)], for the falloff of -ds.d about ds.n
+MTR_HD f3 to_local_about(f3 n, f3 v)
+{
+    const float sign = copysignf(1.0f, n.z), a = -(1.0f / (sign + n.z)), b = (n.x * n.y) * a;
+    const f3 s = mk((sign_neg(n.z) ? -((n.x * n.x) * a) : (n.x * n.x) * a) + 1.0f, sign_neg(n.z) ? -b : b, sign_neg(n.z) ? n.x : -n.x);
+    const f3 t = mk(b, fmaf(n.y, n.y * a, sign), -n.y);
+    return mk(dot(v, s), dot(v, t), dot(v, n));
+}
 
 struct Camera {
     float s2c[16];
@@ -1983,7 +1994,7 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
         const bool ang = !kOneRect && E.angular != 0u;
         if (!prev_delta) {
             float dp = dot(dd, c.sn);                  // DirectionSample(scene, si, ref): ds.n = si.sh_frame.n
-            if (dp < 0.0f && (!ang || angular_falloff(E, -dp) > 0.0f)) {
+            if (dp < 0.0f && (!ang || angular_falloff(E, unit_z(to_local_about(c.sn, -dd))) > 0.0f)) {
                 float adp = fabsf(dp);
                 em_pdf = E.inv_area * (adp != 0.0f ? (dist * dist) / adp : 0.0f);
                 if (n_emitters > 1) em_pdf *= rc.inv_n_emitters;
@@ -1991,7 +2002,7 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
         }
         float mis = mis_weight(p.prev_pdf, em_pdf);
         if (ang) {
-            const float fall = angular_falloff(E, c.wi.z);
+            const float fall = angular_falloff(E, unit_z(c.wi));
             if (c.wi.z > 0.0f && fall > 0.0f)
                 pd.Le = mk((p.beta.x * mis) * (E.radiance[0] * fall), (p.beta.y * mis) * (E.radiance[1] * fall),
                            (p.beta.z * mis) * (E.radiance[2] * fall));
@@ -2033,10 +2044,10 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
         float dp = dot(dd, en), adp = fabsf(dp);
         float x = dist2 / adp;
         float pdf_dir = E.inv_area * ((fabsf(x) <= 3.402823466e+38f) ? x : 0.0f);
-        // angulararea sample_direction (angulararea.py:107-128): falloff of -ds.d in Frame3f(ds.n), the term dropped where it is
+        // angulararea sample_direction (angulararea.py:107-128): falloff of normalize(Frame3f(ds.n).to_local(-ds.d)), the term dropped where it is
         // zero, and radiance * (falloff * inv_dist^2) / ds.pdf — the reference's extra 1 / dist^2 on top of the solid-angle pdf
         const bool ang = !kOneRect && E.angular != 0u;
-        const float fall = ang ? angular_falloff(E, -dp) : 1.0f;
+        const float fall = ang ? angular_falloff(E, unit_z(to_local_about(en, -dd))) : 1.0f;
         if ((dp < 0.0f) & (pdf_dir != 0.0f) & (fall > 0.0f)) {
             f3 emw;
             if (ang) { const float inv_dist = 1.0f / dist; emw = (ld3(E.radiance) * (fall * (inv_dist * inv_dist))) / pdf_dir; }

@@ -1410,11 +1410,12 @@ void orc_polar_to_world_mueller(const double *M16, const double *stn9, const dou
 /* ------------------------------------------------------------------ */
 /* Film  (transient_hdr_film.py:250-276, transient_image_block.py:103-151) */
 /* ------------------------------------------------------------------ */
-typedef struct { uint64_t closest, shadow, bounces, splats; } lane_counters;
+typedef struct { uint64_t closest, shadow, bounces, splats, ang_near; } lane_counters;
 typedef struct {
     const mtr_film_desc *f; float *transient; float *steady;
     orc_splat_rec *log; uint64_t log_cap; uint64_t *log_n;
     uint8_t *rr_near;            /* polarized renders: per film pixel, 1 where a roulette draw lay within 1e-5 of rr_prob */
+    uint8_t *ang_near;           /* angulararea: per film pixel, 1 where a falloff sat at a threshold (ang_is_near) */
 } film_t;
 
 int orc_bin_index(float distance, float start_opl, float bin_width_opl, uint32_t T)
@@ -1559,6 +1560,54 @@ static float mis_weight(float a, float b)
 }
 
 /* ------------------------------------------------------------------ */
+/* angulararea  (mitransient/emitters/angulararea.py:55-144)           */
+/* ------------------------------------------------------------------ */
+/* _fallof_curve (:74-82) of cos_theta = normalize(local direction).z: the selects compare the f32 cosine with the stored f32
+ * cos_beam / cos_cutoff; the transition (cutoff - acos(cos_theta)) * inv_transition is taken in f64 with libm acos */
+static double ang_falloff_d(const mtr_emitter *E, float cos_theta)
+{
+    if (!(cos_theta > E->cos_cutoff)) return 0.0;                        /* select(cos_theta > cos_cutoff, beam_res, 0) */
+    if (cos_theta >= E->cos_beam) return 1.0;                           /* select(cos_theta >= cos_beam, 1, ...) */
+    return ((double)E->cutoff - acos((double)cos_theta)) * (double)E->inv_transition;
+}
+void orc_angular_falloff(const mtr_emitter *E, uint32_t n, const float *cos_theta, double *out)
+{
+    for (uint32_t i = 0; i < n; ++i) out[i] = ang_falloff_d(E, cos_theta[i]);
+}
+/* distance in f32 steps between two finite floats */
+static int64_t f32_ulps_apart(float a, float b)
+{
+    int32_t ia = (int32_t)orc_fbits(a), ib = (int32_t)orc_fbits(b);
+    const int64_t oa = ia < 0 ? -(int64_t)(ia & 0x7fffffff) : ia, ob = ib < 0 ? -(int64_t)(ib & 0x7fffffff) : ib;
+    return oa > ob ? oa - ob : ob - oa;
+}
+/* an f32 restatement may decide `falloff > 0` the other way here: the cosine within 4 ulps of cos_cutoff or cos_beam, or the f64
+ * cutoff - acos(cos_theta) within 4 f32 ulps (of cutoff, where the f32 difference is taken) of 0 */
+static int ang_is_near(const mtr_emitter *E, float cos_theta)
+{
+    if (f32_ulps_apart(cos_theta, E->cos_cutoff) <= 4 || f32_ulps_apart(cos_theta, E->cos_beam) <= 4) return 1;
+    const double gap = (double)E->cutoff - acos((double)cos_theta);
+    return fabs(gap) <= 4.0 * ((double)nextafterf(E->cutoff, INFINITY) - (double)E->cutoff);
+}
+/* the f64 falloff rounded to f32 once, where it meets the f32 path; a near evaluation is reported for the film pixel (x, y) */
+static float ang_falloff(film_t *F, const mtr_emitter *E, float cos_theta, uint32_t x, uint32_t y, lane_counters *C)
+{
+    if (ang_is_near(E, cos_theta)) {
+        C->ang_near += 1;
+        if (F->ang_near && x < F->f->width && y < F->f->height) F->ang_near[(size_t)y * F->f->width + x] = 1;
+    }
+    return (float)ang_falloff_d(E, cos_theta);
+}
+/* normalize(Frame3f(n).to_local(v)).z  [mitsuba3: coordinate_system(n), Frame3f::to_local; dr.normalize] */
+static float ang_local_cos(v3 n, v3 v)
+{
+    const float sign = copysignf(1.0f, n.z), a = -(1.0f / (sign + n.z)), b = (n.x * n.y) * a;
+    const v3 s = V(mulsign((n.x * n.x) * a, n.z) + 1.0f, mulsign(b, n.z), mulsign(-n.x, n.z));
+    const v3 t = V(b, fmaf(n.y, n.y * a, sign), -n.y);
+    return vnormalize(V(vdot(v, s), vdot(v, t), vdot(v, n))).z;
+}
+
+/* ------------------------------------------------------------------ */
 /* One lane of TransientPath.sample (transientpath.py:88-326)          */
 /* ------------------------------------------------------------------ */
 
@@ -1615,15 +1664,26 @@ static void trace_lane(const orc_scene *sc, const mtr_render_params *P, film_t *
             v3 dd = vdivs(rel, dist);
             /* pdf_emitter_direction(prev_si, ds, ~prev_bsdf_delta) [AreaLight::pdf_direction, Shape::pdf_direction] */
             float em_pdf = 0.0f;
+            const mtr_emitter *EH = &d->emitters[em];
+            const uint32_t fx = px - f->crop_offset_x, fy = py - f->crop_offset_y;
             if (!prev_delta) {
                 float dp = vdot(dd, si.n);          /* DirectionSample3f(scene, si, ref): ds.n = si.sh_frame.n [PositionSample(si)] */
-                if (dp < 0.0f) {
+                /* angulararea pdf_direction (:130-144): zero where the falloff of Frame3f(ds.n).to_local(-ds.d) is */
+                if (dp < 0.0f && (!EH->angular || ang_falloff(F, EH, ang_local_cos(si.n, vneg(dd)), fx, fy, C) > 0.0f)) {
                     float adp = fabsf(dp);
                     em_pdf = sc->em_inv_area[em] * (adp != 0.0f ? (dist * dist) / adp : 0.0f);
                     if (d->n_emitters > 1) em_pdf *= 1.0f / (float)d->n_emitters;
                 }
             }
             float mis = mis_weight(prev_pdf, em_pdf);
+            if (EH->angular) {
+                /* AngularAreaLight.eval (:94-102): radiance * falloff(si.wi), active &= falloff > 0 && cos_theta(si.wi) > 0 */
+                if (si.wi.z > 0.0f) {
+                    const float fall = ang_falloff(F, EH, vnormalize(si.wi).z, fx, fy, C);
+                    if (fall > 0.0f)
+                        for (int k = 0; k < 3; ++k) Le[k] = (beta[k] * mis) * (EH->radiance[k] * fall);
+                }
+            } else
             /* emitter.eval(si): radiance where cos_theta(si.wi) > 0 [AreaLight::eval] */
             if (si.wi.z > 0.0f)
                 for (int k = 0; k < 3; ++k) Le[k] = (beta[k] * mis) * d->emitters[em].radiance[k];
@@ -1683,6 +1743,16 @@ static void trace_lane(const orc_scene *sc, const mtr_render_params *P, film_t *
             /* [AreaLight::sample_direction] active &= dot(d,n) < 0 && pdf != 0; spec = radiance / pdf */
             int ok = (dp < 0.0f) && (pdf_dir != 0.0f);
             float emw[3] = { 0, 0, 0 };
+            if (E->angular) {
+                /* [AngularAreaLight::sample_direction] (:107-128): active &= falloff(Frame3f(ds.n).to_local(-ds.d)) > 0;
+                 * spec = (radiance * (falloff * sqr(rcp(ds.dist)))) / ds.pdf — the extra 1 / dist^2 on a solid-angle pdf */
+                if (ok) {
+                    const float fall = ang_falloff(F, E, ang_local_cos(en, vneg(dd)), px - f->crop_offset_x, py - f->crop_offset_y, C);
+                    ok = fall > 0.0f;
+                    const float inv_dist = 1.0f / dist;
+                    if (ok) for (int k = 0; k < 3; ++k) emw[k] = (E->radiance[k] * (fall * (inv_dist * inv_dist))) / pdf_dir;
+                }
+            } else
             if (ok) { float ip = 1.0f / pdf_dir; for (int k = 0; k < 3; ++k) emw[k] = E->radiance[k] * ip; }
             float pdf = pdf_dir;
             if (d->n_emitters > 1) {                                    /* ds.pdf *= pmf; spec *= 1/pmf */
@@ -2199,10 +2269,13 @@ static void trace_lane_nlos(const orc_scene *sc, const nlos_scene *N, const mtr_
 static int g_default_threads = 0;
 static int render_impl(const mtr_scene_desc *d, const mtr_render_params *P, float *transient_hwt4, float *steady_hw4,
                        mtr_counters *out, int n_threads, int use_bvh,
-                       orc_splat_rec *log, uint64_t log_cap, uint64_t *log_n, uint8_t *rr_near)
+                       orc_splat_rec *log, uint64_t log_cap, uint64_t *log_n, uint8_t *rr_near,
+                       uint8_t *ang_near, uint64_t *ang_near_total)
 {
     if (!d || !P || !transient_hwt4) return -1;
     if ((P->flags & MTR_FLAG_POLARIZED) && (d->nlos || d->film.n_frequencies || d->film.laser_scan_width)) return -1;
+    for (uint32_t i = 0; i < d->n_emitters; ++i)        /* angulararea is restated for the transient path loop only */
+        if (d->emitters[i].angular && (d->nlos || (P->flags & MTR_FLAG_POLARIZED))) return -1;
     if (P->spp_total == 0 || P->spp_end > P->spp_total || P->spp_begin > P->spp_end) return -1;
     if ((uint64_t)d->film.crop_width * d->film.crop_height * P->spp_total > (1ull << 32)) return -2;   /* common.py:51 */
     if (P->pixel_end > d->film.crop_width * d->film.crop_height || P->pixel_begin > P->pixel_end) return -1;
@@ -2212,11 +2285,11 @@ static int render_impl(const mtr_scene_desc *d, const mtr_render_params *P, floa
     film_t F; memset(&F, 0, sizeof F);
     F.f = &d->film; F.transient = transient_hwt4; F.steady = steady_hw4;
     uint64_t zero = 0; F.log = log; F.log_cap = log_cap; F.log_n = log_n ? log_n : &zero;
-    F.rr_near = rr_near;
+    F.rr_near = rr_near; F.ang_near = ang_near;
     if (log_n) *log_n = 0;
     nlos_scene NS; memset(&NS, 0, sizeof NS);
     if (d->nlos) nlos_build(&NS, &sc, use_bvh);
-    uint64_t closest = 0, shadow = 0, bounces = 0, paths = 0, splats = 0;
+    uint64_t closest = 0, shadow = 0, bounces = 0, paths = 0, splats = 0, near = 0;
     const int64_t n_pix = (int64_t)P->pixel_end - (int64_t)P->pixel_begin;
     const uint32_t s0 = P->spp_begin, s1 = P->spp_end;
 #ifdef _OPENMP
@@ -2227,15 +2300,15 @@ static int render_impl(const mtr_scene_desc *d, const mtr_render_params *P, floa
 #else
     (void)n_threads;
 #endif
-#pragma omp parallel for schedule(dynamic, 16) reduction(+ : closest, shadow, bounces, paths, splats)
+#pragma omp parallel for schedule(dynamic, 16) reduction(+ : closest, shadow, bounces, paths, splats, near)
     for (int64_t ip = 0; ip < n_pix; ++ip) {
         uint32_t pix = P->pixel_begin + (uint32_t)ip;
         for (uint32_t s = s0; s < s1; ++s) {
             uint32_t lane = pix * P->spp_total + s;      /* lane identity == RNG identity */
-            lane_counters C = { 0, 0, 0, 0 };
+            lane_counters C = { 0, 0, 0, 0, 0 };
             if (d->nlos) trace_lane_nlos(&sc, &NS, P, &F, lane, use_bvh, &C);
             else trace_lane(&sc, P, &F, lane, use_bvh, &C);
-            closest += C.closest; shadow += C.shadow; bounces += C.bounces; splats += C.splats; paths += 1;
+            closest += C.closest; shadow += C.shadow; bounces += C.bounces; splats += C.splats; near += C.ang_near; paths += 1;
         }
     }
     if (out) {
@@ -2243,6 +2316,7 @@ static int render_impl(const mtr_scene_desc *d, const mtr_render_params *P, floa
         out->paths = paths; out->rays_closest = closest; out->rays_shadow = shadow;
         out->bounces = bounces; out->splats_issued = splats;
     }
+    if (ang_near_total) *ang_near_total = near;
     if (d->nlos) nlos_free(&NS);
     free_scene(&sc);
     return 0;
@@ -2251,7 +2325,16 @@ int orc_render(const mtr_scene_desc *d, const mtr_render_params *P, float *trans
                mtr_counters *out, int n_threads, int use_bvh,
                orc_splat_rec *log, uint64_t log_cap, uint64_t *log_n)
 {
-    return render_impl(d, P, transient_hwt4, steady_hw4, out, n_threads, use_bvh, log, log_cap, log_n, NULL);
+    return render_impl(d, P, transient_hwt4, steady_hw4, out, n_threads, use_bvh, log, log_cap, log_n, NULL, NULL, NULL);
+}
+/* orc_render, and the angulararea near-threshold report: ang_near (H, W) bytes, set for a pixel where a falloff evaluation sat at a
+ * threshold (ang_is_near), and the number of such evaluations */
+int orc_render_ex(const mtr_scene_desc *d, const mtr_render_params *P, float *transient_hwt4, float *steady_hw4,
+                  mtr_counters *out, int n_threads, int use_bvh, orc_splat_rec *log, uint64_t log_cap, uint64_t *log_n,
+                  uint8_t *ang_near_hw, uint64_t *ang_near_total)
+{
+    return render_impl(d, P, transient_hwt4, steady_hw4, out, n_threads, use_bvh, log, log_cap, log_n, NULL, ang_near_hw,
+                       ang_near_total);
 }
 /* the polarized render (MTR_FLAG_POLARIZED whatever P->flags says): transient (H, W, T, 4) = S0..S3, steady (H, W, 4) =
  * (S0, S1, S2, weight), and rr_near (H, W) bytes, set where a roulette draw lay within 1e-5 (relative) of rr_prob */
@@ -2261,7 +2344,7 @@ int orc_render_polarized(const mtr_scene_desc *d, const mtr_render_params *P, fl
     if (!P) return -1;
     mtr_render_params Q = *P;
     Q.flags |= MTR_FLAG_POLARIZED;
-    return render_impl(d, &Q, transient_hwt4, steady_hw4, out, n_threads, use_bvh, NULL, 0, NULL, rr_near);
+    return render_impl(d, &Q, transient_hwt4, steady_hw4, out, n_threads, use_bvh, NULL, 0, NULL, rr_near, NULL, NULL);
 }
 
 /* develop (transient_hdr_film.py:220-248; steady hdrfilm: sum / weight) */

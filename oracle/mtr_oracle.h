@@ -18,6 +18,10 @@ typedef struct orc_splat_rec {
 int  orc_render(const mtr_scene_desc *d, const mtr_render_params *P, float *transient_hwt4, float *steady_hw4,
                 mtr_counters *out, int n_threads, int use_bvh,
                 orc_splat_rec *log, uint64_t log_cap, uint64_t *log_n);
+/* orc_render with the angulararea near-threshold report (per-pixel bytes and the number of near falloff evaluations) */
+int  orc_render_ex(const mtr_scene_desc *d, const mtr_render_params *P, float *transient_hwt4, float *steady_hw4,
+                   mtr_counters *out, int n_threads, int use_bvh, orc_splat_rec *log, uint64_t log_cap, uint64_t *log_n,
+                   uint8_t *ang_near_hw, uint64_t *ang_near_total);
 int  orc_render_polarized(const mtr_scene_desc *d, const mtr_render_params *P, float *transient_hwt4, float *steady_hw4,
                           mtr_counters *out, int n_threads, int use_bvh, uint8_t *rr_near_hw);
 /* f64 polarization building blocks (row-major 4x4) */
@@ -26,6 +30,8 @@ void orc_polar_transmission(double cos_i, double eta, double *out16);
 void orc_polar_rotate_basis(const double *fwd3, const double *cur3, const double *tgt3, double *out16);
 void orc_polar_stokes_basis(const double *w3, double *out3);
 void orc_polar_to_world_mueller(const double *M16, const double *stn9, const double *wi3, const double *wo3, double *out16);
+/* angulararea.py:74-82 _fallof_curve of n cosines, the transition in f64 */
+void orc_angular_falloff(const mtr_emitter *E, uint32_t n, const float *cos_theta, double *out);
 void orc_develop(const mtr_film_desc *f, const float *transient_hwt4, float *transient_hwt3,
                  const float *steady_hw4, float *steady_hw3);
 void orc_phasor_term(float freq, float opl, float *c, float *s);

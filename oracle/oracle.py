@@ -40,6 +40,10 @@ def lib():
                                  C.POINTER(_cabi.mtr_counters), C.c_int, C.c_int,
                                  C.POINTER(orc_splat_rec), C.c_uint64, C.POINTER(C.c_uint64)]
         L.orc_render.restype = C.c_int
+        L.orc_render_ex.argtypes = L.orc_render.argtypes + [C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
+        L.orc_render_ex.restype = C.c_int
+        L.orc_angular_falloff.argtypes = [C.POINTER(_cabi.mtr_emitter), C.c_uint32, fp, C.POINTER(C.c_double)]
+        L.orc_angular_falloff.restype = None
         L.orc_render_polarized.argtypes = [C.POINTER(_cabi.mtr_scene_desc), C.POINTER(_cabi.mtr_render_params), fp, fp,
                                            C.POINTER(_cabi.mtr_counters), C.c_int, C.c_int, C.POINTER(C.c_uint8)]
         L.orc_render_polarized.restype = C.c_int
@@ -102,9 +106,11 @@ def alloc_film(film_desc, prefault=False):
     return t4, s4
 
 
-def render(scene_data, params: _cabi.mtr_render_params, n_threads=0, use_bvh=False, log_capacity=0, out=None):
-    """Returns (transient (H,W,T,4) f32, steady (H,W,4) f32, counters dict[, log ndarray]).
-    ``out=(t4, s4)`` accumulates into existing buffers."""
+def render(scene_data, params: _cabi.mtr_render_params, n_threads=0, use_bvh=False, log_capacity=0, out=None, near=False):
+    """Returns (transient (H,W,T,4) f32, steady (H,W,4) f32, counters dict[, log ndarray][, near]).
+    ``out=(t4, s4)`` accumulates into existing buffers.  ``near=True`` appends the angulararea near-threshold report
+    ``(map (H,W) bool, total)``: the pixels, and the number of falloff evaluations, where the cosine sat within 4 ulps of
+    cos_cutoff / cos_beam or cutoff - acos(cos) within 4 ulps of 0 — an f32 falloff may take the other side of `> 0` there."""
     f = scene_data.film
     t4, s4 = out if out is not None else alloc_film(f)
     cnt = _cabi.mtr_counters()
@@ -113,16 +119,25 @@ def render(scene_data, params: _cabi.mtr_render_params, n_threads=0, use_bvh=Fal
     n_log = C.c_uint64(0)
     if log_capacity:
         log = (orc_splat_rec * log_capacity)()
-    rc = lib().orc_render(C.byref(d), C.byref(params), _fp(t4), _fp(s4), C.byref(cnt), n_threads, int(use_bvh),
-                          log, log_capacity, C.byref(n_log))
+    args = (C.byref(d), C.byref(params), _fp(t4), _fp(s4), C.byref(cnt), n_threads, int(use_bvh), log, log_capacity,
+            C.byref(n_log))
+    if near:
+        near_map = np.zeros((f.height, f.width), np.uint8)
+        near_total = C.c_uint64(0)
+        rc = lib().orc_render_ex(*args, near_map.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(near_total))
+    else:
+        rc = lib().orc_render(*args)
     if rc != 0:
         raise RuntimeError(f"orc_render failed ({rc})")
+    res = (t4, s4, cnt.as_dict())
     if log_capacity:
         n = min(int(n_log.value), log_capacity)
         arr = np.frombuffer(log, dtype=np.dtype([("lane", "u4"), ("depth_kind", "u4"), ("pixel", "u4"), ("bin", "u4"),
                                                   ("r", "f4"), ("g", "f4"), ("b", "f4"), ("opl", "f4")]))[:n].copy()
-        return t4, s4, cnt.as_dict(), arr
-    return t4, s4, cnt.as_dict()
+        res += (arr,)
+    if near:
+        res += ((near_map.astype(bool), int(near_total.value)),)
+    return res
 
 
 def render_polarized(scene_data, params: _cabi.mtr_render_params, n_threads=0, use_bvh=False, out=None):
@@ -184,6 +199,15 @@ def polar_to_world_mueller(M, frame_stn, wi, wo):
     o, op = _out(16)
     lib().orc_polar_to_world_mueller(mp, fp_, ap, bp, op)
     return o.reshape(4, 4)
+
+
+def angular_falloff(emitter, cos_theta):
+    """angulararea.py:74-82 _fallof_curve in f64 for an `mtr_emitter`: the selects on the f32 cosines, the transition
+    (cutoff - acos(c)) * inv_transition with f64 acos"""
+    c = np.ascontiguousarray(cos_theta, np.float32).ravel()
+    o = np.zeros(c.size, np.float64)
+    lib().orc_angular_falloff(C.byref(emitter), c.size, _fp(c), o.ctypes.data_as(C.POINTER(C.c_double)))
+    return o
 
 
 def develop(film_desc, t4=None, s4=None):

@@ -240,6 +240,15 @@ extern "C" void hh_special(int which, uint64_t n, const float *x, float *y)
         y[i] = which == 0 ? mtr_expf(x[i]) : which == 1 ? mtr_logf(x[i]) : which == 2 ? mtr_erff(x[i]) : mtr_erfinvf(x[i]);
 }
 
+// the product's angulararea falloff (mtr_core.h angular_falloff, f32) of n cosines, for the emitter's stored constants
+extern "C" void hh_angular_falloff(const mtr_emitter *e, uint64_t n, const float *cos_theta, float *y)
+{
+    Emitter E{};
+    E.angular = e->angular; E.cutoff = e->cutoff; E.cos_cutoff = e->cos_cutoff; E.cos_beam = e->cos_beam;
+    E.inv_transition = e->inv_transition;
+    for (uint64_t i = 0; i < n; ++i) y[i] = angular_falloff(E, cos_theta[i]);
+}
+
 // the product's BSDF arithmetic on arrays of local directions (tests/test_rough_bsdf.py)
 extern "C" void hh_bsdf_eval_pdf(const mtr_material *m, uint32_t n, const float *wi3, const float *wo3, float *val3, float *pdf)
 {

@@ -166,3 +166,93 @@ def test_notebook_cells_run_as_written():
     data_steady, data_transient = mi.render(scene, spp=16)
     second = np.array(data_steady)
     assert second.shape == (32, 32, 3) and second.max() > 0 and not np.allclose(first, second)
+
+
+# ---------------------------------------------------------------- against the oracle's restatement of angulararea.py (f64 falloff)
+import angular_cases as AC          # noqa: E402
+
+
+def _vs_oracle(scene, spp, seed, what="", **p):
+    s, t, c = _gpu(scene, spp, seed)
+    return AC.assert_matches_oracle(s, t, c, AC.oracle_render(scene, seed, spp, **p), what)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("case", list(AC.SCENE_CASES))
+def test_gpu_matches_oracle(tmp_path, mode, case):
+    """every scene of tests/angular_cases.py in both organisations against the oracle: rel-L2 <= 1e-5 outside the near pixels,
+    counters equal up to the near total"""
+    build, seed, spp, _ = AC.SCENE_CASES[case]
+    scene = build(str(tmp_path))
+    scene.integrator().amd_mode = mode
+    _vs_oracle(scene, spp, seed, case)
+
+
+@pytest.mark.parametrize("case", ["notebook_view1", "cornell_60_30", "area_and_angular"])
+def test_gpu_deterministic_rows_match_oracle(tmp_path, case):
+    """amd_deterministic (64-bit fixed-point rows): two renders bit for bit equal, and the oracle's film within the bar"""
+    build, seed, spp, _ = AC.SCENE_CASES[case]
+    scene = build(str(tmp_path))
+    integ = scene.integrator()
+    integ.amd_mode = "auto"
+    integ.deterministic = True
+    a, b = _gpu(scene, spp, seed), _gpu(scene, spp, seed)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    AC.assert_matches_oracle(*a, AC.oracle_render(scene, seed, spp), case)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_gpu_crop_window_one_spp_and_shards(mode):
+    """a 13 x 9 film with a 9 x 6 crop window at offset (3, 2), 1 spp; then sample shards of 5 spp that sum to the whole"""
+    import torch
+    crop = {"width": 13, "height": 9, "crop_width": 9, "crop_height": 6, "crop_offset_x": 3, "crop_offset_y": 2}
+    scene = AC.cornell(45, 25, film=crop)
+    scene.integrator().amd_mode = mode
+    s, t, c = _gpu(scene, 1, 14)
+    AC.assert_matches_oracle(s, t, c, AC.oracle_render(scene, 14, 1), "crop 1 spp")
+    assert s.shape[:2] == (6, 9) and np.all(t[6:] == 0) and np.all(t[:, 9:] == 0)
+    spp = 5
+    s_full, t_full, _ = _gpu(scene, spp, 15)
+    integ, sens = scene.integrator(), scene.sensors()[0]
+    passes = integ.prepare(scene, sens, 15, spp, [])
+    for rng in ((0, 2), (2, 5)):
+        integ.accumulate(scene, sens, passes, spp, spp_range=rng)
+    torch.cuda.synchronize()
+    s_a, t_a = (np.array(x) for x in sens.film().develop())
+    assert rel_l2(t_a, t_full) <= 1e-6 and rel_l2(s_a, s_full) <= 1e-6
+    ref = AC.oracle_render(scene, 15, spp)
+    assert rel_l2(t_a, ref[1]) <= TOL and rel_l2(s_a, ref[0]) <= TOL
+
+
+def test_gpu_staircase_auto_is_wavefront_in_hbm():
+    """an angular cube emitter in staircase_like(tiles=6): AUTO resolves to the wavefront organisation (the scene walked in HBM)"""
+    scene = AC.staircase()
+    integ = scene.integrator()
+    integ.amd_mode = "auto"
+    _vs_oracle(scene, 8, 16, "staircase")
+    assert integ.resolved_mode(scene, scene.sensors()[0], 8) == "wavefront"        # (mtr_render_plan, the film prepared)
+
+
+def test_gpu_phasor_film_matches_oracle():
+    """phasor_hdr_film with an angulararea luminaire against the oracle's phasor render"""
+    import torch
+    import mitransient_amd.mi as mi
+    try:
+        scene = AC.phasor(res=12)
+        integ = scene.integrator()
+        integ.collect_stats = True
+        steady, ph = integ.render(scene, seed=17, spp=32)
+        torch.cuda.synchronize()
+        got = dict(integ.last_counters)
+        sd = scene.data()
+        assert sd.emitters[0].angular == 1
+        from oracle import oracle as _o
+        p = integ.render_params(scene.sensors()[0].film(), 17, 32)
+        t, s4, cnt, (near, n_near) = _o.render(sd, p, use_bvh=True, near=True)
+        ph_ref, s_ref = _o.develop(sd.film, t, s4)
+        assert np.abs(np.array(ph_ref)).max() > 0
+        assert rel_l2(np.array(ph), ph_ref) <= TOL and rel_l2(np.array(steady)[..., 0], s_ref[..., 0]) <= TOL
+        for k in COUNTERS:
+            assert abs(got[k] - cnt[k]) <= n_near, k
+    finally:
+        mi.set_variant("llvm_ad_rgb")
