@@ -3,13 +3,19 @@
 (BASELINE.json configs[1]; with N GPUs: N*1024 spp sharded by samples + one RCCL film reduction,
 configs[2] at N=8).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one complete transient render on every rank: film clear, the path kernel(s) over
 rank's sample slice of all 512^2 pixels, (N>1) reduce-scatter of the raw (H,W,T,4) film over
 RCCL + all-gather of the developed tensor, develop.  Scene, BVH and film live in HBM before the
 timed region starts.  Rank 0 prints ONE JSON line.  --dump-outputs DIR: rank 0 also writes the (steady, transient) tensors the
 last timed step returned to DIR (see dump_outputs); the inputs are seeded, identical from run to run.
+
+A plain run does only what the headline needs: set-up, W warm-up and K timed steps, the dump, the line (its roofline blocks
+come from the timed steps' own HIP-event times and the committed profiles).  --full adds the legs that take runs of their
+own: the CPU oracle baseline, the wavefront scatter-add leg, the config-4 / config-5 side legs and the scatter-add
+micro-benchmark (rank 0, N = 1), and with N > 1 the reduce-scatter-only, row-sharded and communication-only legs.
+The --no-* options leave single legs out of a --full run.
 """
 from __future__ import annotations
 
@@ -463,10 +469,14 @@ def main():
     ap.add_argument("--bins", type=int, default=None)
     ap.add_argument("--spp", type=int, default=None, help="samples per pixel PER GPU (weak scaling)")
     ap.add_argument("--mode", default=None, choices=[None, "auto", "fused", "wavefront"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-scatter-leg", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip the config-4 / config-5 side legs")
-    ap.add_argument("--no-splat-microbench", action="store_true", help="skip SURVEY 8d's stand-alone scatter-add micro-benchmark (2^30 contributions)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also run the legs that take runs of their own: CPU baseline, scatter-add leg, config-4 / "
+                         "config-5 side legs, scatter-add micro-benchmark (N = 1); reduce-scatter-only, row-sharded, communication-only "
+                         "legs (N > 1).  Off by default: a plain run times the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
+    ap.add_argument("--no-scatter-leg", action="store_true", help="--full: skip the wavefront scatter-add leg")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full: skip the config-4 / config-5 side legs")
+    ap.add_argument("--no-splat-microbench", action="store_true", help="--full: skip SURVEY 8d's stand-alone scatter-add micro-benchmark (2^30 contributions)")
     ap.add_argument("--splat-log2", type=int, default=30, help="log2 of the micro-benchmark's contribution count")
     ap.add_argument("--reduced-config5", action="store_true", help="config-5 side leg at 128 of its 2048 spp (quick runs)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
@@ -527,10 +537,10 @@ def main():
         if dist.get_world_size() != args.gpus:
             raise SystemExit(f"--gpus {args.gpus} but the process group has {dist.get_world_size()} ranks")
 
-    # the CPU baseline runs FIRST (rank 0, N = 1): the GPU legs then sit at the end of the command, where a coarse
+    # --full: the CPU baseline runs FIRST (rank 0, N = 1): the GPU legs then sit at the end of the command, where a coarse
     # utilisation sampler cannot miss them behind ~20 s of host work
     cpu_res = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_res = cpu_baseline(args.width, args.height, args.bins, args.spp, args.cpu_seconds)
 
     scene = build_scene(args.width, args.height, args.bins, mode=args.mode)
@@ -647,10 +657,10 @@ def main():
     totals_rank0 = wf_t["rank_totals"]
     path_taken = renderer.last_path
     renderer_collectives = renderer.last_collectives
-    # N > 1: the same steps with the film reduction ALONE (reduce-scatter, every rank keeps the developed rows it owns —
+    # --full, N > 1: the same steps with the film reduction ALONE (reduce-scatter, every rank keeps the developed rows it owns —
     # north_star's "single RCCL reduce"); the headline keeps the all-gather that hands every rank the whole tensor
-    rs_only = rows_leg = single_leg = None
-    if world > 1:
+    rs_only = rows_leg = single_leg = comm_full = comm_rs = None
+    if args.full and world > 1:
         r2 = mdist.DistributedRenderer(scene, partition="spp", gather=False)
         e2, t2, *_ = timed_run(r2)
         rs_only = {"ms_per_step": e2 / args.steps * 1e3, "value": (t2["rays_closest"] + t2["rays_shadow"]) / e2 / 1e6,
@@ -678,10 +688,10 @@ def main():
                           "what": "the headline's reduce_scatter + all_gather pipeline behind ONE launch with band completion words"}
             del r4
 
-    # ---- untimed extra leg (rank 0, N=1): the same render in wavefront mode, to time the stand-alone
+    # ---- untimed extra leg (--full, rank 0, N=1): the same render in wavefront mode, to time the stand-alone
     # time-bin scatter-add kernel (k_wf_scatter) with HIP events on its stream
     scatter = None
-    if rank == 0 and world == 1 and not args.no_scatter_leg:
+    if args.full and rank == 0 and world == 1 and not args.no_scatter_leg:
         sc2 = build_scene(args.width, args.height, args.bins, mode="wavefront")
         i2 = sc2.integrator()
         i2.collect_stats = True
@@ -701,13 +711,13 @@ def main():
         del sc2, i2
 
     extra = None
-    if rank == 0 and world == 1 and SCENE == "cornell" and not args.no_extra_configs:
+    if args.full and rank == 0 and world == 1 and SCENE == "cornell" and not args.no_extra_configs:
         del renderer, scene
         torch.cuda.empty_cache()
         extra = extra_config_legs(512, 2048 if not args.reduced_config5 else 128)
 
     splat_mb = None
-    if rank == 0 and world == 1 and SCENE == "cornell" and not args.no_splat_microbench and not args.no_extra_configs:
+    if args.full and rank == 0 and world == 1 and SCENE == "cornell" and not args.no_splat_microbench and not args.no_extra_configs:
         try:
             del renderer, scene
         except NameError:
@@ -809,12 +819,13 @@ def main():
             res["comm_backend"] = backend
         if world > 1:
             res["render_path"] = path_taken
-            res["reduce_scatter_only"] = rs_only
-            res["row_sharded"] = rows_leg
-            if single_leg:
-                res["single_launch_bands"] = single_leg
-            res["comm_only"] = comm_full
-            res["comm_only_reduce_scatter"] = comm_rs
+            if args.full:
+                res["reduce_scatter_only"] = rs_only
+                res["row_sharded"] = rows_leg
+                if single_leg:
+                    res["single_launch_bands"] = single_leg
+                res["comm_only"] = comm_full
+                res["comm_only_reduce_scatter"] = comm_rs
             res["reserve_cus"] = reserve
             res["collectives_per_step"] = renderer_collectives
         if scatter:

@@ -307,10 +307,10 @@ def test_four_ranks_on_one_gpu(tmp_path, partition, gather, single):
 
 
 def test_bench_with_four_ranks_dry_run():
-    """`python bench.py --gpus 4` in the dry-run form (every rank on this GPU, gloo): one JSON line, weak scaling, 17 collectives"""
+    """`python bench.py --gpus 4 --full` in the dry-run form (every rank on this GPU, gloo): one JSON line, weak scaling, 17 collectives"""
     res = _bench_line({"MTR_BENCH_BACKEND": "gloo", "MTR_BENCH_DEVICE": "0", "OMP_NUM_THREADS": "1"},
                       ["--gpus", str(SHARED_RANKS), "--steps", "2", "--warmup", "1", "--spp", "8", "--width", "128", "--height", "128", "--bins", "128",
-                       "--no-cpu-baseline"], timeout=900)
+                       "--no-cpu-baseline", "--full"], timeout=900)
     assert res["n_gpus"] == SHARED_RANKS and res["comm_backend"] == "gloo" and res["scaling"] == "weak"
     assert res["counters_per_step"]["paths"] == 128 * 128 * 8 * SHARED_RANKS
     assert res["render_path"] == "pipelined" and res["collectives_per_step"] == 17
@@ -335,8 +335,9 @@ BENCH_SMALL = ["--steps", "2", "--warmup", "1", "--spp", "8", "--width", "128", 
 
 def test_bench_self_launches_its_ranks():
     """the driver's command form for N > 1 WITHOUT a launcher — `python bench.py --gpus 2 ...` — starts its two ranks
-    itself and prints one JSON line (both ranks on this box's GPU, gloo instead of RCCL: MTR_BENCH_* dry-run hooks)"""
-    res = _bench_line({"MTR_BENCH_BACKEND": "gloo", "MTR_BENCH_DEVICE": "0", "MTR_BENCH_SINGLE_LAUNCH": "1"}, ["--gpus", "2"] + BENCH_SMALL)
+    itself and prints one JSON line (both ranks on this box's GPU, gloo instead of RCCL: MTR_BENCH_* dry-run hooks); with
+    --full the line carries the side legs of N > 1"""
+    res = _bench_line({"MTR_BENCH_BACKEND": "gloo", "MTR_BENCH_DEVICE": "0", "MTR_BENCH_SINGLE_LAUNCH": "1"}, ["--gpus", "2", "--full"] + BENCH_SMALL)
     assert res["n_gpus"] == 2 and res["steps"] == 2 and res["comm_backend"] == "gloo" and res["rccl_ranks"] == 0
     assert res["single_launch_bands"]["band_launches_per_step"] == 1 and res["single_launch_bands"]["value"] > 0      # the opt-in leg
     assert res["render_path"] == "pipelined" and res["scaling"] == "weak"
@@ -374,6 +375,21 @@ def test_bench_dump_outputs_are_the_last_steps_result(tmp_path):
     s_ref, t_ref = np.array(s_ref), np.array(t_ref)
     px = np.sort(np.random.default_rng(0).choice(128 * 128, size=transient.shape[0], replace=False))
     assert rel_l2(steady, s_ref) <= 1e-6 and rel_l2(transient, t_ref[px // 128, px % 128]) <= 1e-6
+
+
+def test_bench_plain_line_is_the_headline_and_full_adds_the_legs():
+    """a plain `bench.py --gpus 1` runs no leg of its own beside the timed steps; `--full` adds them (here the CPU baseline
+    and the scatter-add leg — the full-size side configurations are left out with --no-extra-configs)"""
+    small = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "8", "--width", "128", "--height", "128", "--bins", "256"]
+    plain = _bench_line({}, small)
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["ms_per_step"] > 0 and plain["value"] > 0
+    assert plain["roofline"]["bound"] == "hbm"
+    for k in ("cpu_baseline", "gpu_over_cpu", "scatter_add", "extra_configs", "splat_microbench"):
+        assert k not in plain, k
+    full = _bench_line({}, small + ["--full", "--no-extra-configs", "--cpu-seconds", "1"])
+    assert full["counters_per_step"] == plain["counters_per_step"]
+    assert full["cpu_baseline"]["value"] > 0 and full["gpu_over_cpu"] > 0
+    assert full["scatter_add"]["launches_per_render"] >= 1 and "extra_configs" not in full and "splat_microbench" not in full
 
 
 def test_reserved_compute_units_change_nothing_but_the_grid():

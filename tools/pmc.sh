@@ -2,7 +2,7 @@
 # tools/pmc.sh <lib.so> <tag>: quick SQ counter pass for the path kernel
 LIB=$(pwd)/$1; TAG=$2; shift; shift; EXTRA="$@"; REPO=$(pwd); OUT=$REPO/gpurun_out/pmc_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline $EXTRA"
+CMD="python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline $EXTRA"
 for grp in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU" \
            "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA"; do
   name=$(echo $grp | tr ' ' '_' | cut -c1-30)
