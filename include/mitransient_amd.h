@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 14
+#define MTR_ABI_VERSION 15
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -384,6 +384,11 @@ int  mtr_scene_bvh_info(const mtr_scene *, uint32_t *n_nodes, uint32_t *max_dept
 #define MTR_TRAIT_NO_LOBES        32u   /* extended shading (interpolated normals, bitmaps) without any microfacet lobe / plastic / thin dielectric */
 #define MTR_TRAIT_GREY            64u   /* every colour (materials, emitters, the NLOS laser) has three equal channels, no bitmaps: r == g == b in every contribution */
 int  mtr_scene_traits(const mtr_scene *, uint32_t *traits);
+/* (ABI 15) mi.traverse(scene) parameters changed (params.update()): new constant colours for the scene's tables, without
+ * rebuilding anything else — material_a (host, n_materials x 3) replaces every mtr_material.a, emitter_radiance (host,
+ * n_emitters x 3) every mtr_emitter.radiance; the traits that depend on colours are decided again.  Synchronises the context's
+ * stream.  MTR_ERR_UNSUPPORTED for a scene with the NLOS tier (recreate it). */
+int  mtr_scene_set_colors(mtr_scene *, const float *material_a, const float *emitter_radiance);
 
 /* TransientImageBlock.clear (transient_image_block.py:56-70): zero the
  * (H,W,T,4) f32 accumulator and the (H,W,4) steady accumulator. */
@@ -408,6 +413,24 @@ int  mtr_render(mtr_scene *, const mtr_render_params *,
  * (rotating work tickets); the wavefront organisation has one workspace per scene and must stay on one stream. */
 int  mtr_render_plan(mtr_scene *, const mtr_render_params *, uint32_t *mode_out,
                      uint32_t *developed_rows_ok /* may be NULL: 1 when MTR_FLAG_DEVELOPED_ROWS would be honoured */);
+
+/* (ABI 15) Reverse-mode gradients of transient_path: TransientADIntegrator.render_backward (common.py:325-409) with
+ * TransientPath.sample's backward pass (transientpath.py:88-326, :284-299).  For the lanes of `params` (the same lanes, seeds
+ * and passes mtr_render would run) the gradient of  sum g_s . steady + sum g_t . transient  of the seeded estimator is STORED to
+ *   grad_materials : device f32 (n_materials, 3)  d loss / d reflectance of every plain `diffuse` material (constant `a`;
+ *                                                  other materials and bitmap-textured ones receive 0)
+ *   grad_emitters  : device f32 (n_emitters, 3)   d loss / d radiance of every `area` / `angulararea` emitter
+ * with the upstream gradients of the DEVELOPED tensors
+ *   grad_steady_hw3     : device f32 (H, W, 3)
+ *   grad_transient_hwt3 : device f32 (H, W, T, 3)
+ * Sampling is detached (Russian-roulette probabilities, BSDF and emitter sampling are constants); a contribution's transient
+ * weight is read at its own time bin (film_bin of its optical path length), which departs from the reference's single read at the
+ * vertex distance — DESIGN.md §2.  A render split into passes (pixel / sample ranges, spp_scale) has the sum of its passes'
+ * gradients.  Only transient_path with an RGB transient_hdr_film: the NLOS tier, a phasor film, an exhaustive_scan film and
+ * MTR_FLAG_POLARIZED are MTR_ERR_UNSUPPORTED.  params.mode, n_bands and the film flags are ignored.  Synchronises the stream. */
+int  mtr_render_grad(mtr_scene *, const mtr_render_params *params,
+                     const float *grad_steady_hw3, const float *grad_transient_hwt3,
+                     float *grad_materials, float *grad_emitters);
 
 /* Zero the context's device counters on the context stream (then issue every mtr_render of the render with
  * MTR_FLAG_KEEP_COUNTERS and read the sums once with mtr_counters_read). */

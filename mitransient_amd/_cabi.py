@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MITRANSIENT_AMD_LIB") or os.path.join(_HERE, "csrc", "libmitransient_amd.so")   # env override: kernel A/B experiments
 
-MTR_ABI_VERSION = 14
+MTR_ABI_VERSION = 15
 MTR_TRAIT_DIFFUSE, MTR_TRAIT_ONE_RECT_EMITTER, MTR_TRAIT_LEAF_PAIR, MTR_TRAIT_FLAT_TOP, MTR_TRAIT_FLAT_LEAVES, MTR_TRAIT_NO_LOBES, MTR_TRAIT_GREY = 1, 2, 4, 8, 16, 32, 64      # mtr_scene_traits
 MTR_SPLAT_FILM_ZERO = 0x100      # mtr_splat_add: OR into `variant` when the film is all-zero on entry
 
@@ -154,6 +154,7 @@ EXPORTS = [
     "mtr_abi_version", "mtr_ctx_create", "mtr_ctx_destroy", "mtr_ctx_set_stream", "mtr_last_error",
     "mtr_scene_create", "mtr_scene_destroy", "mtr_scene_set_film", "mtr_scene_set_nlos", "mtr_scene_bvh_info", "mtr_scene_traits",
     "mtr_ctx_trim", "mtr_film_clear", "mtr_render", "mtr_render_plan", "mtr_counters_reset", "mtr_counters_read", "mtr_film_develop", "mtr_splat_add", "mtr_debug_set_splat_log",
+    "mtr_render_grad", "mtr_scene_set_colors",
 ]
 
 _lib = None
@@ -203,6 +204,8 @@ def load_library() -> C.CDLL:
     lib.mtr_splat_add.argtypes = [vp, C.POINTER(mtr_splat_soa), C.POINTER(mtr_film_desc), C.c_int, vp,
                                   C.POINTER(C.c_float)]
     lib.mtr_debug_set_splat_log.argtypes = [vp, vp, C.c_uint64, vp]
+    lib.mtr_render_grad.argtypes = [vp, C.POINTER(mtr_render_params), vp, vp, vp, vp]      # (ABI 15)
+    lib.mtr_scene_set_colors.argtypes = [vp, vp, vp]
     if lib.mtr_abi_version() != MTR_ABI_VERSION:
         raise MitransientAMDError("libmitransient_amd.so ABI version mismatch; rebuild")
     _lib = lib

@@ -9,6 +9,7 @@
 #include "mtr_core.h"
 #include "mtr_kernels.h"
 #include "mtr_polar.h"
+#include "mtr_grad.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -409,6 +410,37 @@ int mtr_scene_bvh_info(const mtr_scene *s, uint32_t *n_nodes, uint32_t *max_dept
     if (n_nodes) *n_nodes = s->dev.n_nodes;
     if (max_depth) *max_depth = s->dev.bvh_depth;
     if (n_leaves) *n_leaves = s->n_leaves;
+    return MTR_OK;
+}
+
+int mtr_scene_set_colors(mtr_scene *s, const float *material_a, const float *emitter_radiance)
+{
+    if (!s || (s->dev.n_mats && !material_a) || (s->dev.n_ems && !emitter_radiance))
+        return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_scene_set_colors: NULL argument");
+    mtr_ctx *c = s->ctx;
+    if (s->nlos.on) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_scene_set_colors: not for the NLOS tier (its laser enters the scene's traits)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // (renders in flight read the tables)
+    std::vector<mtr_material> mats(s->dev.n_mats);
+    std::vector<Emitter> ems(s->dev.n_ems);
+    if (!mats.empty()) HIP_TRY(c, hipMemcpy(mats.data(), s->dev.mats, mats.size() * sizeof(mtr_material), hipMemcpyDeviceToHost));
+    if (!ems.empty()) HIP_TRY(c, hipMemcpy(ems.data(), s->dev.ems, ems.size() * sizeof(Emitter), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < mats.size(); ++i) for (int k = 0; k < 3; ++k) mats[i].a[k] = material_a[3 * i + k];
+    for (size_t i = 0; i < ems.size(); ++i) for (int k = 0; k < 3; ++k) ems[i].radiance[k] = emitter_radiance[3 * i + k];
+    if (!mats.empty()) HIP_TRY(c, hipMemcpy((void *)s->dev.mats, mats.data(), mats.size() * sizeof(mtr_material), hipMemcpyHostToDevice));
+    if (!ems.empty()) HIP_TRY(c, hipMemcpy((void *)s->dev.ems, ems.data(), ems.size() * sizeof(Emitter), hipMemcpyHostToDevice));
+    // kTrGrey is the only trait that depends on colours (mtr_scene_create): decided again over the new tables
+    auto eq3 = [](const float *v) { return memcmp(v, v + 1, sizeof(float)) == 0 && memcmp(v, v + 2, sizeof(float)) == 0; };
+    bool grey = s->dev.texels == nullptr;
+    for (size_t i = 0; grey && i < mats.size(); ++i) {
+        const mtr_material &m = mats[i];
+        const bool aniso = (m.flags & MTR_MAT_ANISOTROPIC) != 0u;
+        grey = m.albedo_texture == 0u && eq3(m.a) && eq3(m.c) &&
+               ((aniso && m.type == MTR_BSDF_ROUGHDIELECTRIC) || eq3(m.b)) && ((aniso && m.type == MTR_BSDF_ROUGHCONDUCTOR) || eq3(m.c2));
+    }
+    for (size_t i = 0; grey && i < ems.size(); ++i) grey = eq3(ems[i].radiance);
+    s->grey_scene = grey;
+    s->dev.traits = grey ? (s->dev.traits | kTrGrey) : (s->dev.traits & ~kTrGrey);
     return MTR_OK;
 }
 
@@ -851,6 +883,68 @@ int mtr_render_plan(mtr_scene *s, const mtr_render_params *p, uint32_t *mode_out
     uint32_t mode = p->mode;
     if (int r = resolve_mode(s, p, p->pixel_end - p->pixel_begin, p->spp_end - p->spp_begin, &mode, developed_rows_ok)) return r;
     *mode_out = mode;
+    return MTR_OK;
+}
+
+int mtr_render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_s, const float *g_t,
+                    float *grad_materials, float *grad_emitters)
+{
+    if (!s || !p || !g_s || !g_t || !grad_materials || (s->dev.n_ems && !grad_emitters))
+        return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_render_grad: NULL argument");
+    mtr_ctx *c = s->ctx;
+    const Film &f = s->film;
+    const uint64_t npix_crop = (uint64_t)f.crop_w * f.crop_h;
+    if (p->spp_total == 0 || p->spp_begin > p->spp_end || p->spp_end > p->spp_total)
+        return fail(c, MTR_ERR_INVALID, "mtr_render_grad: bad sample range");
+    if (p->pixel_begin > p->pixel_end || p->pixel_end > npix_crop)
+        return fail(c, MTR_ERR_INVALID, "mtr_render_grad: bad pixel range");
+    if (npix_crop * p->spp_total > (1ull << 32))
+        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: W*H*spp exceeds 2^32 lanes (common.py:51); render in passes");
+    if (p->max_depth < -1 || p->rr_depth <= 0) return fail(c, MTR_ERR_INVALID, "mtr_render_grad: bad max_depth / rr_depth");
+    if (s->nlos.on || f.n_freq || f.lasers > 1u || (p->flags & MTR_FLAG_POLARIZED))
+        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: transient_path with a plain transient_hdr_film (RGB) only: "
+                                            "no NLOS tier, phasor film, exhaustive_scan or polarized transport");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t n_m = s->dev.n_mats, n_e = s->dev.n_ems, slab_n = 3u * (n_m + n_e);
+    const uint32_t n_pixels = p->pixel_end - p->pixel_begin, chunk = p->spp_end - p->spp_begin;
+    const uint64_t n_lanes = (uint64_t)n_pixels * chunk;
+    size_t lds = 0; bool scene_lds = false;
+    const uint32_t grid = n_lanes ? grad_grid(s->dev, n_lanes, c->n_cu, &lds, &scene_lds) : 0u;
+    if (n_lanes && grid == 0u) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: the gradient slab and traversal stack exceed LDS");
+    if (grid == 0u) {
+        HIP_TRY(c, hipMemsetAsync(grad_materials, 0, (size_t)n_m * 3u * sizeof(float), c->stream));
+        if (n_e) HIP_TRY(c, hipMemsetAsync(grad_emitters, 0, (size_t)n_e * 3u * sizeof(float), c->stream));
+        return MTR_OK;
+    }
+    // the traced emitter table carries unit radiance (a contribution without its radiance factor); the true radiance goes alongside
+    std::vector<Emitter> ems(n_e);
+    std::vector<float> rad(3u * (size_t)n_e + 3u, 0.0f);
+    if (n_e) HIP_TRY(c, hipMemcpy(ems.data(), s->dev.ems, n_e * sizeof(Emitter), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n_e; ++i)
+        for (int k = 0; k < 3; ++k) { rad[3u * i + k] = ems[i].radiance[k]; ems[i].radiance[k] = 1.0f; }
+    const size_t partial_b = (size_t)grid * slab_n * sizeof(double);
+    const size_t ems_b = ((size_t)n_e * sizeof(Emitter) + 255u) & ~(size_t)255u;
+    const size_t ws_b = ems_b + ((rad.size() * sizeof(float) + 255u) & ~(size_t)255u) + partial_b;
+    unsigned char *ws = nullptr;
+    HIP_TRY(c, hipMalloc((void **)&ws, ws_b));
+    Emitter *d_ems = (Emitter *)ws;
+    float *d_rad = (float *)(ws + ems_b);
+    double *d_partial = (double *)(ws + ems_b + ((rad.size() * sizeof(float) + 255u) & ~(size_t)255u));
+    hipError_t e = hipSuccess;
+    if (n_e) e = hipMemcpy(d_ems, ems.data(), n_e * sizeof(Emitter), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rad, rad.data(), rad.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const RenderConst rc = make_render_const(*p, f, n_e);
+        GradConst gc;
+        gc.g_s = g_s; gc.g_t = g_t; gc.em_radiance = d_rad;
+        gc.steady_scale = rc.sample_scale; gc.transient_scale = rc.sample_scale;
+        e = launch_grad(s->dev, d_ems, s->cam, f, rc, gc, p->pixel_begin, n_pixels, p->spp_begin, chunk, d_partial, grid, lds,
+                        scene_lds, grad_materials, grad_emitters, c->stream);
+    }
+    const hipError_t e_sync = hipStreamSynchronize(c->stream);
+    (void)hipFree(ws);
+    HIP_TRY(c, e);
+    HIP_TRY(c, e_sync);
     return MTR_OK;
 }
 

@@ -1959,11 +1959,14 @@ struct Pending {
 
 // Part A of one loop iteration (transientpath.py:148-218): consumes the closest hit, splats the
 // emission term, samples the emitter and emits the shadow ray.  RNG: next_2d (:193).
-template <bool ROUGH = true, uint32_t TR = 0u, class Sink>
+// pick: (optional) told the index of the emitter the emitter-sampling term samples (mtr_grad.h: whose radiance the term carries);
+// the default does nothing
+struct NoEmitterPick { MTR_HD void operator()(uint32_t) const {} };
+template <bool ROUGH = true, uint32_t TR = 0u, class Sink, class Pick = NoEmitterPick>
 // keep: (optional) the surface interaction for shade_finish — a caller that runs nothing between the two parts (k_wf_shade over scenes
 // in HBM: the shadow ray goes to a list) hands it over instead of having shade_finish fetch the shading record a second time
 MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &film, const RenderConst &rc,
-                      Sink &sink, Pending &pd, Ray &shadow, HitCtx *keep = nullptr)
+                      Sink &sink, Pending &pd, Ray &shadow, HitCtx *keep = nullptr, Pick pick = Pick())
 {
     constexpr bool kDiff = (TR & kTrDiffuse) != 0u, kOneRect = (TR & kTrOneRectEmitter) != 0u;
     const bool valid = h.prim >= 0;
@@ -2027,6 +2030,7 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
             if (i > n_emitters - 1) i = n_emitters - 1;
             ei = i; u1 = su - (float)i;
         }
+        pick(ei);
         const Emitter &E = sc.ems[ei];
         f3 ep, en;
         if (!kOneRect && E.is_mesh) {

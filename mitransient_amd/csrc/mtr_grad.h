@@ -1,0 +1,138 @@
+// mtr_grad.h — reverse-mode gradients of transient_path (ABI 15, mtr_render_grad): the per-lane arithmetic, shared by the
+// gfx950 kernel (mtr_grad.hip) and the host build of the tests (tests/host_grad.cpp).
+//
+// What is differentiated: the constant RGB reflectance of `diffuse` materials and the constant RGB radiance of
+// `area` / `angulararea` emitters, for the loss  sum g_s . steady + sum g_t . transient  of the seeded estimator, sampling
+// detached as in the reference's PRB (transientpath.py:284-299, integrators/common.py:325-409): Russian-roulette probabilities,
+// BSDF sampling and emitter sampling are constants.  Each contribution c (an emission or an emitter-sampling term) carries the
+// adjoint weight  w_c = g_s[pixel] * steady_scale + g_t[pixel, film_bin(opl_c)] * transient_scale  (the transient term only when
+// the bin is in range), and
+//   d loss / d a_m = sum_c w_c (.) c (.) n_m(c) / a_m       n_m(c): vertices on m whose BSDF factor is part of c
+//   d loss / d L_e = sum_{c lit by e} w_c (.) c / L_e      computed from c with the radiance left out: the traced emitter table
+//                                                         carries UNIT radiance, c = c_unit (.) L_e
+// PATH REPLAY in the time domain: a lane traces its path once to sum A = sum_c w_c (.) c, then again from the same seed,
+// subtracting each term as it is re-emitted; at every diffuse vertex the remaining sum (this vertex's emitter-sampling term and
+// every later term) divided by the vertex's albedo goes to its material.  Nothing per path is kept in memory between the walks.
+#pragma once
+#include "mtr_core.h"
+
+namespace mtr {
+
+struct GradConst {
+    const float *g_s;          // (H, W, 3): upstream gradient of the developed steady image
+    const float *g_t;          // (H, W, T, 3): upstream gradient of the developed transient tensor
+    const float *em_radiance;  // [n_emitters * 3]: the emitters' true radiance (the traced table has unit radiance)
+    float steady_scale;        // d steady / d contribution: 1 / total spp (develop divides the sum by the sample count)
+    float transient_scale;     // d transient / d contribution: the sample scale the splat multiplies by (common.py:417-421)
+};
+
+struct d3 { double x, y, z; };
+
+// shade_hit's emitter-pick hook (mtr_core.h): the index of the emitter its sampling term samples
+struct EmitterPickTo {
+    uint32_t *out;
+    MTR_HD void operator()(uint32_t e) const { *out = e; }
+};
+
+// Acc: add_mat(m, g) / add_em(e, g) receive the gradients; vertex(m, dist, active_next) and term(kind, e, opl, c_unit) see the
+// replay's vertices and terms in path order (kind 0 emission, 1 emitter sampling) — no-ops in the kernel, per-vertex records in
+// the host build of the tests (tests/host_grad.cpp)
+struct NullGradSink {
+    MTR_HD void splat(uint32_t, uint32_t, uint32_t, float, float, float, float, uint32_t, uint32_t) {}
+};
+
+// w_c of a contribution of film pixel (fx, fy) at optical path length opl; the bin is the splat's own (film_bin)
+MTR_HD f3 grad_weight(const GradConst &gc, const Film &film, uint32_t fx, uint32_t fy, float opl)
+{
+    if (!((fx < film.width) & (fy < film.height))) return mk(0, 0, 0);
+    const size_t pix = (size_t)fy * film.width + fx;
+    const float *gs = gc.g_s + 3u * pix;
+    f3 w = mk(gs[0] * gc.steady_scale, gs[1] * gc.steady_scale, gs[2] * gc.steady_scale);
+    const int32_t bin = film_bin(film, opl);
+    if (bin >= 0) {
+        const float *gt = gc.g_t + 3u * (pix * film.bins + (uint32_t)bin);
+        w = mk(fmaf(gt[0], gc.transient_scale, w.x), fmaf(gt[1], gc.transient_scale, w.y), fmaf(gt[2], gc.transient_scale, w.z));
+    }
+    return w;
+}
+
+// One walk of a lane's path (transientpath.py:140-319 through shade_hit / shade_finish, the general shading code).
+// REPLAY = false: returns A = sum_c w_c (.) c.  REPLAY = true: R starts at A; every term is subtracted as it is met, emitter
+// gradients go to acc.add_em(e, w_c (.) c_unit), material gradients to acc.add_mat(m, R / a_m) at each diffuse vertex whose
+// BSDF factor enters the remaining terms.  unwarp: camera_unwarp from bounce 0's own closest hit (as path_bounce).
+template <bool ROUGH, bool REPLAY, class Stack, class Acc>
+MTR_HD d3 grad_walk(Path p, const SceneView &sc, const Film &film, const RenderConst &rc, const GradConst &gc, Stack &st,
+                    Acc &acc, d3 R)
+{
+    NullGradSink ns;
+    const bool unwarp = (rc.flags & MTR_FLAG_CAMERA_UNWARP) != 0u;
+    const uint32_t fx = p.px - film.crop_x, fy = p.py - film.crop_y;
+    bool alive = true;
+    while (alive) {
+        const Hit h = traverse<false>(sc, p.ray.o, p.ray.d, p.ray.tmax, st);
+        if (unwarp && p.depth == 0u && h.prim >= 0) p.dist = -h.t;
+        Pending pd; Ray shadow; HitCtx hc;
+        shadow.o = mk(0, 0, 0); shadow.d = mk(0, 0, 1); shadow.tmax = 0.0f;
+        hc.em_plus1 = 0u; hc.mat = 0u;
+        uint32_t e_sampled = 0u;                             // which emitter shade_hit's emitter-sampling term samples
+        shade_hit<ROUGH>(p, h, sc, film, rc, ns, pd, shadow, &hc, EmitterPickTo{ &e_sampled });
+        const bool valid = h.prim >= 0;
+        if (REPLAY && valid) acc.vertex(hc.mat, p.dist, pd.active_next != 0u);
+        // emission (transientpath.py:166-180), at the distance of this vertex
+        if (valid && hc.em_plus1 != 0u) {
+            const uint32_t e = hc.em_plus1 - 1u;
+            const float *L = gc.em_radiance + 3u * e;
+            const f3 w = grad_weight(gc, film, fx, fy, p.dist);
+            const f3 cu = pd.Le;
+            const double cx = (double)w.x * (double)(cu.x * L[0]), cy = (double)w.y * (double)(cu.y * L[1]),
+                         cz = (double)w.z * (double)(cu.z * L[2]);
+            if (REPLAY) {
+                R.x -= cx; R.y -= cy; R.z -= cz;
+                acc.add_em(e, mk(w.x * cu.x, w.y * cu.y, w.z * cu.z));
+                acc.term(0u, e, p.dist, cu);
+            } else { R.x += cx; R.y += cy; R.z += cz; }
+        }
+        // the BSDF factor of this vertex is part of its emitter-sampling term and of every later term
+        if (REPLAY && valid && pd.active_next) {
+            const mtr_material &m = sc.mats[hc.mat];
+            if (m.type == MTR_BSDF_DIFFUSE && m.albedo_texture == 0u) {
+                // a zero channel gets no gradient from paths through m (its remaining sum is zero up to rounding)
+                acc.add_mat(hc.mat, mk(m.a[0] != 0.0f ? (float)(R.x / (double)m.a[0]) : 0.0f,
+                                       m.a[1] != 0.0f ? (float)(R.y / (double)m.a[1]) : 0.0f,
+                                       m.a[2] != 0.0f ? (float)(R.z / (double)m.a[2]) : 0.0f));
+            }
+        }
+        bool occluded = false;
+        if (pd.has_shadow) occluded = traverse<true>(sc, shadow.o, shadow.d, shadow.tmax, st).prim >= 0;
+        // emitter sampling (:188-218), at distance + ds.dist * eta
+        if (pd.has_shadow && !occluded) {
+            const uint32_t e = e_sampled;
+            const float *L = gc.em_radiance + 3u * e;
+            const f3 w = grad_weight(gc, film, fx, fy, pd.opl);
+            const f3 cu = pd.Lr;
+            const double cx = (double)w.x * (double)(cu.x * L[0]), cy = (double)w.y * (double)(cu.y * L[1]),
+                         cz = (double)w.z * (double)(cu.z * L[2]);
+            if (REPLAY) {
+                R.x -= cx; R.y -= cy; R.z -= cz;
+                acc.add_em(e, mk(w.x * cu.x, w.y * cu.y, w.z * cu.z));
+                acc.term(1u, e, pd.opl, cu);
+            } else { R.x += cx; R.y += cy; R.z += cz; }
+        }
+        alive = shade_finish<ROUGH>(p, h, occluded, pd, sc, film, rc, ns);
+    }
+    return R;
+}
+
+// lane (pixel, s) of the render: identity = RNG identity (lane = pixel * spp_total + s), as every primal organisation
+template <bool ROUGH, class Stack, class Acc>
+MTR_HD void grad_lane(const SceneView &sc, const Camera &cam, const Film &film, const RenderConst &rc, const GradConst &gc,
+                      uint32_t pixel, uint32_t s, Stack &st, Acc &acc)
+{
+    Path p;
+    path_begin(p, cam, film, rc, pixel, s);
+    const d3 zero = { 0.0, 0.0, 0.0 };
+    const d3 A = grad_walk<ROUGH, false>(p, sc, film, rc, gc, st, acc, zero);
+    grad_walk<ROUGH, true>(p, sc, film, rc, gc, st, acc, A);
+}
+
+} // namespace mtr

@@ -53,6 +53,42 @@ __device__ __forceinline__ void nt_store(float4 *p, float4 v)
     __builtin_nontemporal_store(v.x, w); __builtin_nontemporal_store(v.y, w + 1); __builtin_nontemporal_store(v.z, w + 2); __builtin_nontemporal_store(v.w, w + 3);
 }
 
+// per-lane traversal stack in LDS: column `tid` of kBlock-wide rows (the wavefront kernels, k_grad_paths)
+struct WStack {
+    static constexpr bool kPark = false;      // (k_fused's stack can park path state in LDS: mtr_kernels.hip)
+    __device__ __forceinline__ void park_prev_p(mtr::f3) {}
+    __device__ __forceinline__ mtr::f3 unpark_prev_p() const { return mtr::mk(0, 0, 0); }
+    __device__ __forceinline__ void park_inc(uint64_t) {}
+    __device__ __forceinline__ uint64_t unpark_inc() const { return 0; }
+    __device__ __forceinline__ void park_prev_pdf(float) {}
+    __device__ __forceinline__ float unpark_prev_pdf() const { return 0.0f; }
+    int32_t *base; int sp;
+    __device__ __forceinline__ void reset() { sp = 0; }
+    __device__ __forceinline__ void push_if(bool c, int32_t v) { base[sp * kBlock] = v; sp += c ? 1 : 0; }
+    __device__ __forceinline__ int32_t pop() { --sp; return base[sp * kBlock]; }
+    __device__ __forceinline__ bool empty() const { return sp == 0; }
+    __device__ __forceinline__ void prof_mark(int) {}
+    __device__ __forceinline__ void prof_flat(int) {}
+    __device__ __forceinline__ void count(int) {}
+    __device__ __forceinline__ void tail(unsigned int) {}
+};
+
+// stage the scene in LDS: sizes, the copy, the stack rows a walk needs (one group per level of the tree walked, + 1: push_if writes
+// before it counts)
+__host__ __device__ constexpr uint32_t al16(uint32_t x) { return (x + 15u) & ~15u; }
+__device__ __forceinline__ void cp16(void *dst, const void *src, uint32_t bytes, int tid)
+{
+    const uint4 *s = (const uint4 *)src; uint4 *d = (uint4 *)dst;
+    for (uint32_t i = tid; i < bytes / 16u; i += kBlock) d[i] = s[i];
+}
+__host__ __device__ inline uint32_t wf_stack_rows(const SceneDev &sc, bool scene_lds) { return (scene_lds ? sc.wide_levels : (sc.wnodes8q ? sc.wide8q_levels : sc.wide4_levels)) + 1u; }
+// bytes of the tables a kernel stages in LDS: 8-wide tree, triangle pairs, shading records, materials, emitters
+__host__ __device__ inline uint32_t lds_scene_bytes(const SceneDev &sc)
+{
+    return al16(sc.n_wnodes * sizeof(WNode)) + al16(sc.n_slots / 2 * sizeof(TriPair)) + al16(sc.n_slots * sizeof(TriShade)) +
+           al16(sc.n_mats * sizeof(mtr_material)) + al16(sc.n_ems * sizeof(Emitter));
+}
+
 struct SplatLog { uint32_t *rec; unsigned long long cap; unsigned long long *count; };
 
 struct FusedArgs {
@@ -159,5 +195,12 @@ size_t splat_partition_scratch_bytes(const mtr_splat_soa &s, const Film &film);
 hipError_t launch_splat_partitioned(const mtr_splat_soa &s, const Film &film, float *film_out, bool film_zero, DevCounters *counters,
                                     void *scratch, int n_cu, hipStream_t stream);
 hipError_t launch_develop(const Film &film, const float *t4, float *t3, const float *s4, float *s3, hipStream_t stream);
+
+// mtr_render_grad (mtr_grad.hip): the grid of k_grad_paths (0: its LDS does not fit), then both kernels
+struct GradConst;
+uint32_t grad_grid(const SceneDev &sc, uint64_t n_lanes, int n_cu, size_t *lds_out, bool *scene_lds_out);
+hipError_t launch_grad(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
+                       const GradConst &gc, uint32_t pixel_begin, uint32_t n_pixels, uint32_t spp_begin, uint32_t spp_chunk,
+                       double *partial, uint32_t grid, size_t lds, bool scene_lds, float *grad_mats, float *grad_ems, hipStream_t stream);
 
 } // namespace mtr

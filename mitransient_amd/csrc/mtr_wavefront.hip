@@ -32,39 +32,9 @@ namespace mtr {
 
 namespace {
 
-template <int DEPTH>
-struct WStack {
-    static constexpr bool kPark = false;      // (k_fused's stack can park path state in LDS: mtr_kernels.hip)
-    __device__ __forceinline__ void park_prev_p(mtr::f3) {}
-    __device__ __forceinline__ mtr::f3 unpark_prev_p() const { return mtr::mk(0, 0, 0); }
-    __device__ __forceinline__ void park_inc(uint64_t) {}
-    __device__ __forceinline__ uint64_t unpark_inc() const { return 0; }
-    __device__ __forceinline__ void park_prev_pdf(float) {}
-    __device__ __forceinline__ float unpark_prev_pdf() const { return 0.0f; }
-    int32_t *base; int sp;
-    __device__ __forceinline__ void reset() { sp = 0; }
-    __device__ __forceinline__ void push_if(bool c, int32_t v) { base[sp * kBlock] = v; sp += c ? 1 : 0; }
-    __device__ __forceinline__ int32_t pop() { --sp; return base[sp * kBlock]; }
-    __device__ __forceinline__ bool empty() const { return sp == 0; }
-    __device__ __forceinline__ void prof_mark(int) {}
-    __device__ __forceinline__ void prof_flat(int) {}
-    __device__ __forceinline__ void count(int) {}
-    __device__ __forceinline__ void tail(unsigned int) {}
-};
-
-__host__ __device__ constexpr uint32_t al16(uint32_t x) { return (x + 15u) & ~15u; }
-
-__device__ __forceinline__ void cp16(void *dst, const void *src, uint32_t bytes, int tid)
-{
-    const uint4 *s = (const uint4 *)src; uint4 *d = (uint4 *)dst;
-    for (uint32_t i = tid; i < bytes / 16u; i += kBlock) d[i] = s[i];
-}
-
 // stage the scene in LDS (or point at HBM) and carve the traversal stack
-__host__ __device__ inline uint32_t wf_stack_rows(const SceneDev &sc, bool scene_lds) { return (scene_lds ? sc.wide_levels : (sc.wnodes8q ? sc.wide8q_levels : sc.wide4_levels)) + 1u; }
-
 template <int STACK, bool SCENE_LDS>
-__device__ __forceinline__ void wf_setup(const SceneDev &sc, unsigned char *smem, int tid, SceneView &sv, WStack<STACK> &st,
+__device__ __forceinline__ void wf_setup(const SceneDev &sc, unsigned char *smem, int tid, SceneView &sv, WStack &st,
                                          uint32_t &off)
 {
     // all LDS scratch lives in the dynamic region, every carve offset a multiple of 16 (a static
@@ -407,7 +377,7 @@ __global__ void __launch_bounds__(kBlock) k_wf_raygen(const WfArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
-    SceneView sv; WStack<STACK> st; uint32_t off;
+    SceneView sv; WStack st; uint32_t off;
     wf_setup<STACK, SCENE_LDS>(a.sc, smem, tid, sv, st, off);
     const PlanesT<!SCENE_LDS> P{ (float4 *)a.planes, a.n_slots };
     uint32_t n_closest = 0;
@@ -477,7 +447,7 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_TRACE_WAVES_LDS : (
     uint32_t *s_fetch = (uint32_t *)smem + 8;                   // cursor into the segment's live list
     const int tid = threadIdx.x;
     const uint32_t lane_id = (uint32_t)tid & 63u;
-    SceneView sv; WStack<STACK> st; uint32_t off;
+    SceneView sv; WStack st; uint32_t off;
     wf_setup<STACK, SCENE_LDS>(a.sc, smem, tid, sv, st, off);
     uint8_t *s_key = (uint8_t *)(smem + off);                   // [seg] hit material type per list position
     const PlanesT<!SCENE_LDS> P{ (float4 *)a.planes, a.n_slots };
@@ -656,7 +626,7 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_SHADE_WAVES_LDS : M
     uint32_t *s_shadow_p = (uint32_t *)smem + 1;                // (DEFER) tail of the segment's shadow-ray list
     uint32_t *s_zombie_p = (uint32_t *)smem + 2;                // (DEFER) tail of the segment's next zombie list
     const int tid = threadIdx.x;
-    SceneView sv; WStack<STACK> st; uint32_t off;
+    SceneView sv; WStack st; uint32_t off;
     wf_setup<STACK, SCENE_LDS>(a.sc, smem, tid, sv, st, off);
     uint32_t *s_rec = (uint32_t *)(smem + off);                 // [G] record-list tails of the segment's pixels
     float *s_steady = (float *)(smem + off + al16(a.G * 4u));   // [G][4] radiance sums of the paths that end here
@@ -871,7 +841,7 @@ __global__ void __launch_bounds__(kBlock, 2) k_wf_nlos_bounce(const WfArgs a)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t *s_next_p = (uint32_t *)smem;
     const int tid = threadIdx.x;
-    SceneView sv; WStack<STACK> st; uint32_t off;
+    SceneView sv; WStack st; uint32_t off;
     wf_setup<STACK, SCENE_LDS>(a.sc, smem, tid, sv, st, off);
     uint32_t *s_rec = (uint32_t *)(smem + off);
     float *s_steady = (float *)(smem + off + al16(a.G * 4u));
@@ -1212,7 +1182,7 @@ __global__ void __launch_bounds__(kBlock, 2) k_wf_polar_bounce(const WfArgs a)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t *s_next_p = (uint32_t *)smem;
     const int tid = threadIdx.x;
-    SceneView sv; WStack<STACK> st; uint32_t off;
+    SceneView sv; WStack st; uint32_t off;
     wf_setup<STACK, SCENE_LDS>(a.sc, smem, tid, sv, st, off);
     uint32_t *s_rec = (uint32_t *)(smem + off);
     float *s_steady = (float *)(smem + off + al16(a.G * 4u));
@@ -1410,8 +1380,7 @@ bool wf_plan(const SceneDev &sc, WfConfig &cfg)
 {
     if (sc.bvh_depth > 64) return false;
     cfg.stack = sc.bvh_depth <= 8 ? 8 : sc.bvh_depth <= 16 ? 16 : sc.bvh_depth <= 32 ? 32 : 64;
-    uint32_t scene_b = al16(sc.n_wnodes * sizeof(WNode)) + al16(sc.n_slots / 2 * sizeof(TriPair)) + al16(sc.n_slots * sizeof(TriShade)) +
-                       al16(sc.n_mats * sizeof(mtr_material)) + al16(sc.n_ems * sizeof(Emitter));
+    const uint32_t scene_b = lds_scene_bytes(sc);
     cfg.scene_lds = sc.wnodes != nullptr && scene_b <= 64u * 1024u;
     cfg.lds_bytes = 64 + (size_t)wf_stack_rows(sc, cfg.scene_lds) * kBlock * 4 + (cfg.scene_lds ? scene_b : 0) + 16;
     return true;

@@ -161,6 +161,10 @@ class DistributedRenderer:
         self.last_collectives = 0        # collectives the last render issued on the data path
         self.owned_rows = None
 
+    def render_backward(self, *a, **k):
+        raise ValueError("DistributedRenderer: differentiable rendering is available on one GPU only (render_backward of the "
+                         "scene's integrator)")
+
     def render(self, spp: int, seed: int = 0, sensor: int = 0):
         import torch
         import torch.distributed as dist

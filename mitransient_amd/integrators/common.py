@@ -4,7 +4,8 @@ Mirrors mitransient/integrators/common.py — ``__init__`` (:22-30), ``prepare``
 ``render`` (:122-213), ``add_transient_f`` (:411-422), ``check_transient_`` (:424-447) —
 with the Dr.Jit trace replaced by launches of the HIP library: ``sample_rays`` +
 ``sample`` + the film splats of one pass are ONE call to ``mtr_render``.
-The AD entry points (render_forward / render_backward, :215-409) are out of scope.
+``render_backward`` (:325-409) is the reverse mode over the constant diffuse reflectances and emitter radiances (one call to
+``mtr_render_grad`` per pass); ``render_forward`` (:215-323) is not available.
 """
 from __future__ import annotations
 
@@ -93,6 +94,11 @@ class TransientADIntegrator:
         if wavefront_size > self.max_wavefront_size and int(self.pass_wavefront_size / n_pixels) == 0:
             raise Exception("Your film is too big. Please make it smaller.")      # (before the film's storage is allocated)
         film.prepare(aovs)
+        return self._pass_samplers(sensor, sampler, seed, spp, n_pixels)
+
+    def _pass_samplers(self, sensor, sampler, seed, spp, n_pixels):
+        """prepare()'s samplers of the passes (common.py:51-85) for a sampler whose sample count is ``spp``"""
+        wavefront_size = n_pixels * spp
         if wavefront_size <= self.max_wavefront_size:
             sampler.seed(seed, wavefront_size)
             return [(sampler, spp)]
@@ -311,10 +317,97 @@ class TransientADIntegrator:
         return self.total_counters
 
     def render_forward(self, *a, **k):
-        raise NotImplementedError("differentiable rendering (common.py:215-323) is outside the north-star path")
+        raise NotImplementedError("forward-mode differentiation (common.py:215-323) is not available; use render_backward")
 
-    def render_backward(self, *a, **k):
-        raise NotImplementedError("differentiable rendering (common.py:325-409) is outside the north-star path")
+    # -- common.py:325-409 -----------------------------------------------------
+    def check_grad_(self, scene, sensor, params):
+        """the refusals of the reverse mode (ValueError), all of them before any GPU work"""
+        from ..films.phasor_hdr_film import PhasorHDRFilm
+        from .transientnlospath import TransientNLOSPath
+        v = variant.get() or ""
+        if not v.endswith("_ad_rgb"):
+            raise ValueError(f"{v}: differentiable rendering is available in the *_ad_rgb variants only")
+        if isinstance(self, TransientNLOSPath):
+            raise ValueError("transient_nlos_path: differentiable rendering is available with transient_path only")
+        if isinstance(sensor, int):
+            sensor = scene.sensors()[sensor]
+        film = sensor.film()
+        if isinstance(film, PhasorHDRFilm):
+            raise ValueError("phasor_hdr_film: differentiable rendering needs a transient_hdr_film")
+        if not isinstance(film, TransientHDRFilm):
+            raise ValueError("differentiable rendering needs a transient_hdr_film")
+        if film.exhaustive_scan:
+            raise ValueError("transient_hdr_film with exhaustive_scan: differentiable rendering is not available")
+        wanted = [k for k, val in (params or {}).items() if getattr(val, "requires_grad", False)]
+        scene.ensure_own_records([k for k in wanted if k in scene.param_keys()], sensor)
+        keys = scene.grad_keys(sensor)
+        for k, val in (params or {}).items():
+            if getattr(val, "requires_grad", False) and k not in keys:
+                raise ValueError(f"{k}: not a differentiable parameter (the constant reflectance of a diffuse BSDF and the "
+                                 f"constant radiance of an area / angulararea emitter are: {sorted(keys)})")
+        return keys
+
+    def render_backward(self, scene, params, grad_in, sensor=0, seed=0, spp=0):
+        """Gradients of  sum g_s . steady + sum g_t . transient  of the seeded estimator (``grad_in = (g_s, g_t)``, the upstream
+        gradients of the developed (H, W, 3) / (H, W, T, 3) tensors) with respect to every value of ``params`` that requires grad:
+        ``{key: torch.float32 (3,)}`` on the render device.  Sampling is detached."""
+        import torch
+        keys = self.check_grad_(scene, sensor, params)
+        wanted = [k for k, val in (params or {}).items() if getattr(val, "requires_grad", False)]
+        if isinstance(sensor, int):
+            sensor = scene.sensors()[sensor]
+        film = sensor.film()
+        if getattr(params, "_dirty", None):
+            params.update()
+        # the passes and seeds of render() (prepare, without touching the film: the primal's tensors stay as they are)
+        sampler = sensor.sampler().clone()
+        if spp != 0:
+            sampler.set_sample_count(spp)
+        spp = sampler.sample_count()
+        sampler.set_samples_per_wavefront(spp)
+        n_pixels = film.crop_size()[0] * film.crop_size()[1]
+        if n_pixels * spp > self.max_wavefront_size and int(self.pass_wavefront_size / n_pixels) == 0:
+            raise Exception("Your film is too big. Please make it smaller.")
+        samplers_spps = self._pass_samplers(sensor, sampler, seed, spp, n_pixels)
+        total_spp = sum(s for _, s in samplers_spps)
+        W, H = film.size()
+        cw, ch = film.crop_size()
+        T = film.temporal_bins
+        dev = film._device if film._device is not None else torch.device("cuda", torch.cuda.current_device())
+        g_s, g_t = grad_in
+        g_s = torch.zeros((ch, cw, 3), dtype=torch.float32, device=dev) if g_s is None else \
+            torch.as_tensor(g_s.torch() if hasattr(g_s, "torch") else g_s).to(device=dev, dtype=torch.float32)
+        g_t = torch.zeros((H, W, T, 3), dtype=torch.float32, device=dev) if g_t is None else \
+            torch.as_tensor(g_t.torch() if hasattr(g_t, "torch") else g_t).to(device=dev, dtype=torch.float32)
+        if tuple(g_s.shape) != (ch, cw, 3) or tuple(g_t.shape) != (H, W, T, 3):
+            raise ValueError(f"render_backward: grad_in shapes {tuple(g_s.shape)}, {tuple(g_t.shape)}; expected "
+                             f"{(ch, cw, 3)}, {(H, W, T, 3)}")
+        # the steady gradient in the accumulator's layout: (H, W, 3), the crop window at the top-left corner (develop's view)
+        gs_full = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+        gs_full[:ch, :cw] = g_s
+        g_t = g_t.contiguous()
+        ctx = get_context(dev.index)
+        ctx.bind_current_stream()
+        handle = scene.gpu_handle(ctx, sensor)
+        sd = scene.data(sensor)
+        n_m, n_e = max(1, sd.n_materials), max(1, sd.n_emitters)
+        gm = torch.zeros((n_m, 3), dtype=torch.float32, device=dev)
+        ge = torch.zeros((n_e, 3), dtype=torch.float32, device=dev)
+        pm = torch.empty_like(gm)
+        pe = torch.empty_like(ge)
+        multi = len(samplers_spps) > 1
+        for sampler_i, spp_i in samplers_spps:
+            p = self.render_params(film, sampler_i.seed_value(), spp_i if multi else total_spp, 0, spp_i, 0, None,
+                                   spp_scale=total_spp if multi else 0)
+            ctx.check(ctx.lib.mtr_render_grad(handle, C.byref(p), C.c_void_p(gs_full.data_ptr()), C.c_void_p(g_t.data_ptr()),
+                                              C.c_void_p(pm.data_ptr()), C.c_void_p(pe.data_ptr())), "mtr_render_grad")
+            gm += pm
+            ge += pe
+        out = {}
+        for k in wanted:
+            kind, i = keys[k]
+            out[k] = (gm if kind == "material" else ge)[i].clone()
+        return out
 
     def to_string(self):
         return f"{type(self).__name__}[\n  max_depth = {self.max_depth}, \n  rr_depth = {self.rr_depth}\n]"

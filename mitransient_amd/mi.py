@@ -140,6 +140,9 @@ class Scene:
     def __init__(self, d: Dict[str, Any], base_dir: str = ".", approximate_materials: bool = False, geometry=None):
         self.approximate_materials = approximate_materials
         self.geometry_ = geometry              # pre-flattened triangles + tables (scene.load_geometry), or None
+        # differentiable parameters (mi.traverse): one material record per key, and the values set through params.update()
+        self.own_materials_ = False
+        self.param_values_ = {}
         from . import integrators as _i, films as _f  # noqa: F401  (registers the plugins)
         from .shapes import Shape
         from .emitters import Projector
@@ -225,7 +228,9 @@ class Scene:
         self._data_ver[key] = ver
         if key not in self._data:
             self._data[key] = flatten_scene(self.dict_, sensor.film(), sensor.dict_, self.base_dir,
-                                            self.relay_names_.get(key), self.approximate_materials, self.geometry_)
+                                            self.relay_names_.get(key), self.approximate_materials, self.geometry_,
+                                            own_materials=self.own_materials_)
+            self._apply_params(self._data[key])
         sd = self._data[key]
         sd.film = film_desc_from(sensor.film())
         from .integrators.transientnlospath import TransientNLOSPath
@@ -241,6 +246,66 @@ class Scene:
                                      "NLOS capture meter. You should have only 1.")
             sd.nlos = nlos_desc_from(self.integrator_, sensor, self.emitters_[0], sd.relay_shape)
         return sd
+
+    # -- differentiable parameters (mi.traverse keys of mtr_render_grad) ------------------------------------------
+    def param_keys(self):
+        """{key: 3 floats}: the differentiable parameters and their values, from the dictionary (nothing is flattened)"""
+        from .scene import param_locations, rgb3
+        if self.geometry_ is not None:
+            return {}
+        return {k: list(self.param_values_.get(k, rgb3(v))) for k, (_, _, v) in param_locations(self.dict_).items()}
+
+    def grad_keys(self, sensor=0):
+        """{key: ("material" | "emitter", index)}: the parameters mtr_render_grad differentiates, resolved to the flattened
+        tables"""
+        return self.data(sensor).grad_keys
+
+    def ensure_own_records(self, keys, sensor=0):
+        """every key of ``keys`` must own its material record: a BSDF dictionary that several shapes share is flattened once per
+        shape from then on (only when one of its keys is set or differentiated: other scenes keep their tables as they are)"""
+        if self.own_materials_:
+            return
+        gk = self.data(sensor).grad_keys
+        recs = list(gk.values())
+        if any(k in gk and recs.count(gk[k]) > 1 for k in keys):
+            self.own_materials_ = True
+            for key in list(self._data):
+                del self._data[key]
+                self._drop_handles(key)
+
+    def _apply_params(self, sd):
+        for k, v in self.param_values_.items():
+            if k not in sd.grad_keys:
+                continue
+            kind, i = sd.grad_keys[k]
+            arr = sd.materials[i].a if kind == "material" else sd.emitters[i].radiance
+            for c in range(3):
+                arr[c] = v[c]
+
+    def set_param(self, key, value):
+        """a differentiable parameter's new value (3 floats): the flattened tables take it, and the device scenes re-upload their
+        material and emitter tables (mtr_scene_set_colors) — no BVH is rebuilt"""
+        import numpy as np
+        if key not in self.param_keys():
+            raise KeyError(key)
+        if hasattr(value, "detach"):
+            value = value.detach().cpu().numpy()
+        v = np.asarray(value, dtype=np.float64).reshape(-1)
+        if v.size == 1:
+            v = np.repeat(v, 3)
+        if v.size != 3:
+            raise ValueError(f"{key}: expected 3 values, got {v.size}")
+        self.ensure_own_records([key])
+        self.param_values_[key] = [float(np.float32(x)) for x in v]
+        lib = _cabi.load_library()
+        for skey, sd in self._data.items():
+            self._apply_params(sd)
+            a = np.array([[sd.materials[i].a[c] for c in range(3)] for i in range(max(1, sd.n_materials))], np.float32)
+            r = np.array([[sd.emitters[i].radiance[c] for c in range(3)] for i in range(max(1, sd.n_emitters))], np.float32)
+            for hkey in [h for h in self._handles if h[0] == skey]:
+                if lib.mtr_scene_set_colors(self._handles[hkey], C.c_void_p(a.ctypes.data), C.c_void_p(r.ctypes.data)) != 0:
+                    lib.mtr_scene_destroy(self._handles.pop(hkey))     # (the NLOS tier: the next render creates the scene again)
+                    self._nlos_fp.pop(hkey, None)
 
     def gpu_handle(self, ctx, sensor=0):
         if isinstance(sensor, int):
@@ -310,11 +375,60 @@ def load_dict(d: Dict[str, Any], base_dir: str = ".", approximate_materials: boo
     raise ValueError(f"load_dict(): unsupported top-level plugin type \"{t}\"")
 
 
+def _tea32(v0, v1, rounds=4):
+    """sample_tea_32 (mitsuba3's TEA, 4 rounds): returns v0"""
+    M = 0xFFFFFFFF
+    v0, v1, s = v0 & M, v1 & M, 0
+    for _ in range(rounds):
+        s = (s + 0x9E3779B9) & M
+        v0 = (v0 + ((((v1 << 4) & M) + 0xA341316C) ^ ((v1 + s) & M) ^ ((v1 >> 5) + 0xC8013EA4))) & M
+        v1 = (v1 + ((((v0 << 4) & M) + 0xAD90777D) ^ ((v0 + s) & M) ^ ((v0 >> 5) + 0x7E95761E))) & M
+    return v0
+
+
+def _grad_values(params):
+    """the (key, tensor) pairs of ``params`` whose value is a torch tensor that requires grad"""
+    if not params:
+        return []
+    return [(k, v) for k, v in params.items() if getattr(v, "requires_grad", False)]
+
+
 def render(scene: Scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, spp=0, spp_grad=0):
     """``mi.render``: returns ``(steady (H,W,3), transient (H,W,T,3))`` like the reference's
-    TransientADIntegrator.render (common.py:212-213)."""
+    TransientADIntegrator.render (common.py:212-213).  When a value of ``params`` is a torch tensor that requires grad, the
+    tensors' ``.torch()`` carry a ``grad_fn``: their backward pass is ``integrator.render_backward`` at ``seed_grad`` (0: a TEA
+    scramble of ``seed``, as mitsuba's mi.render) with ``spp_grad`` samples (0: ``spp``)."""
     integ = integrator or scene.integrator()
-    return integ.render(scene, sensor=sensor, seed=seed, spp=spp)
+    grads = _grad_values(params)
+    if not grads:
+        return integ.render(scene, sensor=sensor, seed=seed, spp=spp)
+    if not hasattr(integ, "check_grad_"):
+        raise ValueError(f"{type(integ).__name__}: differentiable rendering is available with transient_path on one GPU only")
+    integ.check_grad_(scene, sensor, params)              # every refusal before any GPU work
+    if spp_grad == 0:
+        spp_grad = spp
+    if seed_grad == 0:
+        seed_grad = _tea32(seed, 1)                       # de-correlates the primal and the differential phase
+    elif seed_grad == seed:
+        raise ValueError("The primal and differential seed should be different to ensure unbiased gradient computation!")
+    if getattr(params, "_dirty", None):
+        params.update()
+    import torch
+
+    class _Render(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, *values):
+            steady, transient = integ.render(scene, sensor=sensor, seed=seed, spp=spp)
+            return steady.torch().clone(), transient.torch().clone()
+
+        @staticmethod
+        def backward(ctx, g_s, g_t):
+            g = integ.render_backward(scene, params, grad_in=(g_s, g_t), sensor=sensor, seed=seed_grad, spp=spp_grad)
+            return tuple(g[k].to(dtype=v.dtype, device=v.device).reshape(v.shape) if v.numel() == 3 else g[k].sum().reshape(v.shape)
+                         for k, v in grads)
+
+    s, t = _Render.apply(*[v for _, v in grads])
+    return TensorXf(s), TensorXf(t)
 
 
 class _Params(dict):
@@ -332,6 +446,9 @@ class _Params(dict):
             return super().update(*a, **k)
         for key in self._dirty:
             obj, attr = self._objs[key]
+            if isinstance(obj, Scene):                 # a differentiable parameter (attr is its key)
+                obj.set_param(attr, self[key])
+                continue
             cur = getattr(obj, attr)
             try:
                 setattr(obj, attr, type(cur)(self[key]))
@@ -353,7 +470,13 @@ def traverse(obj):
             objs[self.prefix + name] = (self.o, name)
 
     targets = []
+    scene_keys = {}
     if isinstance(obj, Scene):
+        # mitsuba's keys of the differentiable parameters: <bsdf id>.reflectance.value,
+        # <shape id>.bsdf[.brdf_0].reflectance.value, <shape id>.emitter.radiance.value
+        for k, v in obj.param_keys().items():
+            objs[k] = (obj, k)
+            scene_keys[k] = v
         for i, s in enumerate(obj.sensors()):
             targets.append((f"sensor{'' if i == 0 else i}.film.", s.film()))
             if isinstance(s, PerspectiveSensor):
@@ -367,7 +490,7 @@ def traverse(obj):
         o.traverse(_CB(prefix, o))
     p = _Params(objs)
     for k, (o, attr) in objs.items():
-        dict.__setitem__(p, k, getattr(o, attr))
+        dict.__setitem__(p, k, scene_keys[k] if k in scene_keys else getattr(o, attr))
     return p
 
 

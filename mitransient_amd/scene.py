@@ -153,8 +153,14 @@ def fresnel_diffuse_reflectance(eta):
 
 
 class _SceneBuilder:
-    def __init__(self, d: Dict[str, Any], base_dir: str = ".", approximate_materials: bool = False):
+    def __init__(self, d: Dict[str, Any], base_dir: str = ".", approximate_materials: bool = False, own_materials: bool = False):
         self.d = d
+        # own_materials (differentiable parameters, mi.traverse): a BSDF written inline gets a material record per shape, even where
+        # one dictionary object is shared by several shapes, so that no two parameter keys share a record
+        self.own_materials = own_materials
+        self.cur_shape = None
+        self.shape_mat: Dict[str, int] = {}
+        self.shape_em: Dict[str, int] = {}
         self.base_dir = base_dir
         self.approx = approximate_materials
         self.mesh_cache: Dict[str, np.ndarray] = {}
@@ -184,7 +190,7 @@ class _SceneBuilder:
             if rid not in self.d:
                 raise ValueError(f"reference to unknown object '{rid}'")
             return self.d[rid], ("ref", rid)
-        return v, ("obj", id(v))
+        return v, ("obj", id(v), self.cur_shape) if self.own_materials else ("obj", id(v))
 
     def material_index(self, v) -> int:
         bd, key = self._resolve(v)
@@ -432,7 +438,10 @@ class _SceneBuilder:
                 bsdf = v
         if bsdf is None:
             bsdf = {"type": "diffuse", "reflectance": 0.5}     # mitsuba's default BSDF
+        self.cur_shape = name
         mi_ = self.material_index(bsdf)
+        self.cur_shape = None
+        self.shape_mat[name] = mi_
         em_index = -1
         if em is not None:
             et = em.get("type")
@@ -459,6 +468,7 @@ class _SceneBuilder:
                 e.radiance[k] = np.float32(rad[k])
             self.emitters.append(e)
             em_index = len(self.emitters) - 1
+            self.shape_em[name] = em_index
         n = tris.shape[0]
         first = sum(a.shape[0] for a in self.tri_verts)
         self.tri_verts.append(tris.astype(np.float32))
@@ -921,8 +931,8 @@ def _check_polarized(b, film, sd):
 
 def flatten_scene(d: Dict[str, Any], film, sensor_dict: Dict[str, Any], base_dir: str = ".",
                   relay_shape_name: Optional[str] = None, approximate_materials: bool = False,
-                  geometry: Optional[Dict[str, Any]] = None) -> SceneData:
-    b = _SceneBuilder(d, base_dir, approximate_materials)
+                  geometry: Optional[Dict[str, Any]] = None, own_materials: bool = False) -> SceneData:
+    b = _SceneBuilder(d, base_dir, approximate_materials, own_materials)
     for name, v in d.items():
         if not isinstance(v, dict):
             continue
@@ -994,4 +1004,92 @@ def flatten_scene(d: Dict[str, Any], film, sensor_dict: Dict[str, Any], base_dir
     sd.film = film_desc_from(film)
     sd.shape_names, sd.shape_ranges = b.shape_names, b.shape_ranges
     sd.relay_shape = b.shape_names.index(relay_shape_name) if relay_shape_name is not None else -1
+    sd.grad_keys = differentiable_keys(d, b) if geometry is None else {}
     return sd
+
+
+def _constant_rgb(v):
+    """a constant colour of a scene dictionary (a float, three floats or an ``rgb`` dictionary); None for anything else"""
+    if isinstance(v, dict):
+        return v.get("value") if v.get("type") == "rgb" else None
+    if isinstance(v, (int, float)):
+        return v
+    if isinstance(v, (list, tuple)) and len(v) == 3:
+        return v
+    return None
+
+
+def _bsdf_key(bd, prefix):
+    """mitsuba's key of the differentiable reflectance of a BSDF dictionary: ``reflectance.value`` of a `diffuse` with a constant
+    reflectance, ``brdf_0.reflectance.value`` through `twosided`; None for anything else"""
+    t = bd.get("type") if isinstance(bd, dict) else None
+    if t == "diffuse":
+        return prefix + "reflectance.value" if _constant_rgb(bd.get("reflectance", 0.5)) is not None else None
+    if t == "twosided":
+        inner = [v for k, v in bd.items() if isinstance(v, dict) and k != "type"]
+        if len(inner) == 1 and inner[0].get("type") != "ref":
+            return _bsdf_key(inner[0], prefix + "brdf_0.")
+    return None
+
+
+_GRAD_SHAPE_TYPES = ("rectangle", "cube", "obj", "ply", "sphere", "disk", "cylinder")
+
+
+def _shape_bsdf(sd):
+    """the BSDF dictionary of a shape dictionary (add_shape's rule: any nested plugin that is not an emitter or a sensor)"""
+    bsdf = [v for v in sd.values() if isinstance(v, dict) and str(v.get("type", "")) not in _EMITTER_TYPES
+            and not str(v.get("type", "")).startswith("nlos_") and v.get("type") not in ("perspective", "irradiancemeter")]
+    return bsdf[-1] if bsdf else None
+
+
+def param_locations(d) -> Dict[str, tuple]:
+    """the parameters mtr_render_grad differentiates, from the scene dictionary alone (nothing is flattened), by mitsuba key:
+    (kind, where, value) with kind "material" / "emitter", where ("ref", id) for a top-level BSDF that a shape references,
+    ("shape", name) for a BSDF nested in a shape or the shape's emitter, and the constant colour the dictionary gives"""
+    shapes = {k: v for k, v in d.items() if isinstance(v, dict) and v.get("type") in _GRAD_SHAPE_TYPES}
+    refs = set()
+    out = {}
+    for name, sd in shapes.items():
+        b = _shape_bsdf(sd)
+        if b is not None and b.get("type") == "ref":
+            refs.add(b["id"])
+        elif b is not None:
+            k = _bsdf_key(b, f"{name}.bsdf.")
+            if k is not None:
+                out[k] = ("material", ("shape", name), _bsdf_value(b))
+        em = [v for v in sd.values() if isinstance(v, dict) and v.get("type") in ("area", "angulararea")]
+        if em and _constant_rgb(em[0].get("radiance", 1.0)) is not None:
+            out[f"{name}.emitter.radiance.value"] = ("emitter", ("shape", name), _constant_rgb(em[0].get("radiance", 1.0)))
+    for rid in refs:                               # BSDFs declared at the top level and referenced by id
+        v = d.get(rid)
+        k = _bsdf_key(v, f"{rid}.") if isinstance(v, dict) else None
+        if k is not None:
+            out[k] = ("material", ("ref", rid), _bsdf_value(v))
+    return out
+
+
+def _bsdf_value(bd):
+    if bd.get("type") == "twosided":
+        return _bsdf_value([v for k, v in bd.items() if isinstance(v, dict) and k != "type"][0])
+    return _constant_rgb(bd.get("reflectance", 0.5))
+
+
+def rgb3(v):
+    """a constant colour as three floats"""
+    v = np.asarray(v, dtype=np.float64).reshape(-1)
+    return [float(np.float32(x)) for x in (np.repeat(v, 3) if v.size == 1 else v)]
+
+
+def differentiable_keys(d, b) -> Dict[str, tuple]:
+    """param_locations resolved to the flattened tables: {key: ("material" | "emitter", index)}"""
+    keys = {}
+    for k, (kind, (how, name), _) in param_locations(d).items():
+        if kind == "emitter":
+            if name in b.shape_em:
+                keys[k] = ("emitter", b.shape_em[name])
+        elif how == "ref":
+            if ("ref", name) in b.mat_cache:
+                keys[k] = ("material", b.mat_cache[("ref", name)])
+        elif name in b.shape_mat:
+            keys[k] = ("material", b.shape_mat[name])
+    return keys

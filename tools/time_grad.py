@@ -1,0 +1,68 @@
+"""Time mtr_render_grad (integrator.render_backward) against the primal render of the same Cornell box, the fused and the
+wavefront organisation, on cuda:0.  One JSON line per size:
+
+    python tools/time_grad.py [--sizes 256x256x400x64,512x512x1024x1024] [--reps 3]
+
+Size = width x height x temporal_bins x spp (the second default is BASELINE config 2).  The upstream gradients are random; the
+backward pass differentiates every key of mi.traverse (three albedos, one radiance).  Times are medians of wall-clock time
+around a synchronised call, after one warm-up call."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timed(fn, reps):
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="256x256x400x64,512x512x1024x1024")
+    ap.add_argument("--reps", type=int, default=3)
+    args = ap.parse_args()
+    import torch
+    import mitransient_amd as mitr
+    import mitransient_amd.mi as mi
+    torch.cuda.set_device(0)
+    mi.set_variant("llvm_ad_rgb")
+    for size in args.sizes.split(","):
+        W, H, T, spp = (int(x) for x in size.split("x"))
+        d = mitr.cornell_box()
+        d["sensor"]["film"].update(width=W, height=H, temporal_bins=T, start_opl=3.5, bin_width_opl=6.0 / T)
+        scene = mi.load_dict(d)
+        integ = scene.integrator()
+        g = torch.Generator(device="cuda").manual_seed(0)
+        g_s = torch.randn((H, W, 3), device="cuda", generator=g)
+        g_t = torch.randn((H, W, T, 3), device="cuda", generator=g)
+        p = mi.traverse(scene)
+        for k in scene.grad_keys():
+            p[k] = torch.tensor(p[k], requires_grad=True)
+        res = {"size": size}
+        for mode in ("fused", "wavefront"):
+            integ.amd_mode = mode
+            res[f"primal_{mode}_ms"] = timed(lambda: integ.render(scene, spp=spp, seed=0), args.reps)
+        integ.amd_mode = "auto"
+        res["grad_ms"] = timed(lambda: integ.render_backward(scene, p, grad_in=(g_s, g_t), seed=1, spp=spp), args.reps)
+        res["ratio_vs_fused"] = res["grad_ms"] / res["primal_fused_ms"]
+        res["ratio_vs_wavefront"] = res["grad_ms"] / res["primal_wavefront_ms"]
+        print(json.dumps(res), flush=True)
+        del g_t
+
+
+if __name__ == "__main__":
+    main()
