@@ -34,9 +34,9 @@ struct mtr_ctx {
     uint32_t fused_launches = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev2 = nullptr, ev3 = nullptr;               // mtr_splat_add: the partitioned passes, timed apart from the first pass (the workspace allocation in between is host time)
-    float *d_freq = nullptr; uint32_t freq_cap = 0;      // phasor film frequencies of a ctx-level call (mtr_splat_add)
+    float *d_freq = nullptr; size_t freq_cap = 0;        // phasor film frequencies of a ctx-level call (mtr_splat_add); capacities in bytes (grow_device_buffer)
     void *d_runs = nullptr; size_t runs_cap = 0;         // mtr_splat_add variant 1: sortedness flag + run table
-    uint32_t *d_band_count = nullptr; uint32_t band_cap = 0;     // mtr_render_params.n_bands: flushed pixels per band of the launch in flight
+    uint32_t *d_band_count = nullptr; size_t band_cap = 0;       // mtr_render_params.n_bands: flushed pixels per band of the launch in flight
     void *d_part = nullptr; size_t part_cap = 0;         // ... and the partition workspace of unsorted input (at most 256 MiB of it kept between calls, until mtr_ctx_trim / destroy)
 };
 
@@ -46,6 +46,12 @@ struct WfWorkspace {            // MTR_MODE_WAVEFRONT buffers, sized for one til
     bool polar = false;                  // `planes` also holds the polarized planes (wf_polar_planes_bytes) behind the ordinary ones
     uint32_t *host_count = nullptr;       // pinned: live counts read back between bounce chunks (two words, alternating)
     hipEvent_t poll_ev[2] = { nullptr, nullptr };     // ... and the events that say a word has landed
+    void release()              // the tile's device buffers; the sizes are valid only while every one of them exists
+    {
+        n_slots = 0; P = 0; rec_cap = 0; rows = 0; polar = false;
+        for (void **p : { &planes, &q_live, &q_ray, &q_mat, &q_shadow, &r_shadow, &occ, &counts, &rec, &rec_count, &q_zombie })
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+    }
 };
 
 struct NlosDev {                // NLOS tier: device tables + constants (mtr_scene_set_nlos)
@@ -121,10 +127,7 @@ int mtr_ctx_create(int device_ordinal, mtr_ctx **out)
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     HIP_TRY(nullptr, hipMalloc((void **)&c->d_counters, sizeof(DevCounters)));
     HIP_TRY(nullptr, hipMalloc((void **)&c->d_ticket, 32 * sizeof(uint32_t)));
-    HIP_TRY(nullptr, hipEventCreate(&c->ev0));
-    HIP_TRY(nullptr, hipEventCreate(&c->ev1));
-    HIP_TRY(nullptr, hipEventCreate(&c->ev2));
-    HIP_TRY(nullptr, hipEventCreate(&c->ev3));
+    for (hipEvent_t *e : { &c->ev0, &c->ev1, &c->ev2, &c->ev3 }) HIP_TRY(nullptr, hipEventCreate(e));
     *out = c;
     return MTR_OK;
 }
@@ -133,16 +136,8 @@ void mtr_ctx_destroy(mtr_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->d_counters) (void)hipFree(c->d_counters);
-    if (c->d_ticket) (void)hipFree(c->d_ticket);
-    if (c->d_freq) (void)hipFree(c->d_freq);
-    if (c->d_runs) (void)hipFree(c->d_runs);
-    if (c->d_part) (void)hipFree(c->d_part);
-    if (c->d_band_count) (void)hipFree(c->d_band_count);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->ev2) (void)hipEventDestroy(c->ev2);
-    if (c->ev3) (void)hipEventDestroy(c->ev3);
+    for (void *p : { (void *)c->d_counters, (void *)c->d_ticket, (void *)c->d_freq, c->d_runs, c->d_part, (void *)c->d_band_count }) if (p) (void)hipFree(p);
+    for (hipEvent_t e : { c->ev0, c->ev1, c->ev2, c->ev3 }) if (e) (void)hipEventDestroy(e);
     delete c;
 }
 
@@ -211,12 +206,10 @@ int mtr_scene_create(mtr_ctx *c, const mtr_scene_desc *d, mtr_scene **out)
 #define UP(vec, field)                                                       \
     do { rc = upload(s, vec, &s->dev.field); if (rc) { mtr_scene_destroy(s); return rc; } } while (0)
     UP(hs.nodes, nodes); UP(hs.tpairs, tpairs); UP(hs.tshade, tshade); UP(hs.mats, mats); UP(hs.ems, ems);
-    s->dev.samp_tris = nullptr; s->dev.samp_vn = nullptr; s->dev.face_pmf = s->dev.face_cdf = nullptr; s->dev.vnormals = nullptr; s->dev.texels = s->dev.tex_info = s->dev.uvs = nullptr;
-    s->dev.wnodes = nullptr; s->dev.n_wnodes = (uint32_t)hs.wnodes.size();
+    // (optional tables stay null: `dev` starts zeroed)
+    s->dev.n_wnodes = (uint32_t)hs.wnodes.size(); s->dev.n_wnodes4 = (uint32_t)hs.wnodes4.size(); s->dev.n_wnodes8q = (uint32_t)hs.wnodes8q.size();
     if (hs.has_wide) UP(hs.wnodes, wnodes);
-    s->dev.wnodes4 = nullptr; s->dev.n_wnodes4 = (uint32_t)hs.wnodes4.size();
     UP(hs.wnodes4, wnodes4);
-    s->dev.wnodes8q = nullptr; s->dev.n_wnodes8q = (uint32_t)hs.wnodes8q.size();
     if (!hs.wnodes8q.empty()) UP(hs.wnodes8q, wnodes8q);
     if (!hs.samp_tris.empty()) { UP(hs.samp_tris, samp_tris); UP(hs.face_pmf, face_pmf); UP(hs.face_cdf, face_cdf); }
     if (!hs.samp_vn.empty()) UP(hs.samp_vn, samp_vn);
@@ -225,77 +218,9 @@ int mtr_scene_create(mtr_ctx *c, const mtr_scene_desc *d, mtr_scene **out)
 #undef UP
     s->dev.n_nodes = (uint32_t)hs.nodes.size(); s->dev.n_slots = (uint32_t)hs.tshade.size();
     s->dev.n_mats = d->n_materials; s->dev.n_ems = d->n_emitters;
-    s->polar_ok = hs.texels.empty();
-    for (uint32_t i = 0; i < d->n_materials; ++i) if (!polar_bsdf_supported(d->materials[i].type)) s->polar_ok = false;
-    for (uint32_t i = 0; i < d->n_emitters; ++i) if (hs.ems[i].angular) s->polar_ok = false;
-    s->dev.has_rough = 0u;
-    for (uint32_t i = 0; i < d->n_materials; ++i)
-        if (bsdf_is_rough(d->materials[i].type) || d->materials[i].type == MTR_BSDF_THINDIELECTRIC) s->dev.has_rough = 1u;
-    if (!hs.vnormals.empty() || !hs.texels.empty()) s->dev.has_rough = 1u;      // smooth-shaded triangles, bitmap textures: the extended shading code as well
-    // scene traits (mtr_core.h): facts about the tables that let the kernels drop shading code no hit can reach
-    s->dev.traits = 0u;
-    if (!s->dev.has_rough) {
-        bool diffuse_only = d->n_materials > 0;
-        for (uint32_t i = 0; i < d->n_materials; ++i)
-            if (d->materials[i].type != MTR_BSDF_DIFFUSE || (d->materials[i].flags & MTR_MAT_TWOSIDED)) diffuse_only = false;
-        if (diffuse_only) s->dev.traits |= kTrDiffuse;
-        if (d->n_emitters == 1 && !hs.ems[0].is_mesh && !hs.ems[0].angular) s->dev.traits |= kTrOneRectEmitter;     // (its kernels have no falloff code)
-        bool leaf_pairs = hs.has_wide;
-        for (const WNode &n : hs.wnodes)
-            for (uint32_t k = 0; k < n.count; ++k) {
-                const uint32_t code = ~(uint32_t)n.ref[k];
-                if (n.ref[k] < 0 && !(code & kLeafQuadBit) && (code & 3u) + 1u > 2u) leaf_pairs = false;
-            }
-        if (leaf_pairs) s->dev.traits |= kTrLeafPair;
-    }
-    if (s->dev.has_rough) {          // kTrNoLobes: the extended shading code is needed for normals / bitmaps only
-        bool lobes = false;
-        for (uint32_t i = 0; i < d->n_materials; ++i)
-            if (bsdf_is_rough(d->materials[i].type) || d->materials[i].type == MTR_BSDF_THINDIELECTRIC) lobes = true;
-        if (!lobes) s->dev.traits |= kTrNoLobes;
-    }
-    {   // kTrGrey (the scene's part; mtr_scene_set_nlos adds the laser's): three equal channels in every colour, no bitmap
-        auto eq3 = [](const float *v) { return memcmp(v, v + 1, sizeof(float)) == 0 && memcmp(v, v + 2, sizeof(float)) == 0; };
-        bool grey = hs.texels.empty();
-        for (uint32_t i = 0; grey && i < d->n_materials; ++i) {
-            const mtr_material &m = d->materials[i];
-            const bool aniso = (m.flags & MTR_MAT_ANISOTROPIC) != 0u;
-            grey = m.albedo_texture == 0u && eq3(m.a) && eq3(m.c) &&
-                   ((aniso && m.type == MTR_BSDF_ROUGHDIELECTRIC) || eq3(m.b)) && ((aniso && m.type == MTR_BSDF_ROUGHCONDUCTOR) || eq3(m.c2));
-        }
-        for (uint32_t i = 0; grey && i < d->n_emitters; ++i) grey = eq3(d->emitters[i].radiance);
-        s->grey_scene = grey;
-        if (grey) s->dev.traits |= kTrGrey;
-    }
-    // kTrFlatTop (any materials): the root's children are rectangles and box nodes, the boxes' nodes follow the root in order
-    memset(&s->dev.flat, 0, sizeof s->dev.flat);
-    if (hs.has_wide && !hs.wnodes.empty() && hs.wide_levels <= 2 && !mtr::knob("MTR_NO_FLAT")) {
-        const WNode &root = hs.wnodes[0];
-        bool flat = root.flags == 0u && root.count >= 1u;
-        uint32_t n_inner = 0u, prim_mask = 0u;
-        for (uint32_t k = 0; flat && k < root.count; ++k) {
-            const int32_t ref = root.ref[k];
-            if (k < root.n_quads) { flat = ref < 0 && ((~(uint32_t)ref) & kLeafQuadBit) != 0u; prim_mask |= 1u << k; }
-            else if (ref < 0) { flat = ((~(uint32_t)ref) & kLeafQuadBit) == 0u; prim_mask |= 1u << k; }             // a triangle leaf
-            else {            // an inner child: a box node, and the n-th of them is node n + 1
-                flat = ref == (int32_t)(1u + n_inner) && (size_t)ref < hs.wnodes.size() && hs.wnodes[ref].flags == 3u && hs.wnodes[ref].count == 6u;
-                ++n_inner;
-            }
-        }
-        flat = flat && n_inner <= kFlatMaxBoxes;
-        if (flat) {
-            FlatTop &ft = s->dev.flat;
-            ft.n_quads = root.n_quads; ft.n_boxes = n_inner; ft.node0 = 1u; ft.prim_mask = prim_mask;
-            for (uint32_t b = 0; b < ft.n_boxes; ++b) {
-                const float *x = hs.wnodes[1u + b].xf;
-                memcpy(ft.xf[b], x, 12 * sizeof(float));
-                for (int k = 0; k < 3; ++k) ft.xf[b][12 + k] = (fabsf(x[4 * k]) + fabsf(x[4 * k + 1]) + fabsf(x[4 * k + 2])) * 1.000001f;      // S: row sums of |R| (rounded up)
-                ft.xf[b][15] = 0.0f;
-            }
-            s->dev.traits |= kTrFlatTop;
-            if (prim_mask >> root.n_quads) s->dev.traits |= kTrFlatLeaves;
-        }
-    }
+    // what the kernels are chosen by: decided over the host tables (mtr_scene_host.cpp classify_scene)
+    s->polar_ok = hs.polar_ok; s->grey_scene = hs.grey_scene;
+    s->dev.has_rough = hs.needs_ext ? 1u : 0u; s->dev.traits = hs.traits; s->dev.flat = hs.flat;
     s->dev.bvh_depth = hs.bvh_depth; s->n_leaves = hs.n_leaves;
     s->dev.wide_levels = hs.wide_levels; s->dev.wide4_levels = hs.wide4_levels; s->dev.wide8q_levels = hs.wide8q_levels;
     s->tri_verts.assign(d->tri_verts, d->tri_verts + 9 * (size_t)d->n_tris);
@@ -355,9 +280,7 @@ int mtr_scene_set_nlos(mtr_scene *s, const mtr_nlos_desc *n)
     D.k.hg_tris = (const q4 *)D.hg_tris; D.k.hg_vn = (const q4 *)D.hg_vn; D.k.targets = (const q4 *)D.targets;
     HIP_TRY(c, launch_nlos_prepare(s->dev, D.k, (q4 *)D.targets, c->stream));    // scanned points + laser axis hit
     D.on = true;
-    // kTrGrey: ... and the laser's irradiance
-    const bool laser_grey = memcmp(n->laser_irradiance, n->laser_irradiance + 1, sizeof(float)) == 0 && memcmp(n->laser_irradiance, n->laser_irradiance + 2, sizeof(float)) == 0;
-    if (s->grey_scene && laser_grey) s->dev.traits |= kTrGrey; else s->dev.traits &= ~kTrGrey;
+    s->dev.traits = traits_with_laser(s->dev.traits, s->grey_scene, n->laser_irradiance);
     return MTR_OK;
 }
 
@@ -366,8 +289,7 @@ void mtr_scene_destroy(mtr_scene *s)
     if (!s) return;
     if (s->ctx) (void)hipSetDevice(s->ctx->device);
     for (void *p : s->allocs) (void)hipFree(p);
-    void *w[] = { s->wf.planes, s->wf.q_live, s->wf.q_ray, s->wf.q_mat, s->wf.q_shadow, s->wf.r_shadow, s->wf.occ, s->wf.counts, s->wf.rec, s->wf.rec_count, s->wf.q_zombie };
-    for (void *p : w) if (p) (void)hipFree(p);
+    s->wf.release();
     if (s->wf.host_count) (void)hipHostFree(s->wf.host_count);
     for (hipEvent_t e : s->wf.poll_ev) if (e) (void)hipEventDestroy(e);
     void *nl[] = { s->nlos.shapes, s->nlos.tables, s->nlos.hg_tris, s->nlos.hg_vn, s->nlos.targets, s->d_freq };
@@ -429,16 +351,8 @@ int mtr_scene_set_colors(mtr_scene *s, const float *material_a, const float *emi
     for (size_t i = 0; i < ems.size(); ++i) for (int k = 0; k < 3; ++k) ems[i].radiance[k] = emitter_radiance[3 * i + k];
     if (!mats.empty()) HIP_TRY(c, hipMemcpy((void *)s->dev.mats, mats.data(), mats.size() * sizeof(mtr_material), hipMemcpyHostToDevice));
     if (!ems.empty()) HIP_TRY(c, hipMemcpy((void *)s->dev.ems, ems.data(), ems.size() * sizeof(Emitter), hipMemcpyHostToDevice));
-    // kTrGrey is the only trait that depends on colours (mtr_scene_create): decided again over the new tables
-    auto eq3 = [](const float *v) { return memcmp(v, v + 1, sizeof(float)) == 0 && memcmp(v, v + 2, sizeof(float)) == 0; };
-    bool grey = s->dev.texels == nullptr;
-    for (size_t i = 0; grey && i < mats.size(); ++i) {
-        const mtr_material &m = mats[i];
-        const bool aniso = (m.flags & MTR_MAT_ANISOTROPIC) != 0u;
-        grey = m.albedo_texture == 0u && eq3(m.a) && eq3(m.c) &&
-               ((aniso && m.type == MTR_BSDF_ROUGHDIELECTRIC) || eq3(m.b)) && ((aniso && m.type == MTR_BSDF_ROUGHCONDUCTOR) || eq3(m.c2));
-    }
-    for (size_t i = 0; grey && i < ems.size(); ++i) grey = eq3(ems[i].radiance);
+    // kTrGrey is the only trait that depends on colours: decided again over the new tables
+    const bool grey = colours_are_grey(mats.data(), (uint32_t)mats.size(), ems.data(), (uint32_t)ems.size(), s->dev.texels != nullptr);
     s->grey_scene = grey;
     s->dev.traits = grey ? (s->dev.traits | kTrGrey) : (s->dev.traits & ~kTrGrey);
     return MTR_OK;
@@ -462,10 +376,7 @@ static int wf_alloc(mtr_scene *s, uint32_t n_slots, uint32_t P, uint32_t n_seg, 
     mtr_ctx *c = s->ctx;
     WfWorkspace &w = s->wf;
     if (w.n_slots >= n_slots && w.P >= P && w.rec_cap == rec_cap && w.rows >= n_seg && w.planes && (w.polar || !polar)) return MTR_OK;
-    void **ptrs[] = { &w.planes, &w.q_live, &w.q_ray, &w.q_mat, &w.q_shadow, &w.r_shadow, &w.occ, &w.counts, &w.rec, &w.rec_count, &w.q_zombie };
-    w.n_slots = 0; w.P = 0; w.rec_cap = 0; w.rows = 0;          // sizes are valid only once every buffer below exists
-    for (void **p : ptrs) if (*p) { (void)hipFree(*p); *p = nullptr; }
-    w.polar = false;
+    w.release();
     HIP_TRY(c, hipMalloc(&w.planes, wf_planes_bytes(n_slots) + (polar ? wf_polar_planes_bytes(n_slots) : 0)));
     HIP_TRY(c, hipMalloc(&w.q_live, (size_t)2 * n_slots * 4));
     HIP_TRY(c, hipMalloc(&w.q_ray, (size_t)2 * n_slots * 32));                       // rays of the live lists, in list order
@@ -483,9 +394,39 @@ static int wf_alloc(mtr_scene *s, uint32_t n_slots, uint32_t P, uint32_t n_seg, 
     return MTR_OK;
 }
 
-static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float *s4, const RenderConst &rc,
-                     float *trace_ms, float *scatter_ms, uint32_t *n_trace, uint32_t *n_scatter, bool timed, uint32_t *n_trace_kernel,
-                     bool may_block, float *shade_ms)
+// launches and (timed renders) kernel times of one render, as mtr_kernel_times reports them
+struct RenderStats {
+    uint32_t launches = 0, scatter_launches = 0, trace_kernel_launches = 0;
+    float trace_ms = 0.0f, shade_ms = 0.0f, scatter_ms = 0.0f;          // k_wf_trace, k_wf_shade, the scatter-add
+};
+// the timing events of one class of launches: a pair per launch, destroyed with the holder whichever way the render returns
+struct EventPairs {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+    EventPairs() = default;
+    EventPairs(const EventPairs &) = delete;           // (the holder owns its events)
+    ~EventPairs() { for (auto &pr : ev) { if (pr.first) (void)hipEventDestroy(pr.first); if (pr.second) (void)hipEventDestroy(pr.second); } }
+    hipError_t record_begin(hipStream_t stream)
+    {
+        ev.push_back({ nullptr, nullptr });
+        hipError_t e = hipEventCreate(&ev.back().first);
+        if (e == hipSuccess) e = hipEventCreate(&ev.back().second);
+        return e == hipSuccess ? hipEventRecord(ev.back().first, stream) : e;
+    }
+    hipError_t record_end(hipStream_t stream) { return hipEventRecord(ev.back().second, stream); }
+    hipError_t sum_ms(float *out) const         // (once the stream has drained)
+    {
+        *out = 0.0f;
+        for (auto &pr : ev) {
+            float ms = 0.0f;
+            if (hipError_t e = hipEventElapsedTime(&ms, pr.first, pr.second)) return e;
+            *out += ms;
+        }
+        return hipSuccess;
+    }
+};
+
+static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float *s4, const RenderConst &rc, bool timed, bool may_block,
+                     RenderStats *st)
 {
     mtr_ctx *c = s->ctx;
     const Film &f = s->film;
@@ -578,22 +519,15 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
     const bool unbounded = p->max_depth < 0 || s->nlos.on || (p->max_depth > 16 && may_block);
     // the reference loop always runs its first iteration (emission of the camera-ray hit), also at max_depth 0
     const uint32_t max_depth = p->max_depth < 0 ? 0xffffffffu : (p->max_depth == 0 ? 1u : (uint32_t)p->max_depth + (s->nlos.on ? 2u : 0u));
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> scatter_ev, trace_ev, shade_ev;
-    // (timed renders only) events around every k_wf_trace launch — the dominant kernel of scenes in HBM is timed alone — and
-    // around the HBM-bound k_wf_shade (mtr_kernel_times.wf_shade_ms)
-    auto launch_timed = [&](int which, int grid_, std::vector<std::pair<hipEvent_t, hipEvent_t>> &bucket) -> hipError_t {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (timed) {
-            hipError_t e = hipEventCreate(&e0); if (e != hipSuccess) return e;
-            e = hipEventCreate(&e1); if (e != hipSuccess) return e;
-            e = hipEventRecord(e0, c->stream); if (e != hipSuccess) return e;
-        }
-        hipError_t e = launch_wf(a, cfg, which, grid_, c->stream);
-        if (e != hipSuccess) return e;
-        if (timed) { e = hipEventRecord(e1, c->stream); if (e != hipSuccess) return e; bucket.push_back({ e0, e1 }); }
-        return hipSuccess;
+    EventPairs scatter_ev, trace_ev, shade_ev;
+    // (timed renders only) events around every k_wf_trace launch — the dominant kernel of scenes in HBM is timed alone — around
+    // the HBM-bound k_wf_shade (mtr_kernel_times.wf_shade_ms) and around the scatter-add
+    auto launch_timed = [&](WfKernel which, int grid_, EventPairs &bucket) -> hipError_t {
+        hipError_t e = timed ? bucket.record_begin(c->stream) : hipSuccess;
+        if (e == hipSuccess) e = launch_wf(a, cfg, which, grid_, c->stream);
+        if (e == hipSuccess && timed) e = bucket.record_end(c->stream);
+        return e;
     };
-    auto trace_timed = [&](int which, int grid_) -> hipError_t { return launch_timed(which, grid_, trace_ev); };
 
     for (uint32_t s0 = 0; s0 < spp_chunk; s0 += S) {
         const uint32_t Scur = std::min(S, spp_chunk - s0);
@@ -619,7 +553,7 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
             a.parity = 0;
             a.ticket = c->d_ticket + 16; a.ticket_cur = 0u;                          // segment tickets (k_wf_trace / shadow_gen / shade)
             HIP_TRY(c, hipMemsetAsync(a.ticket, 0, 2 * sizeof(uint32_t), c->stream));
-            HIP_TRY(c, launch_wf(a, cfg, 0, grid_gen, c->stream));                   // raygen (writes live list 0)
+            HIP_TRY(c, launch_wf(a, cfg, WfKernel::Raygen, grid_gen, c->stream));    // (writes live list 0)
             HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)a.seg_list_n, (int)a.n_seg, 1, c->stream));     // bounce 0 walks every segment
             uint32_t depth = 0;
             // "Anyone left?" WITHOUT draining the stream (round 5).  Every 8 bounces the live count is copied to a pinned word and an
@@ -629,7 +563,7 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
             // 1-4 synchronised the stream here, a bubble per chunk and a stall for a caller overlapping bands with collectives.
             uint32_t n_polls = 0;
             // (the count a poll reads is the one the PREVIOUS chunk of 8 bounces left: an unbounded render issues 8 - 16 bounce launches
-            // over empty segment lists after its last path has died — about 4 us each; n_trace / trace_launches and the kernel times of
+            // over empty segment lists after its last path has died — about 4 us each; trace_launches and the kernel times of
             // mtr_kernel_times include that speculative tail)
             auto poll_live = [&](bool &done) -> int {
                 const uint32_t cur = n_polls & 1u;
@@ -647,8 +581,8 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
                 HIP_TRY(c, hipMemsetAsync(a.seg_list_n + (a.parity ^ 1u), 0, 4, c->stream));     // the list this bounce's survivors build
                 if (a.nlos_on || polar) {       // NLOS tier / polarized transport: the whole loop iteration in one launch per bounce
                     if (polar) a.first_bounce = depth == 0u ? 1u : 0u;            // (bounce 0 builds its paths: polar_begin)
-                    HIP_TRY(c, launch_wf(a, cfg, polar ? 6 : 5, grid, c->stream)); a.ticket_cur ^= 1u;
-                    *n_trace += 1;
+                    HIP_TRY(c, launch_wf(a, cfg, polar ? WfKernel::PolarBounce : WfKernel::NlosBounce, grid, c->stream)); a.ticket_cur ^= 1u;
+                    st->launches += 1;
                     a.parity ^= 1u;
                     ++depth;
                     if (unbounded && (depth & 7u) == 0) { bool done = false; if (int r = poll_live(done)) return r; if (done) break; }
@@ -656,58 +590,43 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
                 }
                 a.trace_any = 0u;
                 a.first_bounce = depth == 0u ? 1u : 0u;
-                HIP_TRY(c, trace_timed(1, grid)); a.ticket_cur ^= 1u;                // closest hit + material lists
+                HIP_TRY(c, launch_timed(WfKernel::Trace, grid, trace_ev)); a.ticket_cur ^= 1u;       // closest hit + material lists
                 // shade: commits the emitter-sampling terms the previous bounce parked, runs the loop iteration once, writes the
                 // shadow rays (scene in HBM) or traces them inline (scene in LDS), compacts the survivors
-                HIP_TRY(c, launch_timed(2, grid, shade_ev)); a.ticket_cur ^= 1u;
-                *n_trace += 2;
+                HIP_TRY(c, launch_timed(WfKernel::Shade, grid, shade_ev)); a.ticket_cur ^= 1u;
+                st->launches += 2;
                 if (!cfg.scene_lds) {                                                // scene in HBM/L2: the shadow rays get their own persistent trace
                     a.trace_any = 1u;
-                    HIP_TRY(c, trace_timed(1, grid)); a.ticket_cur ^= 1u;            // occlusion of this bounce's shadow rays: read by the NEXT shade
-                    *n_trace += 1;
+                    HIP_TRY(c, launch_timed(WfKernel::Trace, grid, trace_ev)); a.ticket_cur ^= 1u;       // occlusion of this bounce's shadow rays: read by the NEXT shade
+                    st->launches += 1;
                 }
                 a.parity ^= 1u;
                 ++depth;
                 if (unbounded && (depth & 7u) == 0) { bool done = false; if (int r = poll_live(done)) return r; if (done) break; }      // every 8 bounces: anyone left?
             }
-            hipEvent_t a0 = nullptr, a1 = nullptr;
-            if (timed) {
-                HIP_TRY(c, hipEventCreate(&a0)); HIP_TRY(c, hipEventCreate(&a1));
-                HIP_TRY(c, hipEventRecord(a0, c->stream));
-            }
-            HIP_TRY(c, launch_wf(a, cfg, polar ? 7 : 3, (int)std::min<uint32_t>(Pcur, (uint32_t)grid_full), c->stream));
-            if (timed) { HIP_TRY(c, hipEventRecord(a1, c->stream)); scatter_ev.push_back({ a0, a1 }); }
-            *n_scatter += 1;
+            HIP_TRY(c, launch_timed(polar ? WfKernel::PolarScatter : WfKernel::Scatter, (int)std::min<uint32_t>(Pcur, (uint32_t)grid_full), scatter_ev));
+            st->scatter_launches += 1;
         }
     }
-    float acc_scatter = 0.0f;
     if (timed) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (auto &pr : scatter_ev) {
-            float ms = 0.0f;
-            HIP_TRY(c, hipEventElapsedTime(&ms, pr.first, pr.second));
-            acc_scatter += ms;
-            (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second);
-        }
+        HIP_TRY(c, scatter_ev.sum_ms(&st->scatter_ms));
+        HIP_TRY(c, trace_ev.sum_ms(&st->trace_ms));
+        HIP_TRY(c, shade_ev.sum_ms(&st->shade_ms));
     }
-    float acc_trace = 0.0f;
-    for (auto &pr : trace_ev) {
-        float ms = 0.0f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, pr.first, pr.second));
-        acc_trace += ms;
-        (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second);
-    }
-    float acc_shade = 0.0f;
-    for (auto &pr : shade_ev) {
-        float ms = 0.0f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, pr.first, pr.second));
-        acc_shade += ms;
-        (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second);
-    }
-    *scatter_ms = acc_scatter; *trace_ms = acc_trace; *n_trace_kernel = (uint32_t)trace_ev.size(); *shade_ms = acc_shade;
+    st->trace_kernel_launches = (uint32_t)trace_ev.ev.size();
     return MTR_OK;
 }
 
+// fused_plan's verdict on a render: does a configuration fit, and does it keep the scene / the time-bin rows in LDS
+struct FusedProbe { bool scene_lds, hist_lds; };
+static FusedProbe fused_probe(mtr_scene *s, const mtr_render_params *p, uint32_t n_pixels, uint32_t spp_chunk)
+{
+    FusedArgs probe{}; FusedConfig pc{};
+    probe.sc = s->dev; probe.cam = s->cam; probe.film = s->film; probe.rc = make_render_const(*p, s->film, s->dev.n_ems); probe.nlos_on = s->nlos.on ? 1u : 0u;
+    const bool fits = fused_plan(s->dev, s->film, n_pixels, spp_chunk, usable_cus(s->ctx, p), probe, pc);
+    return { fits && pc.scene_lds, fits && pc.hist_lds };
+}
 // MTR_MODE_AUTO -> the organisation that runs: the fused kernel when the whole scene can be staged in LDS (measured 143 vs
 // 168 ms on config 2), the wavefront pipeline otherwise (BVH in HBM/L2: 21 vs 66 ms on an 81k-triangle scene)
 static int resolve_mode(mtr_scene *s, const mtr_render_params *p, uint32_t n_pixels, uint32_t spp_chunk, uint32_t *mode_io,
@@ -741,10 +660,11 @@ static int resolve_mode(mtr_scene *s, const mtr_render_params *p, uint32_t n_pix
             return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: rough BSDFs / smooth-shaded triangles with a phasor film or deterministic rows need the wavefront mode");
         if (mode == MTR_MODE_AUTO && !fused_ok) mode = MTR_MODE_WAVEFRONT;
     }
+    // (planned once, and only where the answer depends on it)
+    const bool want_rows = developed_ok && !f.n_freq && (mode == MTR_MODE_AUTO || mode == MTR_MODE_FUSED);
+    const FusedProbe probe = (mode == MTR_MODE_AUTO || want_rows) ? fused_probe(s, p, n_pixels, spp_chunk) : FusedProbe{ false, false };
     if (mode == MTR_MODE_AUTO) {
-        FusedArgs probe{}; FusedConfig pc{};
-        probe.sc = s->dev; probe.cam = s->cam; probe.film = f; probe.rc = make_render_const(*p, f, s->dev.n_ems); probe.nlos_on = s->nlos.on ? 1u : 0u;
-        const bool fits = fused_plan(s->dev, f, n_pixels, spp_chunk, usable_cus(c, p), probe, pc) && pc.scene_lds;
+        const bool fits = probe.scene_lds;
         // ... and only a SHALLOW tree (a room of rectangles and a few objects: root + object nodes).  k_fused walks in lock-step — every
         // traversal costs its wave the longest walk of 64 lanes — which a deeper tree punishes at once: the Cornell box with its boxes
         // tessellated 2 x 2 per face (108 triangles, 3 levels) renders in 204 ms fused against 125 ms in the wavefront organisation,
@@ -753,14 +673,44 @@ static int resolve_mode(mtr_scene *s, const mtr_render_params *p, uint32_t n_pix
         mode = (fits && shallow) ? MTR_MODE_FUSED : MTR_MODE_WAVEFRONT;
     }
     *mode_io = mode;
-    if (developed_ok) {          // MTR_FLAG_DEVELOPED_ROWS: the fused kernel's row flush, rows in LDS, time bins (not a phasor film)
-        *developed_ok = 0u;
-        if (mode == MTR_MODE_FUSED && !f.n_freq) {
-            FusedArgs probe{}; FusedConfig pc{};
-            probe.sc = s->dev; probe.cam = s->cam; probe.film = f; probe.rc = make_render_const(*p, f, s->dev.n_ems); probe.nlos_on = s->nlos.on ? 1u : 0u;
-            if (fused_plan(s->dev, f, n_pixels, spp_chunk, usable_cus(c, p), probe, pc) && pc.hist_lds) *developed_ok = 1u;
-        }
-    }
+    // MTR_FLAG_DEVELOPED_ROWS: the fused kernel's row flush, rows in LDS, time bins (not a phasor film)
+    if (developed_ok) *developed_ok = (mode == MTR_MODE_FUSED && want_rows && probe.hist_lds) ? 1u : 0u;
+    return MTR_OK;
+}
+
+// the ranges of mtr_render_params that every render entry point checks; `who` prefixes the message, `advice` ends the lane-count one
+static int check_render_ranges(mtr_ctx *c, const Film &f, const mtr_render_params *p, const char *who, const char *advice)
+{
+    const std::string pre = std::string(who) + ": ";
+    const uint64_t npix_crop = (uint64_t)f.crop_w * f.crop_h;
+    if (p->spp_total == 0 || p->spp_begin > p->spp_end || p->spp_end > p->spp_total)
+        return fail(c, MTR_ERR_INVALID, pre + "bad sample range");
+    if (p->pixel_begin > p->pixel_end || p->pixel_end > npix_crop)
+        return fail(c, MTR_ERR_INVALID, pre + "bad pixel range");
+    if (npix_crop * p->spp_total > (1ull << 32))
+        return fail(c, MTR_ERR_UNSUPPORTED, pre + "W*H*spp exceeds 2^32 lanes (common.py:51); " + advice);
+    if (p->max_depth < -1 || p->rr_depth <= 0) return fail(c, MTR_ERR_INVALID, pre + "bad max_depth / rr_depth");
+    return MTR_OK;
+}
+static int counters_to_abi(mtr_ctx *c, mtr_counters *out)
+{
+    DevCounters h;
+    HIP_TRY(c, hipMemcpy(&h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
+    memset(out, 0, sizeof *out);
+    out->paths = h.paths; out->rays_closest = h.rays_closest; out->rays_shadow = h.rays_shadow;
+    out->splats_issued = h.splats_issued; out->bounces = h.bounces; out->splats_overflow = h.splats_overflow;
+    out->reserved[0] = h.r0; out->reserved[1] = h.r1;
+    return MTR_OK;
+}
+// a context-owned device buffer of at least `need` bytes (a launch in flight may read the old one: the stream drains first)
+static int grow_device_buffer(mtr_ctx *c, void **ptr, size_t *cap, size_t need)
+{
+    if (*cap >= need) return MTR_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (*ptr) (void)hipFree(*ptr);
+    *ptr = nullptr; *cap = 0;
+    HIP_TRY(c, hipMalloc(ptr, need));
+    *cap = need;
     return MTR_OK;
 }
 
@@ -784,14 +734,7 @@ int mtr_render(mtr_scene *s, const mtr_render_params *p, float *t4, float *s4,
     if (!s || !p || !t4 || !s4) return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_render: NULL argument");
     mtr_ctx *c = s->ctx;
     const Film &f = s->film;
-    const uint64_t npix_crop = (uint64_t)f.crop_w * f.crop_h;
-    if (p->spp_total == 0 || p->spp_begin > p->spp_end || p->spp_end > p->spp_total)
-        return fail(c, MTR_ERR_INVALID, "mtr_render: bad sample range");
-    if (p->pixel_begin > p->pixel_end || p->pixel_end > npix_crop)
-        return fail(c, MTR_ERR_INVALID, "mtr_render: bad pixel range");
-    if (npix_crop * p->spp_total > (1ull << 32))
-        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: W*H*spp exceeds 2^32 lanes (common.py:51); shard the render");
-    if (p->max_depth < -1 || p->rr_depth <= 0) return fail(c, MTR_ERR_INVALID, "mtr_render: bad max_depth / rr_depth");
+    if (int r = check_render_ranges(c, f, p, "mtr_render", "shard the render")) return r;
     if (p->mode > MTR_MODE_WAVEFRONT) return fail(c, MTR_ERR_INVALID, "mtr_render: unknown mode");
     HIP_TRY(c, hipSetDevice(c->device));
 
@@ -815,8 +758,7 @@ int mtr_render(mtr_scene *s, const mtr_render_params *p, float *t4, float *s4,
     if (!(p->flags & MTR_FLAG_KEEP_COUNTERS)) HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, sizeof(DevCounters), c->stream));
     if (s->log.count) HIP_TRY(c, hipMemsetAsync(s->log.count, 0, sizeof(unsigned long long), c->stream));
     if (times_out) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    uint32_t launches = 0, scatter_launches = 0, wf_trace_n = 0;
-    float scatter_ms = 0.0f, wf_trace_ms = 0.0f, wf_shade_ms = 0.0f;
+    RenderStats st;
     if (n_pixels && a.spp_chunk) {
         uint32_t mode = p->mode, dev_ok = 0u;
         if (int r = resolve_mode(s, p, n_pixels, a.spp_chunk, &mode, &dev_ok)) return r;
@@ -825,8 +767,7 @@ int mtr_render(mtr_scene *s, const mtr_render_params *p, float *t4, float *s4,
         if (p->n_bands && (mode == MTR_MODE_WAVEFRONT || !p->band_done || p->n_bands > n_pixels))
             return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: band completion words need the fused organisation, a band_done array and at most one band per pixel");
         if (mode == MTR_MODE_WAVEFRONT) {
-            int r = wf_render(s, p, t4, s4, a.rc, &wf_trace_ms, &scatter_ms, &launches, &scatter_launches, times_out != nullptr, &wf_trace_n, want_stats, &wf_shade_ms);
-            if (r) return r;
+            if (int r = wf_render(s, p, t4, s4, a.rc, times_out != nullptr, want_stats, &st)) return r;
         } else {
             FusedConfig cfg{};
             if (!fused_plan(s->dev, f, n_pixels, a.spp_chunk, usable_cus(c, p), a, cfg))
@@ -836,40 +777,26 @@ int mtr_render(mtr_scene *s, const mtr_render_params *p, float *t4, float *s4,
             if (p->n_bands) {
                 // (one banded launch in flight per context: the counts are the context's; callers that overlap launches on two
                 // streams — the per-band pipeline — do not use band words)
-                if (c->band_cap < p->n_bands) {
-                    HIP_TRY(c, hipStreamSynchronize(c->stream));
-                    if (c->d_band_count) (void)hipFree(c->d_band_count);
-                    c->d_band_count = nullptr; c->band_cap = 0;
-                    HIP_TRY(c, hipMalloc((void **)&c->d_band_count, (size_t)p->n_bands * sizeof(uint32_t)));
-                    c->band_cap = p->n_bands;
-                }
+                if (int r = grow_device_buffer(c, (void **)&c->d_band_count, &c->band_cap, (size_t)p->n_bands * sizeof(uint32_t))) return r;
                 HIP_TRY(c, hipMemsetAsync(c->d_band_count, 0, (size_t)p->n_bands * sizeof(uint32_t), c->stream));
                 a.n_bands = p->n_bands; a.band_px = n_pixels / p->n_bands; a.band_epoch = p->band_epoch;      // (>= 1: n_bands <= n_pixels, checked above; the last band takes the remainder)
                 a.band_count = c->d_band_count; a.band_done = (uint32_t *)(uintptr_t)p->band_done;
             }
             HIP_TRY(c, launch_fused(a, cfg, c->stream));
-            launches = 1;
+            st.launches = 1;
         }
     }
     if (times_out) HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     if (want_stats) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (counters_out) {
-            DevCounters h;
-            HIP_TRY(c, hipMemcpy(&h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
-            memset(counters_out, 0, sizeof *counters_out);
-            counters_out->paths = h.paths; counters_out->rays_closest = h.rays_closest;
-            counters_out->rays_shadow = h.rays_shadow; counters_out->splats_issued = h.splats_issued;
-            counters_out->bounces = h.bounces; counters_out->splats_overflow = h.splats_overflow;
-            counters_out->reserved[0] = h.r0; counters_out->reserved[1] = h.r1;
-        }
+        if (counters_out) if (int r = counters_to_abi(c, counters_out)) return r;
         if (times_out) {
             memset(times_out, 0, sizeof *times_out);
             float ms = 0.0f;
             HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            times_out->total_ms = ms; times_out->trace_ms = ms - scatter_ms; times_out->scatter_ms = scatter_ms;
-            times_out->trace_launches = launches; times_out->scatter_launches = scatter_launches;
-            times_out->wf_trace_ms = wf_trace_ms; times_out->wf_trace_kernel_launches = wf_trace_n; times_out->wf_shade_ms = wf_shade_ms;
+            times_out->total_ms = ms; times_out->trace_ms = ms - st.scatter_ms; times_out->scatter_ms = st.scatter_ms;
+            times_out->trace_launches = st.launches; times_out->scatter_launches = st.scatter_launches;
+            times_out->wf_trace_ms = st.trace_ms; times_out->wf_trace_kernel_launches = st.trace_kernel_launches; times_out->wf_shade_ms = st.shade_ms;
         }
     }
     return MTR_OK;
@@ -893,14 +820,7 @@ int mtr_render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_s, 
         return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_render_grad: NULL argument");
     mtr_ctx *c = s->ctx;
     const Film &f = s->film;
-    const uint64_t npix_crop = (uint64_t)f.crop_w * f.crop_h;
-    if (p->spp_total == 0 || p->spp_begin > p->spp_end || p->spp_end > p->spp_total)
-        return fail(c, MTR_ERR_INVALID, "mtr_render_grad: bad sample range");
-    if (p->pixel_begin > p->pixel_end || p->pixel_end > npix_crop)
-        return fail(c, MTR_ERR_INVALID, "mtr_render_grad: bad pixel range");
-    if (npix_crop * p->spp_total > (1ull << 32))
-        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: W*H*spp exceeds 2^32 lanes (common.py:51); render in passes");
-    if (p->max_depth < -1 || p->rr_depth <= 0) return fail(c, MTR_ERR_INVALID, "mtr_render_grad: bad max_depth / rr_depth");
+    if (int r = check_render_ranges(c, f, p, "mtr_render_grad", "render in passes")) return r;
     if (s->nlos.on || f.n_freq || f.lasers > 1u || (p->flags & MTR_FLAG_POLARIZED))
         return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: transient_path with a plain transient_hdr_film (RGB) only: "
                                             "no NLOS tier, phasor film, exhaustive_scan or polarized transport");
@@ -960,13 +880,7 @@ int mtr_counters_read(mtr_ctx *c, mtr_counters *out)
 {
     if (!c || !out) return fail(c, MTR_ERR_INVALID, "mtr_counters_read: NULL argument");
     HIP_TRY(c, hipSetDevice(c->device));
-    DevCounters h;
-    HIP_TRY(c, hipMemcpy(&h, c->d_counters, sizeof h, hipMemcpyDeviceToHost));
-    memset(out, 0, sizeof *out);
-    out->paths = h.paths; out->rays_closest = h.rays_closest; out->rays_shadow = h.rays_shadow;
-    out->splats_issued = h.splats_issued; out->bounces = h.bounces; out->splats_overflow = h.splats_overflow;
-    out->reserved[0] = h.r0; out->reserved[1] = h.r1;
-    return MTR_OK;
+    return counters_to_abi(c, out);
 }
 
 int mtr_film_develop(mtr_ctx *c, const mtr_film_desc *fd, const float *t4, float *t3, const float *s4, float *s3)
@@ -992,26 +906,13 @@ int mtr_splat_add(mtr_ctx *c, const mtr_splat_soa *s, const mtr_film_desc *fd, i
     HIP_TRY(c, hipSetDevice(c->device));
     Film fm = film_from_desc(*fd);
     if (fm.n_freq) {
-        if (c->freq_cap < fm.n_freq) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (c->d_freq) (void)hipFree(c->d_freq);
-            c->d_freq = nullptr; c->freq_cap = 0;
-            HIP_TRY(c, hipMalloc((void **)&c->d_freq, (size_t)fm.n_freq * 4));
-            c->freq_cap = fm.n_freq;
-        }
+        if (int r = grow_device_buffer(c, (void **)&c->d_freq, &c->freq_cap, (size_t)fm.n_freq * 4)) return r;
         HIP_TRY(c, hipMemcpyAsync(c->d_freq, fd->frequencies, (size_t)fm.n_freq * 4, hipMemcpyHostToDevice, c->stream));
         fm.freq = c->d_freq;
     }
     void *scratch = nullptr;
     if (variant == 1 && !fm.n_freq) {
-        const size_t need = 8u * ((size_t)fm.width * fm.height + 2u);
-        if (c->runs_cap < need) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (c->d_runs) (void)hipFree(c->d_runs);
-            c->d_runs = nullptr; c->runs_cap = 0;
-            HIP_TRY(c, hipMalloc(&c->d_runs, need));
-            c->runs_cap = need;
-        }
+        if (int r = grow_device_buffer(c, &c->d_runs, &c->runs_cap, 8u * ((size_t)fm.width * fm.height + 2u))) return r;
         scratch = c->d_runs;
     }
     if (elapsed_ms) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));

@@ -181,10 +181,10 @@ struct WfConfig { int stack; bool scene_lds; size_t lds_bytes; };
 size_t wf_planes_bytes(uint32_t n_slots);
 size_t wf_polar_planes_bytes(uint32_t n_slots);      // polarized transport: what follows wf_planes_bytes, rounded up to 16, in `planes`
 bool wf_plan(const SceneDev &sc, WfConfig &cfg);
-// which: 0 raygen, 1 trace (closest hit + material-sorted queues, or occlusion when a.trace_any), 2 shade,
-// 3 time-bin scatter-add, 5 one whole NLOS bounce (a.nlos_on), 6 one whole polarized bounce, 7 the Stokes scatter-add of
-// polarized transport
-hipError_t launch_wf(const WfArgs &a, const WfConfig &cfg, int which, int grid, hipStream_t stream);
+// Trace: closest hit + material-sorted queues, or occlusion when a.trace_any; Scatter: the time-bin (or phasor) scatter-add;
+// NlosBounce / PolarBounce: one whole bounce of the NLOS tier / of polarized transport; PolarScatter: the Stokes scatter-add
+enum class WfKernel { Raygen, Trace, Shade, Scatter, NlosBounce, PolarBounce, PolarScatter };
+hipError_t launch_wf(const WfArgs &a, const WfConfig &cfg, WfKernel which, int grid, hipStream_t stream);
 
 // scratch (variant 1): device buffer of >= 8 * (width * height + 2) bytes for the run table; NULL forces the atomics
 hipError_t launch_splat_add(int variant, const mtr_splat_soa &s, const Film &film, float *film_out,

@@ -1,4 +1,5 @@
 #include "mtr_scene_host.h"
+#include "mtr_polar.h"
 #include <chrono>
 #include <cstdio>
 #include "mtr_knobs.h"
@@ -331,7 +332,87 @@ const char *derive_scene(const mtr_scene_desc &d, HostScene &s)
     }
     s.mats.assign(d.materials, d.materials + d.n_materials);
     phase("slots, materials, emitters");
+    classify_scene(d, s);
     return nullptr;
+}
+
+static bool eq3(const float *v) { return memcmp(v, v + 1, sizeof(float)) == 0 && memcmp(v, v + 2, sizeof(float)) == 0; }
+
+bool colours_are_grey(const mtr_material *mats, uint32_t n_mats, const Emitter *ems, uint32_t n_ems, bool textured)
+{
+    bool grey = !textured;
+    for (uint32_t i = 0; grey && i < n_mats; ++i) {
+        const mtr_material &m = mats[i];
+        const bool aniso = (m.flags & MTR_MAT_ANISOTROPIC) != 0u;      // (an anisotropic lobe keeps its second roughness in b[0] / c2[0])
+        grey = m.albedo_texture == 0u && eq3(m.a) && eq3(m.c) &&
+               ((aniso && m.type == MTR_BSDF_ROUGHDIELECTRIC) || eq3(m.b)) && ((aniso && m.type == MTR_BSDF_ROUGHCONDUCTOR) || eq3(m.c2));
+    }
+    for (uint32_t i = 0; grey && i < n_ems; ++i) grey = eq3(ems[i].radiance);
+    return grey;
+}
+
+uint32_t traits_with_laser(uint32_t traits, bool grey_scene, const float laser_irradiance[3])
+{
+    return (grey_scene && eq3(laser_irradiance)) ? (traits | kTrGrey) : (traits & ~kTrGrey);
+}
+
+void classify_scene(const mtr_scene_desc &d, HostScene &hs)
+{
+    hs.polar_ok = hs.texels.empty();
+    bool lobes = false;
+    for (uint32_t i = 0; i < d.n_materials; ++i) {
+        if (!polar_bsdf_supported(d.materials[i].type)) hs.polar_ok = false;
+        if (bsdf_is_lobe(d.materials[i].type)) lobes = true;
+    }
+    for (const Emitter &e : hs.ems) if (e.angular) hs.polar_ok = false;
+    hs.needs_ext = lobes || !hs.vnormals.empty() || !hs.texels.empty();      // smooth-shaded triangles, bitmap textures: the extended shading code as well
+    // scene traits (mtr_core.h): facts about the tables that let the kernels drop shading code no hit can reach
+    hs.traits = 0u;
+    if (!hs.needs_ext) {
+        bool diffuse_only = d.n_materials > 0;
+        for (uint32_t i = 0; i < d.n_materials; ++i)
+            if (d.materials[i].type != MTR_BSDF_DIFFUSE || (d.materials[i].flags & MTR_MAT_TWOSIDED)) diffuse_only = false;
+        if (diffuse_only) hs.traits |= kTrDiffuse;
+        if (d.n_emitters == 1 && !hs.ems[0].is_mesh && !hs.ems[0].angular) hs.traits |= kTrOneRectEmitter;     // (its kernels have no falloff code)
+        bool leaf_pairs = hs.has_wide;
+        for (const WNode &n : hs.wnodes)
+            for (uint32_t k = 0; k < n.count; ++k) {
+                const uint32_t code = ~(uint32_t)n.ref[k];
+                if (n.ref[k] < 0 && !(code & kLeafQuadBit) && (code & 3u) + 1u > 2u) leaf_pairs = false;
+            }
+        if (leaf_pairs) hs.traits |= kTrLeafPair;
+    } else if (!lobes) hs.traits |= kTrNoLobes;          // the extended shading code is needed for normals / bitmaps only
+    hs.grey_scene = colours_are_grey(d.materials, d.n_materials, hs.ems.data(), d.n_emitters, !hs.texels.empty());
+    if (hs.grey_scene) hs.traits |= kTrGrey;             // (the scene's part; the NLOS tier adds the laser's: traits_with_laser)
+    // kTrFlatTop (any materials): the root's children are rectangles and box nodes, the boxes' nodes follow the root in order
+    memset(&hs.flat, 0, sizeof hs.flat);
+    if (hs.has_wide && !hs.wnodes.empty() && hs.wide_levels <= 2 && !mtr::knob("MTR_NO_FLAT")) {
+        const WNode &root = hs.wnodes[0];
+        bool flat = root.flags == 0u && root.count >= 1u;
+        uint32_t n_inner = 0u, prim_mask = 0u;
+        for (uint32_t k = 0; flat && k < root.count; ++k) {
+            const int32_t ref = root.ref[k];
+            if (k < root.n_quads) { flat = ref < 0 && ((~(uint32_t)ref) & kLeafQuadBit) != 0u; prim_mask |= 1u << k; }
+            else if (ref < 0) { flat = ((~(uint32_t)ref) & kLeafQuadBit) == 0u; prim_mask |= 1u << k; }             // a triangle leaf
+            else {            // an inner child: a box node, and the n-th of them is node n + 1
+                flat = ref == (int32_t)(1u + n_inner) && (size_t)ref < hs.wnodes.size() && hs.wnodes[ref].flags == 3u && hs.wnodes[ref].count == 6u;
+                ++n_inner;
+            }
+        }
+        flat = flat && n_inner <= kFlatMaxBoxes;
+        if (flat) {
+            FlatTop &ft = hs.flat;
+            ft.n_quads = root.n_quads; ft.n_boxes = n_inner; ft.node0 = 1u; ft.prim_mask = prim_mask;
+            for (uint32_t b = 0; b < ft.n_boxes; ++b) {
+                const float *x = hs.wnodes[1u + b].xf;
+                memcpy(ft.xf[b], x, 12 * sizeof(float));
+                for (int k = 0; k < 3; ++k) ft.xf[b][12 + k] = (fabsf(x[4 * k]) + fabsf(x[4 * k + 1]) + fabsf(x[4 * k + 2])) * 1.000001f;      // S: row sums of |R| (rounded up)
+                ft.xf[b][15] = 0.0f;
+            }
+            hs.traits |= kTrFlatTop;
+            if (prim_mask >> root.n_quads) hs.traits |= kTrFlatLeaves;
+        }
+    }
 }
 
 const char *derive_nlos(const mtr_scene_desc &d, HostNlos &o)

@@ -32,7 +32,21 @@ struct HostScene {
     uint32_t wide_levels = 0, wide4_levels = 0, wide8q_levels = 0;        // levels of the collapsed trees (= their traversal stack bound)
     Camera cam{};
     Film film{};
+    // classify_scene's verdict on the tables above.  The host picks kernels by it, and a specialised kernel LACKS the code a trait rules out
+    uint32_t traits = 0;                       // kTr* (mtr_core.h)
+    bool needs_ext = false;                    // the extended shading code: a lobe, a smooth-shaded triangle, a bitmap (SceneDev::has_rough)
+    bool polar_ok = false;                     // every material and emitter has a polarized form (mtr_polar.h)
+    bool grey_scene = false;                   // kTrGrey without the NLOS laser (traits_with_laser decides with it)
+    FlatTop flat{};                            // traits & kTrFlatTop: the top level as scalar kernel arguments
 };
+
+inline bool bsdf_is_lobe(uint32_t type) { return bsdf_is_rough(type) || type == MTR_BSDF_THINDIELECTRIC; }     // what only the extended shading code evaluates
+// the colour-dependent trait (kTrGrey, the scene's part): three equal channels in every colour, no bitmap
+bool colours_are_grey(const mtr_material *mats, uint32_t n_mats, const Emitter *ems, uint32_t n_ems, bool textured);
+// fills traits, needs_ext, polar_ok, grey_scene and flat from the tables (derive_scene ends with it)
+void classify_scene(const mtr_scene_desc &d, HostScene &s);
+// kTrGrey of the NLOS tier: the scene's colours and the laser's irradiance
+uint32_t traits_with_laser(uint32_t traits, bool grey_scene, const float laser_irradiance[3]);
 
 // NLOS tier tables (TransientNLOSPath.prepare, transientnlospath.py:251-292): shape / face distributions,
 // rectangle normals, triangles in ORIGINAL order for Mesh::sample_position, projector constants

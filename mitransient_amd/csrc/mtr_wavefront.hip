@@ -1335,11 +1335,11 @@ __global__ void __launch_bounds__(kBlock) k_wf_polar_scatter(const WfArgs a)
 }
 
 template <int STACK, bool SL>
-hipError_t launch_set(const WfArgs &a, int which, int grid, size_t lds, hipStream_t stream)
+hipError_t launch_set(const WfArgs &a, WfKernel which, int grid, size_t lds, hipStream_t stream)
 {
     const bool ext = a.sc.has_rough != 0u;
     if constexpr (SL) {          // scenes staged in LDS whose tables allow it: the specialised shading code (as k_fused)
-        if (which == 2 && !ext && (a.sc.traits & kTrCornell) == kTrCornell) {
+        if (which == WfKernel::Shade && !ext && (a.sc.traits & kTrCornell) == kTrCornell) {
             // (NOT the flat top level of k_fused: this kernel's lanes are the samples of neighbouring pixels at the SAME bounce — their shadow
             // rays walk the tree together — and flat_walk_device's uniform stages cost them more than the walk: config 2 in this
             // organisation 82.4 -> 87.4 ms with it, measured in round 6; a flat k_wf_trace changed nothing, 82.4 against 81 - 83)
@@ -1351,7 +1351,7 @@ hipError_t launch_set(const WfArgs &a, int which, int grid, size_t lds, hipStrea
             return hipGetLastError();
         }
     }
-    if (which == 6) {            // polarized bounce: the LDS of k_wf_nlos_bounce (record-list tails, steady sums)
+    if (which == WfKernel::PolarBounce) {            // polarized bounce: the LDS of k_wf_nlos_bounce (record-list tails, steady sums)
         lds += al16(a.G * 4u) + al16(a.G * 16u) + al16(a.seg);
         void (*kp)(const WfArgs) = k_wf_polar_bounce<STACK, SL>;
         hipError_t e = hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1359,12 +1359,13 @@ hipError_t launch_set(const WfArgs &a, int which, int grid, size_t lds, hipStrea
         hipLaunchKernelGGL(kp, dim3(grid), dim3(kBlock), lds, stream, a);
         return hipGetLastError();
     }
-    void (*k)(const WfArgs) = which == 0 ? k_wf_raygen<STACK, SL> : which == 1 ? (a.trace_any ? k_wf_trace<STACK, SL, true> : a.first_bounce ? k_wf_trace<STACK, SL, false, true> : k_wf_trace<STACK, SL, false>)
-                            : which == 5 ? (ext ? k_wf_nlos_bounce<STACK, SL, true> : k_wf_nlos_bounce<STACK, SL, false>)
+    void (*k)(const WfArgs) = which == WfKernel::Raygen ? k_wf_raygen<STACK, SL>
+                            : which == WfKernel::Trace ? (a.trace_any ? k_wf_trace<STACK, SL, true> : a.first_bounce ? k_wf_trace<STACK, SL, false, true> : k_wf_trace<STACK, SL, false>)
+                            : which == WfKernel::NlosBounce ? (ext ? k_wf_nlos_bounce<STACK, SL, true> : k_wf_nlos_bounce<STACK, SL, false>)
                             : a.first_bounce ? (ext ? k_wf_shade<STACK, SL, true, 0u, true> : k_wf_shade<STACK, SL, false, 0u, true>)
                             : (ext ? k_wf_shade<STACK, SL, true> : k_wf_shade<STACK, SL, false>);
     lds += al16(a.G * 4u) + al16(a.G * 16u) + al16(a.seg);        // k_wf_shade: record-list tails, steady sums, sort keys of the next live list; k_wf_trace: hit material types
-    if (which == 2 && a.q_order) lds += (SL ? 0u : al16(a.seg)) + 1056u;      // k_wf_shade, TRACE ORDER experiment: + sort keys of the shadow list (scenes in HBM), trace_sort's histogram
+    if (which == WfKernel::Shade && a.q_order) lds += (SL ? 0u : al16(a.seg)) + 1056u;      // k_wf_shade, TRACE ORDER experiment: + sort keys of the shadow list (scenes in HBM), trace_sort's histogram
     hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, stream, a);
@@ -1386,15 +1387,14 @@ bool wf_plan(const SceneDev &sc, WfConfig &cfg)
     return true;
 }
 
-// which: 0 raygen, 1 trace, 2 shade, 3 scatter, 5 NLOS bounce
-hipError_t launch_wf(const WfArgs &a, const WfConfig &cfg, int which, int grid, hipStream_t stream)
+hipError_t launch_wf(const WfArgs &a, const WfConfig &cfg, WfKernel which, int grid, hipStream_t stream)
 {
-    if (which == 3 && a.film.n_freq) {
+    if (which == WfKernel::Scatter && a.film.n_freq) {
         const size_t lds = 64 + kPhasorChunk * 8u + kBlock * 8u;
         hipLaunchKernelGGL(k_wf_phasor_scatter, dim3(grid), dim3(kBlock), lds, stream, a);
         return hipGetLastError();
     }
-    if (which == 7) {            // polarized transport: the Stokes scatter-add
+    if (which == WfKernel::PolarScatter) {
         if (!a.rec_cap) return hipSuccess;                      // rows do not fit LDS: every contribution went to the film's atomics
         const size_t lds = 64 + (size_t)a.film.bins * 16u;
         hipError_t e = hipFuncSetAttribute((const void *)k_wf_polar_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1402,7 +1402,7 @@ hipError_t launch_wf(const WfArgs &a, const WfConfig &cfg, int which, int grid, 
         hipLaunchKernelGGL(k_wf_polar_scatter, dim3(grid), dim3(kBlock), lds, stream, a);
         return hipGetLastError();
     }
-    if (which == 3) {
+    if (which == WfKernel::Scatter) {
         // fixed-point rows need 24 B per bin; fall back to f32 rows (12 B) when that does not leave 2 workgroups per CU
         const bool fixed = a.rec_cap && (size_t)a.film.bins * 24u <= 72u * 1024u;
         size_t lds = 64 + (a.rec_cap ? (size_t)a.film.bins * (fixed ? 24u : 12u) : 16u);

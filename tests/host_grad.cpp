@@ -67,8 +67,7 @@ static int render_grad(const mtr_scene_desc *d, const mtr_render_params *p, cons
     GradConst gc;
     gc.g_s = g_s; gc.g_t = g_t; gc.em_radiance = rad.data();
     gc.steady_scale = rc.sample_scale; gc.transient_scale = rc.sample_scale;
-    bool ext = !hs.vnormals.empty() || !hs.texels.empty();      // the product's rule (mtr_api.hip: has_rough)
-    for (uint32_t i = 0; i < d->n_materials; ++i) ext = ext || bsdf_is_rough(d->materials[i].type) || d->materials[i].type == MTR_BSDF_THINDIELECTRIC;
+    const bool ext = hs.needs_ext;
     std::memset(grad_mats, 0, sizeof(double) * 3 * d->n_materials);
     std::memset(grad_ems, 0, sizeof(double) * 3 * d->n_emitters);
     HostAcc acc{ grad_mats, grad_ems, d->n_materials, rec };

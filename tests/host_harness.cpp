@@ -92,9 +92,7 @@ extern "C" int hh_render(const mtr_scene_desc *d, const mtr_render_params *p, fl
     // NLOS tier: tables + scanned points (the product computes the latter in k_nlos_prepare)
     HostNlos hn; std::vector<q4> targets;
     const bool nlos = d->nlos != nullptr;
-    // the product's rule for the extended shading code (mtr_api.hip: has_rough): a GGX lobe, a smooth-shaded triangle, a bitmap
-    bool ext = !hs.vnormals.empty() || !hs.texels.empty();
-    for (uint32_t i = 0; i < d->n_materials; ++i) ext = ext || bsdf_is_rough(d->materials[i].type);
+    const bool ext = hs.needs_ext;
     if (nlos) {
         if (derive_nlos(*d, hn)) return -2;
         NlosConst &k = hn.k;
@@ -156,6 +154,19 @@ extern "C" int hh_render(const mtr_scene_desc *d, const mtr_render_params *p, fl
         out->paths = paths; out->rays_closest = closest; out->rays_shadow = shadow;
         out->bounces = bounces; out->splats_issued = sink.n;
     }
+    return 0;
+}
+
+// what the product decides about a scene before it picks kernels (mtr_scene_host.cpp classify_scene; with an NLOS description
+// the laser's part of kTrGrey as mtr_scene_set_nlos adds it): trait word, extended shading code, polarized form, and
+// (n_quads, n_boxes, node0, prim_mask) of the flat top level followed by the levels of the 8-wide tree
+extern "C" int hh_scene_class(const mtr_scene_desc *d, uint32_t *traits, uint32_t *needs_ext, uint32_t *polar_ok, uint32_t *flat5)
+{
+    HostScene hs;
+    if (derive_scene(*d, hs)) return -1;
+    *traits = d->nlos ? traits_with_laser(hs.traits, hs.grey_scene, d->nlos->laser_irradiance) : hs.traits;
+    *needs_ext = hs.needs_ext ? 1u : 0u; *polar_ok = hs.polar_ok ? 1u : 0u;
+    flat5[0] = hs.flat.n_quads; flat5[1] = hs.flat.n_boxes; flat5[2] = hs.flat.node0; flat5[3] = hs.flat.prim_mask; flat5[4] = hs.wide_levels;
     return 0;
 }
 
