@@ -424,7 +424,8 @@ def render(scene: Scene, params=None, sensor=0, integrator=None, seed=0, seed_gr
         @staticmethod
         def backward(ctx, g_s, g_t):
             g = integ.render_backward(scene, params, grad_in=(g_s, g_t), sensor=sensor, seed=seed_grad, spp=spp_grad)
-            return tuple(g[k].to(dtype=v.dtype, device=v.device).reshape(v.shape) if v.numel() == 3 else g[k].sum().reshape(v.shape)
+            # (a 1-element value stands for the three channels: it receives their sum, on its own device like the 3-vector)
+            return tuple((g[k] if v.numel() == 3 else g[k].sum()).to(dtype=v.dtype, device=v.device).reshape(v.shape)
                          for k, v in grads)
 
     s, t = _Render.apply(*[v for _, v in grads])

@@ -39,21 +39,32 @@ def _mi():
     return mi
 
 
-def cornell(res=16, bins=32, max_depth=4, start_opl=3.5, bin_width=0.1, crop=None, angular=False, share=False, **integ):
-    """cornell_box() at a small size, rr_depth >= max_depth; angular: a second, `angulararea` luminaire on the back wall"""
+def angular_spot():
+    """a second, `angulararea` luminaire on the Cornell box's back wall"""
+    from mitransient_amd.transform import ScalarTransform4f as T
+    return dict(type="rectangle", to_world=T().translate([0.4, 0.3, -0.99]).scale([0.2, 0.2, 0.2]),
+                bsdf=dict(type="diffuse", reflectance=dict(type="rgb", value=[0.3, 0.4, 0.5])),
+                emitter=dict(type="angulararea", cutoff_angle=60.0, beam_width=30.0,
+                             radiance=dict(type="rgb", value=[2.0, 3.0, 0.0])))
+
+
+def cornell(res=16, bins=32, max_depth=4, start_opl=3.5, bin_width=0.1, crop=None, angular=False, share=False, rr_depth=None,
+            blue=None, **integ):
+    """cornell_box() at a small size, rr_depth > max_depth unless `rr_depth` says otherwise; angular: a second, `angulararea`
+    luminaire on the back wall; blue: the blue channel of every reflectance (test_grad_general.py: 1.0 keeps rr_prob constant)"""
     import mitransient_amd as mitr
     mi = _mi()
     d = mitr.cornell_box()
-    d["integrator"].update(max_depth=max_depth, rr_depth=max(max_depth, 1) + 1, **integ)
+    d["integrator"].update(max_depth=max_depth, rr_depth=max(max_depth, 1) + 1 if rr_depth is None else rr_depth, **integ)
     d["sensor"]["film"].update(width=res, height=res, temporal_bins=bins, start_opl=start_opl, bin_width_opl=bin_width)
     if crop is not None:
         d["sensor"]["film"].update(crop_width=crop[0], crop_height=crop[1], crop_offset_x=crop[2], crop_offset_y=crop[3])
+    if blue is not None:
+        for name in ("white", "red", "green"):
+            refl = d[name]["reflectance"]
+            refl["value"] = list(refl["value"][:2]) + [blue]
     if angular:
-        from mitransient_amd.transform import ScalarTransform4f as T
-        d["spot"] = dict(type="rectangle", to_world=T().translate([0.4, 0.3, -0.99]).scale([0.2, 0.2, 0.2]),
-                         bsdf=dict(type="diffuse", reflectance=dict(type="rgb", value=[0.3, 0.4, 0.5])),
-                         emitter=dict(type="angulararea", cutoff_angle=60.0, beam_width=30.0,
-                                      radiance=dict(type="rgb", value=[2.0, 3.0, 0.0])))
+        d["spot"] = angular_spot()
     if share:      # one inline BSDF dictionary on two shapes: each of their keys must own a record
         shared = dict(type="twosided", bsdf=dict(type="diffuse", reflectance=dict(type="rgb", value=[0.6, 0.5, 0.4])))
         d["floor"]["bsdf"] = shared
@@ -109,13 +120,25 @@ def upstream(scene, kind, seed=1):
     return g_s, g_t
 
 
-def fd_material(scene, params, g_s, g_t, m, k):
+def fd_material(scene, params, g_s, g_t, m, k, wide=False):
     """five-point stencil of the oracle's loss in channel k of material m.  The loss is a polynomial of degree < max_depth <= 5
     in the albedo, so the stencil is exact for every step; the step is a / 4 rounded down to a power of two (every abscissa
     exact in f32) rather than a / 64: the oracle sums in f32, and its rounding noise over a / 64 is up to 5e-4 of the gradient
-    for the red wall's 0.043 channel, against 1e-5 over a / 4"""
+    for the red wall's 0.043 channel, against 1e-5 over a / 4.
+    wide (test_grad_general.py): the derivative at a of the quartic fitted by least squares to the loss at 16 abscissae from
+    a / 8 to a + 1 / 4 instead — as exact for the same polynomial, all abscissae positive (with a negative reflectance the oracle's
+    loss leaves the polynomial), and the rounding noise of a small channel is spread over a span that does not shrink with a"""
     sd = scene.data()
     a = float(sd.materials[m].a[k])
+    if wide:
+        xs = np.linspace(a / 8, a + 0.25, 16).astype(np.float32).astype(np.float64)
+        vals = []
+        for x in xs:
+            sd.materials[m].a[k] = x
+            vals.append(oracle_loss(scene, params, g_s, g_t)[0])
+        sd.materials[m].a[k] = a
+        span = xs[-1] - xs[0]
+        return float(np.polyder(np.poly1d(np.polyfit((xs - a) / span, vals, 4)))(0.0) / span)
     h = 2.0 ** np.floor(np.log2(a / 4))
     vals = []
     for j in (-2, -1, 1, 2):
@@ -125,15 +148,25 @@ def fd_material(scene, params, g_s, g_t, m, k):
     return (vals[0] - 8 * vals[1] + 8 * vals[2] - vals[3]) / (12 * h)
 
 
-def check_materials(hg, scene, g_s, g_t, mats=None, tol=1e-4):
+def within(g, fd, tol):
+    """the comparison of check_materials: every channel of a material within tol of the largest finite difference"""
+    return bool(np.abs(g - fd).max() <= tol * max(np.abs(fd).max(), 1e-12))
+
+
+def check_materials(hg, scene, g_s, g_t, mats=None, tol=1e-4, chans=(0, 1, 2), gm=None, report=None, wide=False):
+    """gm: the gradients to check (the host build's when None); report: a dictionary that receives {m: (gradient, finite
+    differences, error relative to the largest finite difference)} over the channels `chans`"""
     params = render_params(scene)
-    gm, _ = host_grad(hg, scene, params, g_s, g_t)
+    if gm is None:
+        gm, _ = host_grad(hg, scene, params, g_s, g_t)
     sd = scene.data()
     mats = range(sd.n_materials) if mats is None else mats
+    chans = list(chans)
     for m in mats:
-        fd = np.array([fd_material(scene, params, g_s, g_t, m, k) for k in range(3)])
-        scale = max(np.abs(fd).max(), 1e-12)
-        assert np.abs(gm[m] - fd).max() <= tol * scale, (m, gm[m], fd)
+        fd = np.array([fd_material(scene, params, g_s, g_t, m, k, wide) for k in chans])
+        if report is not None:
+            report[m] = (gm[m][chans], fd, float(np.abs(gm[m][chans] - fd).max() / max(np.abs(fd).max(), 1e-12)))
+        assert within(gm[m][chans], fd, tol), (m, gm[m], fd)
     return gm
 
 
@@ -258,6 +291,26 @@ def test_material_at_several_vertices(hg):
     check_materials(hg, scene, g_s, g_t, mats=[white])
 
 
+def emitter_coefficients(scene, params, g_s, g_t):
+    """(n_emitters, 3): the oracle's loss with channel k of emitter e at 1 as the scene's only light"""
+    sd = scene.data()
+    n = sd.n_emitters
+    saved = [[float(sd.emitters[e].radiance[k]) for k in range(3)] for e in range(n)]
+    ref = np.zeros((n, 3))
+    try:
+        for e in range(n):
+            for k in range(3):
+                for e2 in range(n):
+                    for k2 in range(3):
+                        sd.emitters[e2].radiance[k2] = 1.0 if (e2, k2) == (e, k) else 0.0
+                ref[e, k] = oracle_loss(scene, params, g_s, g_t)[0]
+    finally:
+        for e in range(n):
+            for k in range(3):
+                sd.emitters[e].radiance[k] = saved[e][k]
+    return ref
+
+
 def test_emitter_gradients_are_the_linear_coefficients(hg):
     """the estimator is linear in each radiance channel: d loss / d L_e[k] is the loss of a render whose only light is
     channel k of emitter e at 1 — two emitters, one of them `angulararea`"""
@@ -267,19 +320,10 @@ def test_emitter_gradients_are_the_linear_coefficients(hg):
     _, ge = host_grad(hg, scene, params, g_s, g_t)
     sd = scene.data()
     assert sd.n_emitters == 2 and sd.emitters[1].angular == 1
-    saved = [[float(sd.emitters[e].radiance[k]) for k in range(3)] for e in range(2)]
-    try:
-        for e in range(2):
-            for k in range(3):
-                for e2 in range(2):
-                    for k2 in range(3):
-                        sd.emitters[e2].radiance[k2] = 1.0 if (e2, k2) == (e, k) else 0.0
-                ref = oracle_loss(scene, params, g_s, g_t)[0]
-                assert abs(ge[e, k] - ref) <= 1e-5 * max(abs(ref), 1e-12) + 1e-9, (e, k, ge[e, k], ref)
-    finally:
-        for e in range(2):
-            for k in range(3):
-                sd.emitters[e].radiance[k] = saved[e][k]
+    ref = emitter_coefficients(scene, params, g_s, g_t)
+    for e in range(2):
+        for k in range(3):
+            assert abs(ge[e, k] - ref[e, k]) <= 1e-5 * max(abs(ref[e, k]), 1e-12) + 1e-9, (e, k, ge[e, k], ref[e, k])
     assert ge[1, 2] != 0.0          # a radiance channel of 0 still has its gradient
 
 
