@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 15
+#define MTR_ABI_VERSION 16
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -389,6 +389,18 @@ int  mtr_scene_traits(const mtr_scene *, uint32_t *traits);
  * n_emitters x 3) every mtr_emitter.radiance; the traits that depend on colours are decided again.  Synchronises the context's
  * stream.  MTR_ERR_UNSUPPORTED for a scene with the NLOS tier (recreate it). */
 int  mtr_scene_set_colors(mtr_scene *, const float *material_a, const float *emitter_radiance);
+/* (ABI 16) ... and new texels for one bitmap (params["<bsdf>.reflectance.data"], Mitsuba's BitmapTexture parameter `data`):
+ * rgb (host, height x width x 3 floats, row 0 first, linear RGB, the size the texture was created with) replaces texture
+ * `index` of mtr_scene_desc.textures on the device, and `a` of every material that references it becomes the new mean colour
+ * (summed in f64, rounded to f32 once), so that the scene is the one a fresh mtr_scene_create with these texels gives; a caller
+ * that computes the stand-in its own way (the Python layer: an f32 mean) follows with mtr_scene_set_colors.
+ * Nothing else is rebuilt.  Synchronises the context's stream.  MTR_ERR_INVALID for an unknown index, MTR_ERR_UNSUPPORTED for a
+ * scene with the NLOS tier. */
+int  mtr_scene_set_texture(mtr_scene *, uint32_t index, const float *rgb);
+/* (ABI 16) Where texture `index` lies in the texel array of mtr_render_grad_tex: its first texel (textures follow each other in
+ * scene order, row 0 first) and its size.  Any output may be NULL; index == n_textures answers first_texel = the number of texels
+ * of the whole scene (width = height = 0). */
+int  mtr_scene_texture_layout(const mtr_scene *, uint32_t index, uint32_t *first_texel, uint32_t *width, uint32_t *height);
 
 /* TransientImageBlock.clear (transient_image_block.py:56-70): zero the
  * (H,W,T,4) f32 accumulator and the (H,W,4) steady accumulator. */
@@ -418,7 +430,8 @@ int  mtr_render_plan(mtr_scene *, const mtr_render_params *, uint32_t *mode_out,
  * TransientPath.sample's backward pass (transientpath.py:88-326, :284-299).  For the lanes of `params` (the same lanes, seeds
  * and passes mtr_render would run) the gradient of  sum g_s . steady + sum g_t . transient  of the seeded estimator is STORED to
  *   grad_materials : device f32 (n_materials, 3)  d loss / d reflectance of every plain `diffuse` material (constant `a`;
- *                                                  other materials and bitmap-textured ones receive 0)
+ *                                                  other materials receive 0, and so do bitmap-textured ones: their
+ *                                                  gradient is per texel, mtr_render_grad_tex)
  *   grad_emitters  : device f32 (n_emitters, 3)   d loss / d radiance of every `area` / `angulararea` emitter
  * with the upstream gradients of the DEVELOPED tensors
  *   grad_steady_hw3     : device f32 (H, W, 3)
@@ -431,6 +444,27 @@ int  mtr_render_plan(mtr_scene *, const mtr_render_params *, uint32_t *mode_out,
 int  mtr_render_grad(mtr_scene *, const mtr_render_params *params,
                      const float *grad_steady_hw3, const float *grad_transient_hwt3,
                      float *grad_materials, float *grad_emitters);
+
+/* (ABI 16) mtr_render_grad plus the gradients of bitmap texels (the reference: a BitmapTexture's `data` is an ordinary
+ * differentiable parameter of TransientADIntegrator.render_backward, common.py:325-409):
+ *   grad_texels : device f32 (n_texels, 3)  d loss / d texel of every texture, textures in scene order, row 0 first
+ *                                           (mtr_scene_texture_layout gives a texture's first texel); NULL: exactly mtr_render_grad
+ * At a vertex on a `diffuse` material (also two-sided) with albedo_texture != 0 the remaining sum divided per channel by the
+ * interpolated colour goes to the four taps of the bilinear lookup with the lookup's own weights; taps that wrap onto one texel
+ * add up; a channel whose interpolated colour is exactly 0 gets nothing (0, never NaN).  Gradients are per TEXTURE: materials that
+ * share a bitmap sum into it.  Only `diffuse` vertices contribute: a bitmap that a roughplastic references as well receives its
+ * diffuse materials' part alone and is no parameter (the Python layer gives it no key).  grad_materials of textured materials stay 0.
+ * The sums are f64 in one of two tiers (mtr_render_grad_tex_tier): in the workgroups' LDS slabs when all texel words fit beside
+ * the material / emitter words (bitwise reproducible), by f64 global atomics otherwise (the f32 result can differ in its last
+ * bit from run to run: arrival order). */
+int  mtr_render_grad_tex(mtr_scene *, const mtr_render_params *params,
+                         const float *grad_steady_hw3, const float *grad_transient_hwt3,
+                         float *grad_materials, float *grad_emitters, float *grad_texels);
+/* (ABI 16) Which tier mtr_render_grad_tex runs for this scene (for tests and tools): a function of the scene alone. */
+#define MTR_GRAD_TEX_NONE   0u   /* no bitmap: grad_texels is not touched */
+#define MTR_GRAD_TEX_SLAB   1u   /* texel words in the f64 LDS slab, summed by the reduction pass */
+#define MTR_GRAD_TEX_GLOBAL 2u   /* f64 global atomics into a device buffer, converted to f32 by a small pass */
+int  mtr_render_grad_tex_tier(const mtr_scene *, uint32_t *tier);
 
 /* Zero the context's device counters on the context stream (then issue every mtr_render of the render with
  * MTR_FLAG_KEEP_COUNTERS and read the sums once with mtr_counters_read). */

@@ -78,6 +78,8 @@ struct mtr_scene {
     float *d_freq = nullptr;               // phasor film: device copy of film_desc.frequencies
     std::vector<float> h_freq;
     uint32_t n_leaves = 0;
+    std::vector<q4> tex_info;                // host copy of dev.tex_info: (first texel, width, height, -) per texture
+    uint32_t n_texels = 0;                   // texels of all textures (mtr_render_grad_tex's grad_texels)
     std::vector<void *> allocs;
     SplatLog log{ nullptr, 0, nullptr };
 };
@@ -216,6 +218,7 @@ int mtr_scene_create(mtr_ctx *c, const mtr_scene_desc *d, mtr_scene **out)
     if (!hs.vnormals.empty()) UP(hs.vnormals, vnormals);
     if (!hs.texels.empty()) { UP(hs.texels, texels); UP(hs.tex_info, tex_info); UP(hs.uvs, uvs); }
 #undef UP
+    s->tex_info = hs.tex_info; s->n_texels = (uint32_t)hs.texels.size();
     s->dev.n_nodes = (uint32_t)hs.nodes.size(); s->dev.n_slots = (uint32_t)hs.tshade.size();
     s->dev.n_mats = d->n_materials; s->dev.n_ems = d->n_emitters;
     // what the kernels are chosen by: decided over the host tables (mtr_scene_host.cpp classify_scene)
@@ -355,6 +358,47 @@ int mtr_scene_set_colors(mtr_scene *s, const float *material_a, const float *emi
     const bool grey = colours_are_grey(mats.data(), (uint32_t)mats.size(), ems.data(), (uint32_t)ems.size(), s->dev.texels != nullptr);
     s->grey_scene = grey;
     s->dev.traits = grey ? (s->dev.traits | kTrGrey) : (s->dev.traits & ~kTrGrey);
+    return MTR_OK;
+}
+
+int mtr_scene_set_texture(mtr_scene *s, uint32_t index, const float *rgb)
+{
+    if (!s || !rgb) return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_scene_set_texture: NULL argument");
+    mtr_ctx *c = s->ctx;
+    if (index >= s->tex_info.size()) return fail(c, MTR_ERR_INVALID, "mtr_scene_set_texture: unknown texture");
+    if (s->nlos.on) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_scene_set_texture: not for the NLOS tier");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // (renders in flight read the tables)
+    const q4 info = s->tex_info[index];
+    const size_t first = fbits(info.x), n = (size_t)fbits(info.y) * fbits(info.z);
+    std::vector<q4> tx(n);
+    for (size_t k = 0; k < n; ++k) tx[k] = q4{ rgb[3 * k], rgb[3 * k + 1], rgb[3 * k + 2], 0.0f };
+    HIP_TRY(c, hipMemcpy((void *)(s->dev.texels + first), tx.data(), n * sizeof(q4), hipMemcpyHostToDevice));
+    // the mean colour stands in as `a` of the materials on this bitmap, as the scene builder computes it (f32 texels, f64 sum)
+    double mean[3] = { 0.0, 0.0, 0.0 };
+    for (size_t k = 0; k < n; ++k) for (int j = 0; j < 3; ++j) mean[j] += (double)rgb[3 * k + j];
+    std::vector<mtr_material> mats(s->dev.n_mats);
+    if (!mats.empty()) HIP_TRY(c, hipMemcpy(mats.data(), s->dev.mats, mats.size() * sizeof(mtr_material), hipMemcpyDeviceToHost));
+    for (mtr_material &m : mats)
+        if (m.albedo_texture == index + 1u) for (int j = 0; j < 3; ++j) m.a[j] = (float)(mean[j] / (double)n);
+    if (!mats.empty()) HIP_TRY(c, hipMemcpy((void *)s->dev.mats, mats.data(), mats.size() * sizeof(mtr_material), hipMemcpyHostToDevice));
+    return MTR_OK;
+}
+
+int mtr_scene_texture_layout(const mtr_scene *s, uint32_t index, uint32_t *first_texel, uint32_t *width, uint32_t *height)
+{
+    if (!s || index > s->tex_info.size()) return MTR_ERR_INVALID;
+    const bool end = index == s->tex_info.size();
+    if (first_texel) *first_texel = end ? s->n_texels : fbits(s->tex_info[index].x);
+    if (width) *width = end ? 0u : fbits(s->tex_info[index].y);
+    if (height) *height = end ? 0u : fbits(s->tex_info[index].z);
+    return MTR_OK;
+}
+
+int mtr_render_grad_tex_tier(const mtr_scene *s, uint32_t *tier)
+{
+    if (!s || !tier) return MTR_ERR_INVALID;
+    *tier = grad_tex_tier(s->dev, s->n_texels);
     return MTR_OK;
 }
 
@@ -813,8 +857,9 @@ int mtr_render_plan(mtr_scene *s, const mtr_render_params *p, uint32_t *mode_out
     return MTR_OK;
 }
 
-int mtr_render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_s, const float *g_t,
-                    float *grad_materials, float *grad_emitters)
+// mtr_render_grad (grad_texels == nullptr) and mtr_render_grad_tex
+static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_s, const float *g_t,
+                       float *grad_materials, float *grad_emitters, float *grad_texels)
 {
     if (!s || !p || !g_s || !g_t || !grad_materials || (s->dev.n_ems && !grad_emitters))
         return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_render_grad: NULL argument");
@@ -829,11 +874,15 @@ int mtr_render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_s, 
     const uint32_t n_pixels = p->pixel_end - p->pixel_begin, chunk = p->spp_end - p->spp_begin;
     const uint64_t n_lanes = (uint64_t)n_pixels * chunk;
     size_t lds = 0; bool scene_lds = false;
-    const uint32_t grid = n_lanes ? grad_grid(s->dev, n_lanes, c->n_cu, &lds, &scene_lds) : 0u;
+    const uint32_t n_tx = s->n_texels;
+    const uint32_t tier = grad_texels ? grad_tex_tier(s->dev, n_tx) : MTR_GRAD_TEX_NONE;
+    const uint32_t slab_tx = tier == MTR_GRAD_TEX_SLAB ? n_tx : 0u;
+    const uint32_t grid = n_lanes ? grad_grid(s->dev, n_lanes, c->n_cu, &lds, &scene_lds, slab_tx) : 0u;
     if (n_lanes && grid == 0u) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: the gradient slab and traversal stack exceed LDS");
     if (grid == 0u) {
         HIP_TRY(c, hipMemsetAsync(grad_materials, 0, (size_t)n_m * 3u * sizeof(float), c->stream));
         if (n_e) HIP_TRY(c, hipMemsetAsync(grad_emitters, 0, (size_t)n_e * 3u * sizeof(float), c->stream));
+        if (tier != MTR_GRAD_TEX_NONE) HIP_TRY(c, hipMemsetAsync(grad_texels, 0, (size_t)n_tx * 3u * sizeof(float), c->stream));
         return MTR_OK;
     }
     // the traced emitter table carries unit radiance (a contribution without its radiance factor); the true radiance goes alongside
@@ -842,16 +891,19 @@ int mtr_render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_s, 
     if (n_e) HIP_TRY(c, hipMemcpy(ems.data(), s->dev.ems, n_e * sizeof(Emitter), hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n_e; ++i)
         for (int k = 0; k < 3; ++k) { rad[3u * i + k] = ems[i].radiance[k]; ems[i].radiance[k] = 1.0f; }
-    const size_t partial_b = (size_t)grid * slab_n * sizeof(double);
+    const size_t partial_b = ((size_t)grid * (slab_n + 3u * slab_tx) * sizeof(double) + 255u) & ~(size_t)255u;
     const size_t ems_b = ((size_t)n_e * sizeof(Emitter) + 255u) & ~(size_t)255u;
-    const size_t ws_b = ems_b + ((rad.size() * sizeof(float) + 255u) & ~(size_t)255u) + partial_b;
+    const size_t acc_b = tier == MTR_GRAD_TEX_GLOBAL ? (size_t)n_tx * 3u * sizeof(double) : 0u;      // the global tier's f64 sums
+    const size_t ws_b = ems_b + ((rad.size() * sizeof(float) + 255u) & ~(size_t)255u) + partial_b + acc_b;
     unsigned char *ws = nullptr;
     HIP_TRY(c, hipMalloc((void **)&ws, ws_b));
     Emitter *d_ems = (Emitter *)ws;
     float *d_rad = (float *)(ws + ems_b);
     double *d_partial = (double *)(ws + ems_b + ((rad.size() * sizeof(float) + 255u) & ~(size_t)255u));
+    double *d_acc = acc_b ? (double *)((unsigned char *)d_partial + partial_b) : nullptr;
     hipError_t e = hipSuccess;
-    if (n_e) e = hipMemcpy(d_ems, ems.data(), n_e * sizeof(Emitter), hipMemcpyHostToDevice);
+    if (d_acc) e = hipMemsetAsync(d_acc, 0, acc_b, c->stream);
+    if (n_e && e == hipSuccess) e = hipMemcpy(d_ems, ems.data(), n_e * sizeof(Emitter), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_rad, rad.data(), rad.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const RenderConst rc = make_render_const(*p, f, n_e);
@@ -859,13 +911,25 @@ int mtr_render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_s, 
         gc.g_s = g_s; gc.g_t = g_t; gc.em_radiance = d_rad;
         gc.steady_scale = rc.sample_scale; gc.transient_scale = rc.sample_scale;
         e = launch_grad(s->dev, d_ems, s->cam, f, rc, gc, p->pixel_begin, n_pixels, p->spp_begin, chunk, d_partial, grid, lds,
-                        scene_lds, grad_materials, grad_emitters, c->stream);
+                        scene_lds, grad_materials, grad_emitters, c->stream, tier, n_tx, d_acc, grad_texels);
     }
     const hipError_t e_sync = hipStreamSynchronize(c->stream);
     (void)hipFree(ws);
     HIP_TRY(c, e);
     HIP_TRY(c, e_sync);
     return MTR_OK;
+}
+
+int mtr_render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_s, const float *g_t,
+                    float *grad_materials, float *grad_emitters)
+{
+    return render_grad(s, p, g_s, g_t, grad_materials, grad_emitters, nullptr);
+}
+
+int mtr_render_grad_tex(mtr_scene *s, const mtr_render_params *p, const float *g_s, const float *g_t,
+                        float *grad_materials, float *grad_emitters, float *grad_texels)
+{
+    return render_grad(s, p, g_s, g_t, grad_materials, grad_emitters, grad_texels);
 }
 
 int mtr_counters_reset(mtr_ctx *c)

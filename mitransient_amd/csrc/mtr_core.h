@@ -1936,6 +1936,46 @@ MTR_HD f3 material_albedo(const SceneView &sc, const mtr_material &m, const Hit 
     return texture_eval(sc.texels, sc.tex_info[m.albedo_texture - 1u], u, v);
 }
 
+// The same lookup taken apart for its gradient (mtr_grad.h): the four neighbours of texture_eval as offsets from the texture's
+// first texel (`first`, an index into the scene's texel array) with the filter's weights — the taps weigh w0x w0y, w1x w0y,
+// w0x w1y, w1x w1y — and the texture coordinate of a hit as material_albedo computes it.  Statement for statement the arithmetic
+// of the two functions above, which keep their own text: routed through these helpers their callers compile to other
+// instructions (a different order of the integer remainders), and the primal kernels are to stay bit for bit what they are.
+struct TexTaps { size_t i00, i10, i01, i11; uint32_t first; float w0x, w1x, w0y, w1y; };
+MTR_HD TexTaps texture_taps(q4 info, float u, float v)
+{
+    TexTaps t;
+    const int32_t W = (int32_t)fbits(info.y), H = (int32_t)fbits(info.z);
+    const float fu = fmaf(u, (float)W, -0.5f), fv = fmaf(v, (float)H, -0.5f);
+    const float flu = floorf(fu), flv = floorf(fv);
+    t.w1x = fu - flu; t.w1y = fv - flv; t.w0x = 1.0f - t.w1x; t.w0y = 1.0f - t.w1y;
+    const int32_t ix = (int32_t)flu, iy = (int32_t)flv;
+    int32_t x0 = ix % W, x1 = (ix + 1) % W, y0 = iy % H, y1 = (iy + 1) % H;
+    x0 += x0 < 0 ? W : 0; x1 += x1 < 0 ? W : 0; y0 += y0 < 0 ? H : 0; y1 += y1 < 0 ? H : 0;
+    t.first = fbits(info.x);
+    t.i00 = (size_t)y0 * W + x0; t.i10 = (size_t)y0 * W + x1; t.i01 = (size_t)y1 * W + x0; t.i11 = (size_t)y1 * W + x1;
+    return t;
+}
+MTR_HD f3 texture_eval(const q4 *texels, const TexTaps &k)
+{
+    const float w0x = k.w0x, w1x = k.w1x, w0y = k.w0y, w1y = k.w1y;
+    const q4 *t = texels + k.first;
+    const q4 v00 = t[k.i00], v10 = t[k.i10], v01 = t[k.i01], v11 = t[k.i11];
+    const float r0 = fmaf(w0x, v00.x, w1x * v10.x), r1 = fmaf(w0x, v01.x, w1x * v11.x);
+    const float g0 = fmaf(w0x, v00.y, w1x * v10.y), g1 = fmaf(w0x, v01.y, w1x * v11.y);
+    const float b0 = fmaf(w0x, v00.z, w1x * v10.z), b1 = fmaf(w0x, v01.z, w1x * v11.z);
+    return mk(fmaf(w0y, r0, w1y * r1), fmaf(w0y, g0, w1y * g1), fmaf(w0y, b0, w1y * b1));
+}
+MTR_HD void hit_uv(const SceneView &sc, const Hit &h, float &u, float &v)
+{
+    if (fbits(sc.tshade[h.prim].h[4].w) & kShadeQuadBit) { u = fmaf(h.u, 0.5f, 0.5f); v = fmaf(h.v, 0.5f, 0.5f); }
+    else {
+        const q4 a = sc.uvs[2u * (uint32_t)h.prim], b = sc.uvs[2u * (uint32_t)h.prim + 1u];
+        const float b1 = h.u, b2 = h.v, b0 = 1.0f - b1 - b2;
+        u = fmaf(b.x, b2, fmaf(a.z, b1, a.x * b0)); v = fmaf(b.y, b2, fmaf(a.w, b1, a.y * b0));
+    }
+}
+
 // [mitsuba3: Interaction::offset_p]
 MTR_HD f3 offset_point(f3 sp, f3 sn, f3 dir)
 {

@@ -1,7 +1,9 @@
-// mtr_grad.h — reverse-mode gradients of transient_path (ABI 15, mtr_render_grad): the per-lane arithmetic, shared by the
-// gfx950 kernel (mtr_grad.hip) and the host build of the tests (tests/host_grad.cpp).
+// mtr_grad.h — reverse-mode gradients of transient_path (ABI 15, mtr_render_grad; ABI 16, mtr_render_grad_tex): the per-lane
+// arithmetic, shared by the gfx950 kernel (mtr_grad.hip) and the host builds of the tests (tests/host_grad.cpp,
+// tests/host_grad_tex.cpp).
 //
-// What is differentiated: the constant RGB reflectance of `diffuse` materials and the constant RGB radiance of
+// What is differentiated: the constant RGB reflectance of `diffuse` materials, the texels of a bitmap on a
+// `diffuse` reflectance (through the texel hook below) and the constant RGB radiance of
 // `area` / `angulararea` emitters, for the loss  sum g_s . steady + sum g_t . transient  of the seeded estimator, sampling
 // detached as in the reference's PRB (transientpath.py:284-299, integrators/common.py:325-409): Russian-roulette probabilities,
 // BSDF sampling and emitter sampling are constants.  Each contribution c (an emission or an emitter-sampling term) carries the
@@ -10,6 +12,9 @@
 //   d loss / d a_m = sum_c w_c (.) c (.) n_m(c) / a_m       n_m(c): vertices on m whose BSDF factor is part of c
 //   d loss / d L_e = sum_{c lit by e} w_c (.) c / L_e      computed from c with the radiance left out: the traced emitter table
 //                                                         carries UNIT radiance, c = c_unit (.) L_e
+//   d loss / d t   = sum_{vertices v on a bitmap} w_t(v) R(v) / a(v)   t a texel, a(v) the interpolated colour at the vertex,
+//                                                         w_t(v) the bilinear weight of t in a(v) (texture_taps), R(v) the
+//                                                         remaining sum at v: a(v) is linear in its four taps
 // PATH REPLAY in the time domain: a lane traces its path once to sum A = sum_c w_c (.) c, then again from the same seed,
 // subtracting each term as it is re-emitted; at every diffuse vertex the remaining sum (this vertex's emitter-sampling term and
 // every later term) divided by the vertex's albedo goes to its material.  Nothing per path is kept in memory between the walks.
@@ -41,6 +46,14 @@ struct NullGradSink {
     MTR_HD void splat(uint32_t, uint32_t, uint32_t, float, float, float, float, uint32_t, uint32_t) {}
 };
 
+// The texel hook of grad_walk: tex(i, g) receives g = w_t R / a for the texel at index i of the scene's texel array (all textures
+// in scene order), once per tap — taps that wrap onto one texel (width or height 1) arrive as separate calls and add up.
+// The default does nothing and compiles the texel code out (kOn): callers that pass no hook are what they were.
+struct NoTexelGrad {
+    static constexpr bool kOn = false;
+    MTR_HD void operator()(uint32_t, f3) const {}
+};
+
 // w_c of a contribution of film pixel (fx, fy) at optical path length opl; the bin is the splat's own (film_bin)
 MTR_HD f3 grad_weight(const GradConst &gc, const Film &film, uint32_t fx, uint32_t fy, float opl)
 {
@@ -60,9 +73,10 @@ MTR_HD f3 grad_weight(const GradConst &gc, const Film &film, uint32_t fx, uint32
 // REPLAY = false: returns A = sum_c w_c (.) c.  REPLAY = true: R starts at A; every term is subtracted as it is met, emitter
 // gradients go to acc.add_em(e, w_c (.) c_unit), material gradients to acc.add_mat(m, R / a_m) at each diffuse vertex whose
 // BSDF factor enters the remaining terms.  unwarp: camera_unwarp from bounce 0's own closest hit (as path_bounce).
-template <bool ROUGH, bool REPLAY, class Stack, class Acc>
+// tex: the texel hook (bitmap-textured `diffuse` vertices; extended shading code only: a bitmap implies it).
+template <bool ROUGH, bool REPLAY, class Stack, class Acc, class Tex = NoTexelGrad>
 MTR_HD d3 grad_walk(Path p, const SceneView &sc, const Film &film, const RenderConst &rc, const GradConst &gc, Stack &st,
-                    Acc &acc, d3 R)
+                    Acc &acc, d3 R, Tex tex = Tex())
 {
     NullGradSink ns;
     const bool unwarp = (rc.flags & MTR_FLAG_CAMERA_UNWARP) != 0u;
@@ -101,6 +115,17 @@ MTR_HD d3 grad_walk(Path p, const SceneView &sc, const Film &film, const RenderC
                                        m.a[1] != 0.0f ? (float)(R.y / (double)m.a[1]) : 0.0f,
                                        m.a[2] != 0.0f ? (float)(R.z / (double)m.a[2]) : 0.0f));
             }
+            if (Tex::kOn && ROUGH && m.type == MTR_BSDF_DIFFUSE && m.albedo_texture != 0u && sc.texels) {
+                // a = sum of four taps w_t t: d loss / d a = R / a per channel (0 where a is 0, as above), times w_t to each tap
+                float u, v;
+                hit_uv(sc, h, u, v);
+                const TexTaps k = texture_taps(sc.tex_info[m.albedo_texture - 1u], u, v);
+                const f3 a = pd.has_alb ? pd.alb : texture_eval(sc.texels, k);
+                const f3 g = mk(a.x != 0.0f ? (float)(R.x / (double)a.x) : 0.0f, a.y != 0.0f ? (float)(R.y / (double)a.y) : 0.0f,
+                                a.z != 0.0f ? (float)(R.z / (double)a.z) : 0.0f);
+                tex(k.first + (uint32_t)k.i00, g * (k.w0x * k.w0y)); tex(k.first + (uint32_t)k.i10, g * (k.w1x * k.w0y));
+                tex(k.first + (uint32_t)k.i01, g * (k.w0x * k.w1y)); tex(k.first + (uint32_t)k.i11, g * (k.w1x * k.w1y));
+            }
         }
         bool occluded = false;
         if (pd.has_shadow) occluded = traverse<true>(sc, shadow.o, shadow.d, shadow.tmax, st).prim >= 0;
@@ -124,15 +149,15 @@ MTR_HD d3 grad_walk(Path p, const SceneView &sc, const Film &film, const RenderC
 }
 
 // lane (pixel, s) of the render: identity = RNG identity (lane = pixel * spp_total + s), as every primal organisation
-template <bool ROUGH, class Stack, class Acc>
+template <bool ROUGH, class Stack, class Acc, class Tex = NoTexelGrad>
 MTR_HD void grad_lane(const SceneView &sc, const Camera &cam, const Film &film, const RenderConst &rc, const GradConst &gc,
-                      uint32_t pixel, uint32_t s, Stack &st, Acc &acc)
+                      uint32_t pixel, uint32_t s, Stack &st, Acc &acc, Tex tex = Tex())
 {
     Path p;
     path_begin(p, cam, film, rc, pixel, s);
     const d3 zero = { 0.0, 0.0, 0.0 };
     const d3 A = grad_walk<ROUGH, false>(p, sc, film, rc, gc, st, acc, zero);
-    grad_walk<ROUGH, true>(p, sc, film, rc, gc, st, acc, A);
+    grad_walk<ROUGH, true>(p, sc, film, rc, gc, st, acc, A, tex);
 }
 
 } // namespace mtr

@@ -8,6 +8,12 @@
 //                  stores the slab once to its own row of `partial` — no global atomics on the handful of parameter addresses.
 //   k_grad_reduce  one thread per gradient word: the rows of `partial`, in workgroup order, summed in f64 (f64 throughout: the
 //                  terms of a random upstream gradient cancel, and an f32 slab would lose digits the tests compare).
+// Texel gradients (ABI 16, mtr_render_grad_tex; extended shading code only), in one of two tiers chosen by grad_tex_tier():
+//   slab tier      the texel words extend the LDS slab behind the materials and emitters (k_grad_paths<.., true, kTexSlab>), and
+//                  k_grad_reduce_tex sums the rows: no global atomics, bitwise reproducible.
+//   global tier    bitmaps whose words do not fit: global_atomic_add_f64 into a zeroed (n_texels, 3) f64 buffer
+//                  (k_grad_paths<.., true, kTexGlobal>, zero words skipped), converted to f32 by k_grad_tex_store.
+// A launch without texel gradients runs the kernels it ran before (TEX = kTexNone: no texel code in them).
 #include "mtr_kernels.h"
 #include "mtr_grad.h"
 
@@ -28,6 +34,10 @@ struct GradArgs {
     double *partial;              // [gridDim.x][slab]
     float *grad_mats, *grad_ems;  // k_grad_reduce's outputs
     uint32_t n_rows;              // rows of `partial`
+    // texel gradients (appended: the fields above keep their places in the argument block of the kernels without texel code)
+    uint32_t n_texels;            // texels of all textures (slab tier: 3 more doubles each behind the emitters' words)
+    double *tex_acc;              // global tier: (n_texels, 3) f64, zeroed before the launch
+    float *grad_texels;           // (n_texels, 3) f32: k_grad_reduce_tex's / k_grad_tex_store's output
 };
 
 // LDS slab of the workgroup's gradients
@@ -45,12 +55,38 @@ struct SlabAcc {
     __device__ __forceinline__ void term(uint32_t, uint32_t, float, f3) {}
 };
 
-template <bool SCENE_LDS, bool EXT>
+// the texel hooks of grad_walk (mtr_grad.h)
+struct TexelSlab {                  // slab tier: LDS atomics into the workgroup's slab
+    static constexpr bool kOn = true;
+    double *t;
+    __device__ __forceinline__ void operator()(uint32_t i, f3 g) const
+    {
+        double *p = t + 3u * i;
+        if (g.x != 0.0f) atomicAdd(p, (double)g.x);
+        if (g.y != 0.0f) atomicAdd(p + 1, (double)g.y);
+        if (g.z != 0.0f) atomicAdd(p + 2, (double)g.z);
+    }
+};
+struct TexelGlobal {                // global tier: one no-return global_atomic_add_f64 per non-zero word
+    static constexpr bool kOn = true;
+    double *t;
+    __device__ __forceinline__ void operator()(uint32_t i, f3 g) const
+    {
+        double *p = t + 3u * (size_t)i;
+        if (g.x != 0.0f) atomicAdd(p, (double)g.x);
+        if (g.y != 0.0f) atomicAdd(p + 1, (double)g.y);
+        if (g.z != 0.0f) atomicAdd(p + 2, (double)g.z);
+    }
+};
+enum : int { kTexNone = 0, kTexSlab = 1, kTexGlobal = 2 };
+
+template <bool SCENE_LDS, bool EXT, int TEX = kTexNone>
 __global__ void __launch_bounds__(kBlock) k_grad_paths(const GradArgs a)
 {
+    static_assert(TEX == kTexNone || EXT, "a bitmap implies the extended shading code");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
-    const uint32_t slab_n = 3u * (a.n_mats + a.n_ems);
+    const uint32_t slab_n = 3u * (a.n_mats + a.n_ems) + (TEX == kTexSlab ? 3u * a.n_texels : 0u);
     uint32_t off = 0;
     double *s_slab = (double *)smem; off += al16(slab_n * 8u);
     int32_t *s_stack = (int32_t *)(smem + off); off += a.stack_rows * kBlock * 4u;
@@ -87,7 +123,9 @@ __global__ void __launch_bounds__(kBlock) k_grad_paths(const GradArgs a)
         const uint32_t pixel = a.pixel_begin + (uint32_t)(l / a.spp_chunk);
         const uint32_t s = a.spp_begin + (uint32_t)(l % a.spp_chunk);
         st.reset();
-        grad_lane<EXT>(sv, a.cam, a.film, a.rc, a.gc, pixel, s, st, acc);
+        if constexpr (TEX == kTexSlab) grad_lane<EXT>(sv, a.cam, a.film, a.rc, a.gc, pixel, s, st, acc, TexelSlab{ s_slab + 3u * (a.n_mats + a.n_ems) });
+        else if constexpr (TEX == kTexGlobal) grad_lane<EXT>(sv, a.cam, a.film, a.rc, a.gc, pixel, s, st, acc, TexelGlobal{ a.tex_acc });
+        else grad_lane<EXT>(sv, a.cam, a.film, a.rc, a.gc, pixel, s, st, acc);
     }
     __syncthreads();
     double *row = a.partial + (size_t)blockIdx.x * slab_n;
@@ -105,10 +143,30 @@ __global__ void __launch_bounds__(kBlock) k_grad_reduce(const GradArgs a)
     else a.grad_ems[i - 3u * a.n_mats] = (float)acc;
 }
 
-template <bool SL, bool EXT>
+// slab tier: k_grad_reduce over the slab with its texel words
+__global__ void __launch_bounds__(kBlock) k_grad_reduce_tex(const GradArgs a)
+{
+    const uint32_t n_me = 3u * (a.n_mats + a.n_ems), slab_n = n_me + 3u * a.n_texels;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= slab_n) return;
+    double acc = 0.0;
+    for (uint32_t r = 0; r < a.n_rows; ++r) acc += a.partial[(size_t)r * slab_n + i];
+    if (i < 3u * a.n_mats) a.grad_mats[i] = (float)acc;
+    else if (i < n_me) a.grad_ems[i - 3u * a.n_mats] = (float)acc;
+    else a.grad_texels[i - n_me] = (float)acc;
+}
+
+// global tier: the f64 sums to the f32 output
+__global__ void __launch_bounds__(kBlock) k_grad_tex_store(const GradArgs a)
+{
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < 3u * (size_t)a.n_texels) a.grad_texels[i] = (float)a.tex_acc[i];
+}
+
+template <bool SL, bool EXT, int TEX = kTexNone>
 hipError_t launch_paths(const GradArgs &a, int grid, size_t lds, hipStream_t stream)
 {
-    auto k = k_grad_paths<SL, EXT>;
+    auto k = k_grad_paths<SL, EXT, TEX>;
     hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, stream, a);
@@ -117,9 +175,21 @@ hipError_t launch_paths(const GradArgs &a, int grid, size_t lds, hipStream_t str
 
 } // namespace
 
-uint32_t grad_grid(const SceneDev &sc, uint64_t n_lanes, int n_cu, size_t *lds_out, bool *scene_lds_out)
+uint32_t grad_tex_tier(const SceneDev &sc, uint32_t n_texels)
 {
-    const uint32_t slab_n = 3u * (sc.n_mats + sc.n_ems);
+    if (n_texels == 0u || !sc.has_rough || !sc.texels) return MTR_GRAD_TEX_NONE;
+    if ((uint64_t)n_texels * 24u > kGradTexSlabBytes) return MTR_GRAD_TEX_GLOBAL;
+    // ... and the whole carve-up must still fit (grad_grid's own bound)
+    const uint32_t scene_b = lds_scene_bytes(sc);
+    const bool scene_lds = sc.wnodes != nullptr && scene_b <= 64u * 1024u;
+    const size_t lds = al16((3u * (sc.n_mats + sc.n_ems) + 3u * n_texels) * 8u) + (size_t)wf_stack_rows(sc, scene_lds) * kBlock * 4u +
+                       (scene_lds ? scene_b : 0u);
+    return lds <= 160u * 1024u ? MTR_GRAD_TEX_SLAB : MTR_GRAD_TEX_GLOBAL;
+}
+
+uint32_t grad_grid(const SceneDev &sc, uint64_t n_lanes, int n_cu, size_t *lds_out, bool *scene_lds_out, uint32_t slab_texels)
+{
+    const uint32_t slab_n = 3u * (sc.n_mats + sc.n_ems) + 3u * slab_texels;
     const uint32_t scene_b = lds_scene_bytes(sc);
     const bool scene_lds = sc.wnodes != nullptr && scene_b <= 64u * 1024u;
     const uint32_t rows = wf_stack_rows(sc, scene_lds);
@@ -135,7 +205,8 @@ uint32_t grad_grid(const SceneDev &sc, uint64_t n_lanes, int n_cu, size_t *lds_o
 
 hipError_t launch_grad(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
                        const GradConst &gc, uint32_t pixel_begin, uint32_t n_pixels, uint32_t spp_begin, uint32_t spp_chunk,
-                       double *partial, uint32_t grid, size_t lds, bool scene_lds, float *grad_mats, float *grad_ems, hipStream_t stream)
+                       double *partial, uint32_t grid, size_t lds, bool scene_lds, float *grad_mats, float *grad_ems, hipStream_t stream,
+                       uint32_t tex_tier, uint32_t n_texels, double *tex_acc, float *grad_texels)
 {
     GradArgs a{};
     a.sc = sc; a.ems_unit = ems_unit; a.cam = cam; a.film = film; a.rc = rc; a.gc = gc;
@@ -144,7 +215,25 @@ hipError_t launch_grad(const SceneDev &sc, const Emitter *ems_unit, const Camera
     a.n_mats = sc.n_mats; a.n_ems = sc.n_ems;
     a.stack_rows = wf_stack_rows(sc, scene_lds);
     a.partial = partial; a.grad_mats = grad_mats; a.grad_ems = grad_ems; a.n_rows = grid;
+    a.n_texels = n_texels; a.tex_acc = tex_acc; a.grad_texels = grad_texels;
     const bool ext = sc.has_rough != 0u;
+    if (tex_tier != MTR_GRAD_TEX_NONE) {
+        if (!ext || !grad_texels || (tex_tier == MTR_GRAD_TEX_GLOBAL && !tex_acc)) return hipErrorInvalidValue;
+        hipError_t e;
+        if (tex_tier == MTR_GRAD_TEX_SLAB) {
+            e = scene_lds ? launch_paths<true, true, kTexSlab>(a, (int)grid, lds, stream) : launch_paths<false, true, kTexSlab>(a, (int)grid, lds, stream);
+            if (e != hipSuccess) return e;
+            const uint32_t n = 3u * (sc.n_mats + sc.n_ems + n_texels);
+            hipLaunchKernelGGL(k_grad_reduce_tex, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+            return hipGetLastError();
+        }
+        e = scene_lds ? launch_paths<true, true, kTexGlobal>(a, (int)grid, lds, stream) : launch_paths<false, true, kTexGlobal>(a, (int)grid, lds, stream);
+        if (e != hipSuccess) return e;
+        const uint32_t n_me = 3u * (sc.n_mats + sc.n_ems);
+        hipLaunchKernelGGL(k_grad_reduce, dim3((n_me + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+        hipLaunchKernelGGL(k_grad_tex_store, dim3((uint32_t)((3u * (size_t)n_texels + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+        return hipGetLastError();
+    }
     hipError_t e = scene_lds ? (ext ? launch_paths<true, true>(a, (int)grid, lds, stream) : launch_paths<true, false>(a, (int)grid, lds, stream))
                              : (ext ? launch_paths<false, true>(a, (int)grid, lds, stream) : launch_paths<false, false>(a, (int)grid, lds, stream));
     if (e != hipSuccess) return e;

@@ -196,11 +196,19 @@ hipError_t launch_splat_partitioned(const mtr_splat_soa &s, const Film &film, fl
                                     void *scratch, int n_cu, hipStream_t stream);
 hipError_t launch_develop(const Film &film, const float *t4, float *t3, const float *s4, float *s3, hipStream_t stream);
 
-// mtr_render_grad (mtr_grad.hip): the grid of k_grad_paths (0: its LDS does not fit), then both kernels
+// mtr_render_grad / mtr_render_grad_tex (mtr_grad.hip): the grid of k_grad_paths (0: its LDS does not fit), then the kernels.
+// Texel gradients run in one of two tiers (MTR_GRAD_TEX_*), decided by grad_tex_tier from the scene alone: the texel words join
+// the workgroup's f64 LDS slab when all of them take at most kGradTexSlabBytes (slab_texels of grad_grid = n_texels: the grid keeps
+// its occupancy rule over the larger slab), f64 global atomics into tex_acc otherwise.  8 KiB: a workgroup's share of the 160 KiB
+// when eight are resident is 20 KiB, of which the traversal stack takes 4-16 KiB — a larger texel slab would cost resident
+// workgroups on every scene staged in LDS; the rows of `partial` and k_grad_reduce_tex's pass grow with it as well.
 struct GradConst;
-uint32_t grad_grid(const SceneDev &sc, uint64_t n_lanes, int n_cu, size_t *lds_out, bool *scene_lds_out);
+constexpr uint32_t kGradTexSlabBytes = 8u * 1024u;
+uint32_t grad_tex_tier(const SceneDev &sc, uint32_t n_texels);
+uint32_t grad_grid(const SceneDev &sc, uint64_t n_lanes, int n_cu, size_t *lds_out, bool *scene_lds_out, uint32_t slab_texels = 0u);
 hipError_t launch_grad(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
                        const GradConst &gc, uint32_t pixel_begin, uint32_t n_pixels, uint32_t spp_begin, uint32_t spp_chunk,
-                       double *partial, uint32_t grid, size_t lds, bool scene_lds, float *grad_mats, float *grad_ems, hipStream_t stream);
+                       double *partial, uint32_t grid, size_t lds, bool scene_lds, float *grad_mats, float *grad_ems, hipStream_t stream,
+                       uint32_t tex_tier = 0u, uint32_t n_texels = 0u, double *tex_acc = nullptr, float *grad_texels = nullptr);
 
 } // namespace mtr

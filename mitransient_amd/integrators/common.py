@@ -340,17 +340,31 @@ class TransientADIntegrator:
             raise ValueError("transient_hdr_film with exhaustive_scan: differentiable rendering is not available")
         wanted = [k for k, val in (params or {}).items() if getattr(val, "requires_grad", False)]
         scene.ensure_own_records([k for k in wanted if k in scene.param_keys()], sensor)
-        keys = scene.grad_keys(sensor)
+        keys = dict(scene.grad_keys(sensor))
+        keys.update({k: ("texture", i) for k, i in scene.texture_keys(sensor).items()})
+        seen = {}
         for k, val in (params or {}).items():
-            if getattr(val, "requires_grad", False) and k not in keys:
-                raise ValueError(f"{k}: not a differentiable parameter (the constant reflectance of a diffuse BSDF and the "
-                                 f"constant radiance of an area / angulararea emitter are: {sorted(keys)})")
+            if not getattr(val, "requires_grad", False):
+                continue
+            if k not in keys:
+                raise ValueError(f"{k}: not a differentiable parameter (the constant reflectance of a diffuse BSDF, the texels of a "
+                                 f"bitmap that only diffuse reflectances use and the constant radiance of an area / angulararea "
+                                 f"emitter are: {sorted(keys)})")
+            if keys[k][0] == "texture":
+                if tuple(val.shape) != tuple(scene.data(sensor).textures[keys[k][1]].shape):
+                    raise ValueError(f"{k}: expected texels of shape {tuple(scene.data(sensor).textures[keys[k][1]].shape)}, "
+                                     f"got {tuple(val.shape)}")
+                if keys[k] in seen:
+                    raise ValueError(f"{k} and {seen[keys[k]]} name one bitmap: its gradient is one tensor, differentiate one key")
+                seen[keys[k]] = k
         return keys
 
     def render_backward(self, scene, params, grad_in, sensor=0, seed=0, spp=0):
         """Gradients of  sum g_s . steady + sum g_t . transient  of the seeded estimator (``grad_in = (g_s, g_t)``, the upstream
         gradients of the developed (H, W, 3) / (H, W, T, 3) tensors) with respect to every value of ``params`` that requires grad:
-        ``{key: torch.float32 (3,)}`` on the render device.  Sampling is detached."""
+        ``{key: torch.float32 (3,)}`` — ``(H, W, 3)`` for the texels of a ``.data`` key — on the render device.  Sampling is
+        detached."""
+        import numpy as np
         import torch
         keys = self.check_grad_(scene, sensor, params)
         wanted = [k for k, val in (params or {}).items() if getattr(val, "requires_grad", False)]
@@ -395,18 +409,33 @@ class TransientADIntegrator:
         ge = torch.zeros((n_e, 3), dtype=torch.float32, device=dev)
         pm = torch.empty_like(gm)
         pe = torch.empty_like(ge)
+        # texel gradients only when a `.data` key asks: mtr_render_grad_tex, all textures' texels in scene order
+        textured = any(keys[k][0] == "texture" for k in wanted)
+        if textured:
+            first = np.cumsum([0] + [int(t.shape[0] * t.shape[1]) for t in sd.textures])
+            gx = torch.zeros((int(first[-1]), 3), dtype=torch.float32, device=dev)
+            px = torch.empty_like(gx)
         multi = len(samplers_spps) > 1
         for sampler_i, spp_i in samplers_spps:
             p = self.render_params(film, sampler_i.seed_value(), spp_i if multi else total_spp, 0, spp_i, 0, None,
                                    spp_scale=total_spp if multi else 0)
-            ctx.check(ctx.lib.mtr_render_grad(handle, C.byref(p), C.c_void_p(gs_full.data_ptr()), C.c_void_p(g_t.data_ptr()),
-                                              C.c_void_p(pm.data_ptr()), C.c_void_p(pe.data_ptr())), "mtr_render_grad")
+            if textured:
+                ctx.check(ctx.lib.mtr_render_grad_tex(handle, C.byref(p), C.c_void_p(gs_full.data_ptr()), C.c_void_p(g_t.data_ptr()),
+                                                      C.c_void_p(pm.data_ptr()), C.c_void_p(pe.data_ptr()), C.c_void_p(px.data_ptr())),
+                          "mtr_render_grad_tex")
+                gx += px
+            else:
+                ctx.check(ctx.lib.mtr_render_grad(handle, C.byref(p), C.c_void_p(gs_full.data_ptr()), C.c_void_p(g_t.data_ptr()),
+                                                  C.c_void_p(pm.data_ptr()), C.c_void_p(pe.data_ptr())), "mtr_render_grad")
             gm += pm
             ge += pe
         out = {}
         for k in wanted:
             kind, i = keys[k]
-            out[k] = (gm if kind == "material" else ge)[i].clone()
+            if kind == "texture":
+                out[k] = gx[int(first[i]):int(first[i + 1])].reshape(tuple(sd.textures[i].shape)).clone()
+            else:
+                out[k] = (gm if kind == "material" else ge)[i].clone()
         return out
 
     def to_string(self):

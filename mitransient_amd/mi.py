@@ -143,6 +143,7 @@ class Scene:
         # differentiable parameters (mi.traverse): one material record per key, and the values set through params.update()
         self.own_materials_ = False
         self.param_values_ = {}
+        self.texture_values_ = {}              # {(file, raw): (H, W, 3) f32} texels set through a `.data` key
         from . import integrators as _i, films as _f  # noqa: F401  (registers the plugins)
         from .shapes import Shape
         from .emitters import Projector
@@ -260,6 +261,68 @@ class Scene:
         tables"""
         return self.data(sensor).grad_keys
 
+    def texture_locations_(self):
+        from .scene import texture_locations
+        if self.geometry_ is not None or self.approximate_materials not in (False, None, "textures"):
+            return {}
+        return texture_locations(self.dict_, self.base_dir)
+
+    def texture_param_keys(self):
+        """{key: (H, W, 3) float32}: the texels of the differentiable bitmaps by mitsuba's ``.data`` key — linear RGB, after sRGB
+        decoding unless ``raw`` —, from the dictionary and the bitmap files (nothing is flattened)"""
+        from .scene import load_bitmap_texture
+        out = {}
+        for k, tid in self.texture_locations_().items():
+            if tid not in self.texture_values_:
+                self.texture_values_[tid] = load_bitmap_texture(tid[0], tid[1])
+            out[k] = self.texture_values_[tid].copy()
+        return out
+
+    def texture_keys(self, sensor=0):
+        """{key: index into data().textures}: the bitmaps mtr_render_grad_tex differentiates — every material on them a `diffuse`
+        reflectance.  Keys of BSDFs that name one bitmap file share its index."""
+        return self.data(sensor).texture_keys
+
+    def grad_tex_tier(self, sensor=0):
+        """"none" | "slab" | "global": the tier mtr_render_grad_tex runs for this scene on the current device"""
+        from .runtime import get_context
+        ctx = get_context()
+        t = C.c_uint32(0)
+        ctx.check(ctx.lib.mtr_render_grad_tex_tier(self.gpu_handle(ctx, sensor), C.byref(t)), "mtr_render_grad_tex_tier")
+        return ("none", "slab", "global")[int(t.value)]
+
+    def set_texture_param(self, key, value):
+        """new texels for the bitmap of a ``.data`` key ((H, W, 3), the bitmap's own size): the flattened tables take them
+        — and the mean colour that stands in as the materials' `a` —, the device scenes re-upload that one bitmap
+        (mtr_scene_set_texture); nothing else is rebuilt"""
+        import numpy as np
+        from .scene import texture_mean
+        cur = self.texture_param_keys()
+        if key not in cur:
+            raise KeyError(key)
+        if hasattr(value, "detach"):
+            value = value.detach().cpu().numpy()
+        v = np.ascontiguousarray(value, dtype=np.float32)
+        if v.shape != cur[key].shape:
+            raise ValueError(f"{key}: expected texels of shape {cur[key].shape}, got {v.shape}")
+        tid = self.texture_locations_()[key]
+        self.texture_values_[tid] = v.copy()
+        lib = _cabi.load_library()
+        for skey, sd in self._data.items():
+            if tid not in sd.texture_ids:
+                continue
+            self._apply_params(sd)
+            i = sd.texture_ids[tid]
+            a = np.array([[sd.materials[m].a[c] for c in range(3)] for m in range(max(1, sd.n_materials))], np.float32)
+            r = np.array([[sd.emitters[e].radiance[c] for c in range(3)] for e in range(max(1, sd.n_emitters))], np.float32)
+            for hkey in [h for h in self._handles if h[0] == skey]:
+                h = self._handles[hkey]
+                # (the colour tables follow: `a` of the materials on the bitmap is this layer's own f32 mean)
+                if lib.mtr_scene_set_texture(h, i, C.c_void_p(sd.textures[i].ctypes.data)) != 0 or \
+                        lib.mtr_scene_set_colors(h, C.c_void_p(a.ctypes.data), C.c_void_p(r.ctypes.data)) != 0:
+                    lib.mtr_scene_destroy(self._handles.pop(hkey))
+                    self._nlos_fp.pop(hkey, None)
+
     def ensure_own_records(self, keys, sensor=0):
         """every key of ``keys`` must own its material record: a BSDF dictionary that several shapes share is flattened once per
         shape from then on (only when one of its keys is set or differentiated: other scenes keep their tables as they are)"""
@@ -274,6 +337,18 @@ class Scene:
                 self._drop_handles(key)
 
     def _apply_params(self, sd):
+        import numpy as np
+        from .scene import texture_mean
+        for tid, v in self.texture_values_.items():
+            i = getattr(sd, "texture_ids", {}).get(tid)
+            if i is None or sd.textures[i].shape != v.shape:
+                continue
+            sd.textures[i][...] = v             # in place: descriptors handed out keep pointing at the array
+            mean = texture_mean(sd.textures[i])
+            for m in range(sd.n_materials):
+                if sd.materials[m].albedo_texture == i + 1:
+                    for c in range(3):
+                        sd.materials[m].a[c] = np.float32(mean[c])
         for k, v in self.param_values_.items():
             if k not in sd.grad_keys:
                 continue
@@ -286,6 +361,8 @@ class Scene:
         """a differentiable parameter's new value (3 floats): the flattened tables take it, and the device scenes re-upload their
         material and emitter tables (mtr_scene_set_colors) — no BVH is rebuilt"""
         import numpy as np
+        if key.endswith(".data"):
+            return self.set_texture_param(key, value)
         if key not in self.param_keys():
             raise KeyError(key)
         if hasattr(value, "detach"):
@@ -424,8 +501,9 @@ def render(scene: Scene, params=None, sensor=0, integrator=None, seed=0, seed_gr
         @staticmethod
         def backward(ctx, g_s, g_t):
             g = integ.render_backward(scene, params, grad_in=(g_s, g_t), sensor=sensor, seed=seed_grad, spp=spp_grad)
-            # (a 1-element value stands for the three channels: it receives their sum, on its own device like the 3-vector)
-            return tuple((g[k] if v.numel() == 3 else g[k].sum()).to(dtype=v.dtype, device=v.device).reshape(v.shape)
+            # (a 1-element value stands for the three channels: it receives their sum, on its own device like the 3-vector;
+            # the (H, W, 3) texels of a `.data` key receive their own shape)
+            return tuple((g[k] if v.numel() == g[k].numel() else g[k].sum()).to(dtype=v.dtype, device=v.device).reshape(v.shape)
                          for k, v in grads)
 
     s, t = _Render.apply(*[v for _, v in grads])
@@ -476,6 +554,10 @@ def traverse(obj):
         # mitsuba's keys of the differentiable parameters: <bsdf id>.reflectance.value,
         # <shape id>.bsdf[.brdf_0].reflectance.value, <shape id>.emitter.radiance.value
         for k, v in obj.param_keys().items():
+            objs[k] = (obj, k)
+            scene_keys[k] = v
+        # ... and <bsdf id>.reflectance.data, <shape id>.bsdf[.brdf_0].reflectance.data: the (H, W, 3) texels of a bitmap
+        for k, v in obj.texture_param_keys().items():
             objs[k] = (obj, k)
             scene_keys[k] = v
         for i, s in enumerate(obj.sensors()):

@@ -215,7 +215,7 @@ class _SceneBuilder:
                 self.textures.append(load_bitmap_texture(fn, key[1]))
                 self.texture_cache[key] = len(self.textures) - 1
             m.albedo_texture = self.texture_cache[key] + 1
-            return self.textures[m.albedo_texture - 1].reshape(-1, 3).mean(axis=0).astype(np.float64)
+            return texture_mean(self.textures[m.albedo_texture - 1])
         return _color3(v, what, ab)
 
     def _make_material(self, bd) -> _cabi.mtr_material:
@@ -775,6 +775,9 @@ class SceneData:
         self.tri_uv = None               # (n_tris, 6) f32 corner texture coordinates, or None
         self.tri_normals = None          # (n_tris, 9) f32 corner shading normals (all-zero rows: flat triangle), or None
         self.textures = []               # [(H, W, 3) f32 linear RGB] bitmaps referenced by mtr_material.albedo_texture
+        self.texture_ids = {}            # {(file, raw): index into textures}
+        self.texture_keys = {}           # {mitsuba `.data` key: index into textures} of the differentiable bitmaps
+        self.grad_keys = {}
         self.nlos = None                 # mtr_nlos_desc for the NLOS tier
 
     def desc(self) -> _cabi.mtr_scene_desc:
@@ -1005,6 +1008,9 @@ def flatten_scene(d: Dict[str, Any], film, sensor_dict: Dict[str, Any], base_dir
     sd.shape_names, sd.shape_ranges = b.shape_names, b.shape_ranges
     sd.relay_shape = b.shape_names.index(relay_shape_name) if relay_shape_name is not None else -1
     sd.grad_keys = differentiable_keys(d, b) if geometry is None else {}
+    # bitmaps by file (what params.update() of a `.data` key replaces) and the `.data` keys of the differentiable ones
+    sd.texture_ids = dict(b.texture_cache)
+    sd.texture_keys = differentiable_textures(d, b, base_dir) if geometry is None else {}
     return sd
 
 
@@ -1066,6 +1072,88 @@ def param_locations(d) -> Dict[str, tuple]:
         if k is not None:
             out[k] = ("material", ("ref", rid), _bsdf_value(v))
     return out
+
+
+def _bitmap_id(v, base_dir):
+    """(file, raw) of a `bitmap` dictionary: what _SceneBuilder._albedo caches a texture by"""
+    fn = v.get("filename")
+    if not os.path.isabs(fn):
+        fn = os.path.join(base_dir, fn)
+    return (fn, bool(v.get("raw", False)))
+
+
+def _bsdf_texture_key(bd, prefix):
+    """mitsuba's key of the texels of a bitmap on a `diffuse` reflectance: ``reflectance.data``, ``brdf_0.reflectance.data``
+    through `twosided`, and the bitmap dictionary; (None, None) for anything else"""
+    t = bd.get("type") if isinstance(bd, dict) else None
+    if t == "diffuse":
+        r = bd.get("reflectance", 0.5)
+        if isinstance(r, dict) and r.get("type") == "bitmap":
+            return prefix + "reflectance.data", r
+    if t == "twosided":
+        inner = [v for k, v in bd.items() if isinstance(v, dict) and k != "type"]
+        if len(inner) == 1 and inner[0].get("type") != "ref":
+            return _bsdf_texture_key(inner[0], prefix + "brdf_0.")
+    return None, None
+
+
+def _nonlinear_bitmaps(v, base_dir, out, inside=None):
+    """(file, raw) of every bitmap that colours anything but a `diffuse` reflectance (roughplastic / plastic
+    diffuse_reflectance: the colour enters the BSDF non-linearly), anywhere in the dictionary"""
+    if not isinstance(v, dict):
+        return
+    if v.get("type") == "bitmap" and "filename" in v:
+        if inside != ("diffuse", "reflectance"):
+            out.add(_bitmap_id(v, base_dir))
+        return
+    for k, w in v.items():
+        _nonlinear_bitmaps(w, base_dir, out, (v.get("type"), k))
+
+
+def texture_locations(d, base_dir=".") -> Dict[str, tuple]:
+    """the bitmaps mtr_render_grad_tex differentiates, from the scene dictionary alone, by mitsuba key: {key: (file, raw)}.
+    A bitmap counts only if every BSDF that uses the file is a `diffuse` reflectance; keys of BSDFs that name the
+    same file share one texture."""
+    shapes = {k: v for k, v in d.items() if isinstance(v, dict) and v.get("type") in _GRAD_SHAPE_TYPES}
+    excluded = set()
+    _nonlinear_bitmaps({k: v for k, v in d.items() if isinstance(v, dict)}, base_dir, excluded)
+    refs, out = set(), {}
+    for name, sd in shapes.items():
+        b = _shape_bsdf(sd)
+        if b is not None and b.get("type") == "ref":
+            refs.add(b["id"])
+        elif b is not None:
+            k, bm = _bsdf_texture_key(b, f"{name}.bsdf.")
+            if k is not None:
+                out[k] = _bitmap_id(bm, base_dir)
+    for rid in refs:
+        v = d.get(rid)
+        k, bm = _bsdf_texture_key(v, f"{rid}.") if isinstance(v, dict) else (None, None)
+        if k is not None:
+            out[k] = _bitmap_id(bm, base_dir)
+    return {k: tid for k, tid in out.items() if tid not in excluded}
+
+
+def differentiable_textures(d, b, base_dir) -> Dict[str, int]:
+    """texture_locations resolved to the flattened tables: {key: index into SceneData.textures}; a texture that any material
+    other than a `diffuse` references is left out whatever the dictionary says"""
+    if b.approx not in (False, None, "textures"):
+        return {}
+    users = {}
+    for m in b.materials:
+        if m.albedo_texture:
+            users.setdefault(m.albedo_texture - 1, []).append(m.type)
+    keys = {}
+    for k, tid in texture_locations(d, base_dir).items():
+        i = b.texture_cache.get(tid)
+        if i is not None and users.get(i) and all(t == _cabi.MTR_BSDF_DIFFUSE for t in users[i]):
+            keys[k] = i
+    return keys
+
+
+def texture_mean(t):
+    """the mean colour that stands in as `a` of a material on bitmap ``t`` (_SceneBuilder._albedo's expression)"""
+    return t.reshape(-1, 3).mean(axis=0).astype(np.float64)
 
 
 def _bsdf_value(bd):

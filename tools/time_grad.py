@@ -1,11 +1,13 @@
 """Time mtr_render_grad (integrator.render_backward) against the primal render of the same Cornell box, the fused and the
 wavefront organisation, on cuda:0.  One JSON line per size:
 
-    python tools/time_grad.py [--sizes 256x256x400x64,512x512x1024x1024] [--reps 3]
+    python tools/time_grad.py [--sizes 256x256x400x64,512x512x1024x1024] [--reps 3] [--textures 8x4,256x256]
 
 Size = width x height x temporal_bins x spp (the second default is BASELINE config 2).  The upstream gradients are random; the
 backward pass differentiates every key of mi.traverse (three albedos, one radiance).  Times are medians of wall-clock time
-around a synchronised call, after one warm-up call."""
+around a synchronised call, after one warm-up call.  --textures: per bitmap size W x H, the same box with that bitmap on its back
+wall and floor — the backward pass with the constant keys alone (mtr_render_grad on the textured scene) and with the texels
+as well (mtr_render_grad_tex; the tier it ran is reported)."""
 import argparse
 import json
 import os
@@ -34,6 +36,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="256x256x400x64,512x512x1024x1024")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--textures", default="")
     args = ap.parse_args()
     import torch
     import mitransient_amd as mitr
@@ -61,6 +64,29 @@ def main():
         res["ratio_vs_fused"] = res["grad_ms"] / res["primal_fused_ms"]
         res["ratio_vs_wavefront"] = res["grad_ms"] / res["primal_wavefront_ms"]
         print(json.dumps(res), flush=True)
+        for tex in [t for t in args.textures.split(",") if t]:
+            import tempfile
+            import numpy as np
+            from PIL import Image
+            tw, th = (int(x) for x in tex.split("x"))
+            png = os.path.join(tempfile.mkdtemp(prefix="time_grad_"), "wall.png")
+            Image.fromarray(np.random.default_rng(0).integers(40, 250, (th, tw, 3), dtype=np.uint8)).save(png)
+            d = mitr.cornell_box()
+            d["sensor"]["film"].update(width=W, height=H, temporal_bins=T, start_opl=3.5, bin_width_opl=6.0 / T)
+            d["pattern"] = dict(type="diffuse", reflectance=dict(type="bitmap", filename=png))
+            d["back"]["bsdf"] = d["floor"]["bsdf"] = dict(type="ref", id="pattern")
+            ts = mi.load_dict(d)
+            ti = ts.integrator()
+            q = mi.traverse(ts)
+            for k in ts.grad_keys():
+                q[k] = torch.tensor(q[k], requires_grad=True)
+            r2 = {"size": size, "texture": tex, "tier": ts.grad_tex_tier()}
+            r2["primal_fused_ms"] = timed(lambda: ti.render(ts, spp=spp, seed=0), args.reps)
+            r2["grad_constant_keys_ms"] = timed(lambda: ti.render_backward(ts, q, grad_in=(g_s, g_t), seed=1, spp=spp), args.reps)
+            q["pattern.reflectance.data"] = torch.tensor(q["pattern.reflectance.data"], requires_grad=True)
+            r2["grad_with_texels_ms"] = timed(lambda: ti.render_backward(ts, q, grad_in=(g_s, g_t), seed=1, spp=spp), args.reps)
+            r2["texels_over_constant"] = r2["grad_with_texels_ms"] / r2["grad_constant_keys_ms"]
+            print(json.dumps(r2), flush=True)
         del g_t
 
 
