@@ -41,15 +41,16 @@ struct mtr_ctx {
 };
 
 struct WfWorkspace {            // MTR_MODE_WAVEFRONT buffers, sized for one tile, reused across renders
-    void *planes = nullptr, *q_live = nullptr, *q_ray = nullptr, *q_mat = nullptr, *q_shadow = nullptr, *r_shadow = nullptr, *occ = nullptr, *counts = nullptr, *rec = nullptr, *rec_count = nullptr, *q_zombie = nullptr;
+    void *planes = nullptr, *q_live = nullptr, *q_ray = nullptr, *q_mat = nullptr, *r_shadow = nullptr, *occ = nullptr, *counts = nullptr, *rec = nullptr, *rec_count = nullptr, *q_zombie = nullptr;
     uint32_t n_slots = 0, P = 0, rec_cap = 0, rows = 0;
+    size_t bytes = 0;                    // of the device buffers together (WfBytes::total)
     bool polar = false;                  // `planes` also holds the polarized planes (wf_polar_planes_bytes) behind the ordinary ones
     uint32_t *host_count = nullptr;       // pinned: live counts read back between bounce chunks (two words, alternating)
     hipEvent_t poll_ev[2] = { nullptr, nullptr };     // ... and the events that say a word has landed
     void release()              // the tile's device buffers; the sizes are valid only while every one of them exists
     {
-        n_slots = 0; P = 0; rec_cap = 0; rows = 0; polar = false;
-        for (void **p : { &planes, &q_live, &q_ray, &q_mat, &q_shadow, &r_shadow, &occ, &counts, &rec, &rec_count, &q_zombie })
+        n_slots = 0; P = 0; rec_cap = 0; rows = 0; bytes = 0; polar = false;
+        for (void **p : { &planes, &q_live, &q_ray, &q_mat, &r_shadow, &occ, &counts, &rec, &rec_count, &q_zombie })
             if (*p) { (void)hipFree(*p); *p = nullptr; }
     }
 };
@@ -67,7 +68,6 @@ struct mtr_scene {
     NlosDev nlos;
     std::vector<float> tri_verts;            // host copy (NLOS tables are re-derived when the laser moves)
     std::vector<float> tri_normals;          // ... and the vertex normals (empty without): Mesh::sample_position on hidden meshes
-    float bb_lo[3] = { 0, 0, 0 }, bb_hi[3] = { 0, 0, 0 };   // bounds of the triangles (the grid of the wavefront organisation's trace order)
     uint32_t n_emitters_area = 0;
     bool polar_ok = false;                                   // every material and emitter has a polarized form (mtr_polar.h)
     bool grey_scene = false;                                 // kTrGrey without the NLOS laser (mtr_scene_set_nlos decides with it)
@@ -227,9 +227,6 @@ int mtr_scene_create(mtr_ctx *c, const mtr_scene_desc *d, mtr_scene **out)
     s->dev.bvh_depth = hs.bvh_depth; s->n_leaves = hs.n_leaves;
     s->dev.wide_levels = hs.wide_levels; s->dev.wide4_levels = hs.wide4_levels; s->dev.wide8q_levels = hs.wide8q_levels;
     s->tri_verts.assign(d->tri_verts, d->tri_verts + 9 * (size_t)d->n_tris);
-    for (int k = 0; k < 3; ++k) { s->bb_lo[k] = d->n_tris ? INFINITY : 0.0f; s->bb_hi[k] = d->n_tris ? -INFINITY : 0.0f; }
-    for (size_t i = 0; i < 3 * (size_t)d->n_tris; ++i)
-        for (int k = 0; k < 3; ++k) { const float v = d->tri_verts[3 * i + k]; s->bb_lo[k] = std::min(s->bb_lo[k], v); s->bb_hi[k] = std::max(s->bb_hi[k], v); }
     if (d->tri_normals) s->tri_normals.assign(d->tri_normals, d->tri_normals + 9 * (size_t)d->n_tris);
     s->n_emitters_area = d->n_emitters;
     if (d->nlos) {
@@ -415,26 +412,48 @@ int mtr_scene_traits(const mtr_scene *s, uint32_t *traits)
 } // extern "C"
 
 // ---- MTR_MODE_WAVEFRONT: host loop over tiles and bounces ------------------------------------
+// sizes of a tile's device buffers: what wf_alloc allocates and what wf_render's choice of the tile adds up.  Per slot 317 B
+// (planes 120, live lists 8, their rays 64, material lists 20, zombie lists 8, shadow rays 32, occlusion flag 1, records 64;
+// polarized 461 B: + 80 B of Mueller / Stokes planes, + 64 B of records), the rest per segment or per pixel
+struct WfBytes {
+    size_t planes, q_live, q_ray, q_mat, q_zombie, r_shadow, occ, counts, rec, rec_count;
+    size_t total() const { return planes + q_live + q_ray + q_mat + q_zombie + r_shadow + occ + counts + rec + rec_count; }
+};
+static WfBytes wf_bytes(uint32_t n_slots, uint32_t P, uint32_t n_seg, uint32_t rec_cap, bool polar)
+{
+    WfBytes b;
+    b.planes = wf_planes_bytes(n_slots) + (polar ? wf_polar_planes_bytes(n_slots) : 0);
+    b.q_live = (size_t)2 * n_slots * 4;
+    b.q_ray = (size_t)2 * n_slots * 32;                          // rays of the live lists, in list order
+    b.q_mat = (size_t)kWfKeys * n_slots * 4;
+    b.q_zombie = (size_t)2 * n_slots * 4;                        // paths that ended with an emitter-sampling term parked, per parity
+    b.r_shadow = (size_t)n_slots * 32;
+    b.occ = (size_t)n_slots + (size_t)n_seg * 16u + 16u;         // [n_seg][seg rounded up to 16] occlusion flags in shadow-list order
+    b.counts = ((size_t)n_seg * (7 + kWfKeys) + 16) * 4;         // seg_live[2][n_seg], seg_mat[n_seg][5], seg_shadow[n_seg], live_total + seg_list_n[2] (16 words), seg_list[2][n_seg], seg_zombie[2][n_seg]
+    b.rec = std::max<size_t>(16, (size_t)P * rec_cap * 16);
+    b.rec_count = (size_t)P * 4;
+    return b;
+}
 static int wf_alloc(mtr_scene *s, uint32_t n_slots, uint32_t P, uint32_t n_seg, uint32_t rec_cap, bool polar = false)
 {
     mtr_ctx *c = s->ctx;
     WfWorkspace &w = s->wf;
     if (w.n_slots >= n_slots && w.P >= P && w.rec_cap == rec_cap && w.rows >= n_seg && w.planes && (w.polar || !polar)) return MTR_OK;
     w.release();
-    HIP_TRY(c, hipMalloc(&w.planes, wf_planes_bytes(n_slots) + (polar ? wf_polar_planes_bytes(n_slots) : 0)));
-    HIP_TRY(c, hipMalloc(&w.q_live, (size_t)2 * n_slots * 4));
-    HIP_TRY(c, hipMalloc(&w.q_ray, (size_t)2 * n_slots * 32));                       // rays of the live lists, in list order
-    HIP_TRY(c, hipMalloc(&w.q_mat, (size_t)kWfKeys * n_slots * 4));
-    HIP_TRY(c, hipMalloc(&w.q_shadow, (size_t)2 * n_slots * 2 + 64));                // TRACE ORDER: q_order | q_order_sh, 16 bits per list position (the former shadow-slot list's buffer)
-    HIP_TRY(c, hipMalloc(&w.q_zombie, (size_t)2 * n_slots * 4));                    // paths that ended with an emitter-sampling term parked, per parity
-    HIP_TRY(c, hipMalloc(&w.r_shadow, (size_t)n_slots * 32));
-    HIP_TRY(c, hipMalloc(&w.occ, (size_t)n_slots + (size_t)n_seg * 16u + 16u));       // [n_seg][seg rounded up to 16] occlusion flags in shadow-list order
-    HIP_TRY(c, hipMalloc(&w.counts, ((size_t)n_seg * (7 + kWfKeys) + 16) * 4));     // seg_live[2][n_seg], seg_mat[n_seg][5], seg_shadow[n_seg], live_total + seg_list_n[2] (16 words), seg_list[2][n_seg], seg_zombie[2][n_seg]
-    HIP_TRY(c, hipMalloc(&w.rec, std::max<size_t>(16, (size_t)P * rec_cap * 16)));
-    HIP_TRY(c, hipMalloc(&w.rec_count, (size_t)P * 4));
+    const WfBytes b = wf_bytes(n_slots, P, n_seg, rec_cap, polar);
+    HIP_TRY(c, hipMalloc(&w.planes, b.planes));
+    HIP_TRY(c, hipMalloc(&w.q_live, b.q_live));
+    HIP_TRY(c, hipMalloc(&w.q_ray, b.q_ray));
+    HIP_TRY(c, hipMalloc(&w.q_mat, b.q_mat));
+    HIP_TRY(c, hipMalloc(&w.q_zombie, b.q_zombie));
+    HIP_TRY(c, hipMalloc(&w.r_shadow, b.r_shadow));
+    HIP_TRY(c, hipMalloc(&w.occ, b.occ));
+    HIP_TRY(c, hipMalloc(&w.counts, b.counts));
+    HIP_TRY(c, hipMalloc(&w.rec, b.rec));
+    HIP_TRY(c, hipMalloc(&w.rec_count, b.rec_count));
     if (!w.host_count) HIP_TRY(c, hipHostMalloc((void **)&w.host_count, 64));
     for (hipEvent_t &e : w.poll_ev) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    w.n_slots = n_slots; w.P = P; w.rec_cap = rec_cap; w.rows = n_seg; w.polar = polar;
+    w.n_slots = n_slots; w.P = P; w.rec_cap = rec_cap; w.rows = n_seg; w.bytes = b.total(); w.polar = polar;
     return MTR_OK;
 }
 
@@ -482,7 +501,7 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
     // tile = P pixels x S samples (2^25 slots); segment = G whole pixels (about 4096 slots: with the persistent
     // k_wf_trace a segment is drained once per launch, so longer segments waste less — staircase 1024: 425 ms,
     // 2048: 390, 4096: 360, 8192: 397)
-    // Tile: as many slots as half of the free device memory holds, at most 2^28 (92 GB of workspace at 341 B per slot).  Every
+    // Tile: as many slots as half of the free device memory holds, at most 2^28 (85 GB of workspace at 317 B per slot: wf_bytes).  Every
     // bounce of every tile costs four launches with ~0.1 ms of fixed cost each, and with max_depth 65 most of them run nearly
     // empty: config 5 (2^29 slots) with tiles of 2^25 / 2^26 / 2^27 / 2^28 slots: 2.01 / 1.80 / 1.70 / 1.59 s per render
     // (config 2 in this organisation: 2^22 269 ms, 2^24 174 ms, 2^25 168 ms).
@@ -491,33 +510,32 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
     // 8192 / 12288 / 16384 slots: 97.8 / 81.9 / 79.4 / 77.1 - 79.7 / 77.5 / 80.8 ms, 108 triangles 131.9 / 117.2 / 113.9 / 116.1 / 114.7 /
     // 123.4 ms; rounds 2-4 had 4096: 141 against 169 ms with 8192 then).
     uint32_t kTileSlots = 1u << 28; uint32_t kSegSlots = 8192u;
-    {
-        size_t free_b = 0, total_b = 0;
-        const size_t per_slot = polar ? 488 : 344;                     // planes 128 + queues 52 + rays 96 + records 64 + occlusion 1, rounded up
-                                                                       // (polarized: + 80 B of Mueller / Stokes planes, + 64 B of records)
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            // half of what is free now (the workspace this scene already holds counts as free), and never more than a third of
-            // the device: the caller's allocator (films, all-gather buffers, a second scene) needs room the driver cannot see
-            size_t budget = (free_b + (size_t)s->wf.n_slots * per_slot) / 2;
-            if (budget > total_b / 3) budget = total_b / 3;
-            while (kTileSlots > (1u << 22) && (size_t)kTileSlots * per_slot > budget) kTileSlots >>= 1;
-        } else kTileSlots = 1u << 25;
-    }
-    if (const char *e = mtr::knob("MTR_WF_TILE_LOG2")) kTileSlots = 1u << atoi(e);      // experiments
-    if (const char *e = mtr::knob("MTR_WF_SEG")) kSegSlots = (uint32_t)atoi(e);
+    if (const char *e = mtr::knob("MTR_WF_SEG")) kSegSlots = (uint32_t)atoi(e);      // experiments
     if (kSegSlots > 32768u) kSegSlots = 32768u;          // a segment holds at most 2^16 slots (seg < kSegSlots + S): k_wf_trace packs (list position, slot) into one word
     const uint32_t S = spp_chunk < 4096u ? spp_chunk : 4096u;
     // (at most 1024 pixels per segment: k_wf_shade keeps 20 B of LDS per pixel of its segment — record-list tail, steady sums —
     // and a render of very few samples per pixel would otherwise ask for more LDS than a CU has: 8192 pixels = 164 KB)
     const uint32_t G = std::min<uint32_t>((kSegSlots + S - 1) / S, 1024u);
-    uint32_t P = kTileSlots / S; if (P < G) P = G; if (P > n_pixels) P = n_pixels;
-    const uint32_t n_slots_max = P * S;
-    const uint32_t seg = G * S;
-    const uint32_t n_seg_max = (P + G - 1) / G;      // (of the first attempt; wf_alloc below may settle for a smaller tile)
     // time-bin records: per-pixel lists sized for 4 contributions per path; the rest (and rows that do not
     // fit LDS) fall back to f32 atomics on the film
     const bool rows_fit = (size_t)f.bins * (polar ? 16u : 12u) <= 150u * 1024u;
     const uint32_t rec_cap = rows_fit ? S * (polar ? 8u : 4u) : 0u;        // (polarized: two records per contribution)
+    {
+        size_t free_b = 0, total_b = 0;
+        auto tile_bytes = [&](uint32_t slots) { const uint32_t px = slots / S; return wf_bytes(slots, px, (px + G - 1) / G, rec_cap, polar).total(); };
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            // half of what is free now (the workspace this scene already holds counts as free), and never more than a third of
+            // the device: the caller's allocator (films, all-gather buffers, a second scene) needs room the driver cannot see
+            size_t budget = (free_b + s->wf.bytes) / 2;
+            if (budget > total_b / 3) budget = total_b / 3;
+            while (kTileSlots > (1u << 22) && tile_bytes(kTileSlots) > budget) kTileSlots >>= 1;
+        } else kTileSlots = 1u << 25;
+    }
+    if (const char *e = mtr::knob("MTR_WF_TILE_LOG2")) kTileSlots = 1u << atoi(e);      // experiments
+    uint32_t P = kTileSlots / S; if (P < G) P = G; if (P > n_pixels) P = n_pixels;
+    const uint32_t n_slots_max = P * S;
+    const uint32_t seg = G * S;
+    const uint32_t n_seg_max = (P + G - 1) / G;      // (of the first attempt; wf_alloc below may settle for a smaller tile)
     int rc_ = wf_alloc(s, n_slots_max, P, n_seg_max, rec_cap, polar);
     // out of memory (someone else took it between hipMemGetInfo and here): halve the tile until the workspace fits
     while (rc_ == MTR_ERR_OOM && P > G && (size_t)P * S > (1u << 22)) {
@@ -531,23 +549,10 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
     WfArgs a{};
     a.sc = s->dev; a.cam = s->cam; a.film = f; a.rc = rc;
     a.planes = (float *)w.planes; a.q_live = (uint32_t *)w.q_live; a.q_ray = (float4 *)w.q_ray; a.q_mat = (uint32_t *)w.q_mat;
-    a.q_shadow = nullptr; a.r_shadow = (float4 *)w.r_shadow; a.occ = (uint8_t *)w.occ;
-    // TRACE ORDER (mtr_kernels.h; an EXPERIMENT, off: MTR_WF_SORT=1 / MTR_WF_SORT_SH=1 in the experiments build): rays of the path
-    // tier traced sorted by (origin cell, direction octant); the grid's 5 bits go to the axes along which the scene is longest.
-    // Measured (round 6, config 5 at 256 spp): k_wf_trace 108.2 -> 110.3 ms, render 155.6 -> 160.1 ms; config 2 wavefront 81.4 -> 88.9 ms.
-    a.q_order = nullptr; a.q_order_sh = nullptr;
-    if (!s->nlos.on && mtr::knob("MTR_WF_SORT") && s->tri_verts.size() >= 9) {
-        a.q_order = (uint16_t *)w.q_shadow;
-        if (mtr::knob("MTR_WF_SORT_SH")) a.q_order_sh = (uint16_t *)w.q_shadow + w.n_slots;
-        float ext[3]; uint32_t bits[3] = { 0u, 0u, 0u };
-        for (int k = 0; k < 3; ++k) ext[k] = std::max(s->bb_hi[k] - s->bb_lo[k], 1e-20f);
-        for (int b = 0; b < 5; ++b) {
-            int m = 0;
-            for (int k = 1; k < 3; ++k) if (ext[k] / (float)(1u << bits[k]) > ext[m] / (float)(1u << bits[m])) m = k;
-            bits[m]++;
-        }
-        for (int k = 0; k < 3; ++k) { a.sort_lo[k] = s->bb_lo[k]; a.sort_scale[k] = (float)(1u << bits[k]) / ext[k]; a.sort_bits[k] = bits[k]; }
-    }
+    a.r_shadow = (float4 *)w.r_shadow; a.occ = (uint8_t *)w.occ;
+    // (The rays of a list are traced in list order.  Tracing them sorted by (cell of the origin, octant of the direction) — a counting
+    // sort in k_wf_shade, round 6 — lost: config 5 at 256 spp k_wf_trace 108.2 -> 110.3 ms, render 155.6 -> 160.1 ms; config 2 in this
+    // organisation 81.4 -> 88.9 ms.  That code was removed; it can be read in commit fd0fbb2.)
     a.q_zombie = (uint32_t *)w.q_zombie;
     a.rec = (uint4 *)w.rec; a.rec_count = (uint32_t *)w.rec_count; a.rec_cap = rec_cap;
     a.film_out = t4; a.steady_out = s4; a.counters = c->d_counters; a.log = s->log;

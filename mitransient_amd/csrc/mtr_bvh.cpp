@@ -151,7 +151,7 @@ struct Builder {
         order.push_back((uint32_t)items.size() - 1u);
     }
 
-    // a REFERENCE to a mesh triangle with its own box: a piece of a large triangle (early split clipping / spatial splits, below)
+    // a REFERENCE to a mesh triangle with its own box: a piece of a large triangle (spatial splits, below)
     uint32_t add_reference(uint32_t tri, const Box &b)
     {
         items.push_back(Item{ tri, 1u, kItemTri, -1 }); sbox.push_back(b); wbox.push_back(b);
@@ -585,64 +585,11 @@ void build_bvh(const float *verts, uint32_t n, const BvhPrims *prims, BvhBuild &
         B.add_item(Item{ i, 1u, kItemTri, -1 }, nullptr);
         ++i;
     }
-    // (experiments only — MTR_BVH_ESC — since the builder splits spatially itself, below)
-    // EARLY SPLIT CLIPPING of large mesh triangles (Ernst & Greiner 2007): a wall or floor triangle spanning the room has
-    // a box that overlaps everything below it in the tree; it enters the build as several REFERENCES, each with the box of
-    // the triangle clipped to one cell of a recursive midpoint split.  Intersection is unchanged (a leaf tests the whole
-    // triangle, ties go to the original index, duplicates in one leaf are dropped), only culling gets tighter.
-    // Large scenes only: the scenes staged in LDS are dominated by rectangles and object nodes.
-    if (n >= 1024 && mtr::knob("MTR_BVH_ESC")) {
-        Box scene; scene.reset();
-        for (const Box &b : B.wbox) scene.grow(b);
-        double frac = 1e-4;                                           // staircase (config 5 at 256 spp): off 296, 2e-3 287, 5e-4 290, 1e-4 283, 2e-5 290 ms
-        if (const char *e = mtr::knob("MTR_BVH_SPLIT_FRAC")) frac = atof(e);
-        const float a_max = scene.area() * (float)frac;
-        size_t budget = n / 4;                                        // at most 25 % more references
-        struct Piece { uint32_t item; std::vector<double> poly; };
-        std::vector<Piece> work;
-        for (uint32_t it = 0; it < (uint32_t)B.items.size(); ++it)
-            if (B.items[it].type == kItemTri && B.wbox[it].area() > a_max) {
-                const float *v = verts + 9 * (size_t)B.items[it].first_tri;
-                Piece p; p.item = it; p.poly.assign(v, v + 9);
-                work.push_back(std::move(p));
-            }
-        auto poly_box = [](const std::vector<double> &poly) { return mtr::poly_box((const double (*)[3])poly.data(), (int)(poly.size() / 3)); };
-        auto smaller = [&](const Piece &x, const Piece &y) { return B.wbox[x.item].area() < B.wbox[y.item].area(); };
-        std::make_heap(work.begin(), work.end(), smaller);            // largest piece first
-        while (!work.empty() && budget > 0) {
-            std::pop_heap(work.begin(), work.end(), smaller);
-            Piece cur = std::move(work.back()); work.pop_back();
-            const Box cb = B.wbox[cur.item];
-            if (!(cb.area() > a_max)) continue;
-            int axis = 0;
-            for (int k = 1; k < 3; ++k) if (cb.hi[k] - cb.lo[k] > cb.hi[axis] - cb.lo[axis]) axis = k;
-            const double pos = 0.5 * ((double)cb.lo[axis] + (double)cb.hi[axis]);
-            const int np_ = (int)cur.poly.size() / 3;
-            double in[16][3], lo_p[16][3], hi_p[16][3];
-            if (np_ > 12) continue;
-            for (int k = 0; k < np_; ++k) for (int c = 0; c < 3; ++c) in[k][c] = cur.poly[3 * k + c];
-            const int nl = clip_poly(in, np_, axis, pos, true, lo_p), nh = clip_poly(in, np_, axis, pos, false, hi_p);
-            if (nl < 3 || nh < 3) continue;                            // the plane misses the piece (degenerate): keep it whole
-            Piece a, b2;
-            a.item = cur.item; a.poly.assign(&lo_p[0][0], &lo_p[0][0] + 3 * nl);
-            Box ba = poly_box(a.poly), bb;
-            b2.poly.assign(&hi_p[0][0], &hi_p[0][0] + 3 * nh);
-            bb = poly_box(b2.poly);
-            // never grow beyond the piece being split (clipping can only shrink; the padding must not escape it either)
-            for (int k = 0; k < 3; ++k) { ba.lo[k] = std::max(ba.lo[k], cb.lo[k]); ba.hi[k] = std::min(ba.hi[k], cb.hi[k]); bb.lo[k] = std::max(bb.lo[k], cb.lo[k]); bb.hi[k] = std::min(bb.hi[k], cb.hi[k]); }
-            B.sbox[cur.item] = ba; B.wbox[cur.item] = ba;
-            for (int k = 0; k < 3; ++k) B.cent[3 * (size_t)cur.item + k] = 0.5f * (ba.lo[k] + ba.hi[k]);
-            B.add_reference(B.items[cur.item].first_tri, bb);
-            b2.item = (uint32_t)B.items.size() - 1u;
-            --budget;
-            work.push_back(std::move(a)); std::push_heap(work.begin(), work.end(), smaller);
-            work.push_back(std::move(b2)); std::push_heap(work.begin(), work.end(), smaller);
-        }
-    }
     // SPATIAL SPLITS during the build (the builder's comment; round 5): large scenes walked in HBM only; alpha decides how many
     // references are duplicated, the budget (as many duplicates as triangles) is a bound on memory, not a tuning knob.
-    // Config 5 at 256 spp, k_wf_trace per render: no splits 161 ms, early split clipping (rounds 2-5) 131 ms, spatial splits 113.5 ms
-    // (both together 121 ms: pieces cut before the build take the planes the builder would have chosen).
+    // Config 5 at 256 spp, k_wf_trace per render: no splits 161 ms, early split clipping (Ernst & Greiner 2007: large triangles cut into
+    // references before the build; rounds 2-5) 131 ms, spatial splits 113.5 ms, both together 121 ms — pieces cut before the build take
+    // the planes the builder would have chosen — so the clipping was removed (its code: commit fd0fbb2).
     // (round 6: alpha 3e-7 with room for 2 n duplicates — the parallel build pays for them: staircase build_bvh 0.98 s, 276 k leaves instead of 208 k;
     // alpha 1e-6 / 3e-7 / 1e-7 with leaf target 1: k_wf_trace 101.8 / 100.8 / 99.5 ms at 256 spp, the last at 342 k leaves and 1.2 s)
     long long dup_budget = sbvh ? 2ll * (long long)n : 0;
@@ -671,7 +618,7 @@ void build_bvh(const float *verts, uint32_t n, const BvhPrims *prims, BvhBuild &
     const double t_b2 = now();
     if (mtr::knob("MTR_BVH_VERBOSE")) fprintf(stderr, "build_bvh: top of the tree %.3f s, subtrees + stitching %.3f s\n", t_b1 - t_b0, t_b2 - t_b1);
     if (mtr::knob("MTR_BVH_VERBOSE"))
-        fprintf(stderr, "build_bvh: %u triangles, %zu references before the build (early split clipping), %lld duplicated by spatial splits (budget %lld), %u threads\n",
+        fprintf(stderr, "build_bvh: %u triangles, %zu references before the build, %lld duplicated by spatial splits (budget %lld), %u threads\n",
                 n, n_refs0, dup_budget0 - dup_budget, dup_budget0, B.n_threads);
 
     // flatten: one packet per inner Tmp node

@@ -693,7 +693,7 @@ bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_
     cfg.scene_lds = sc.wnodes != nullptr && scene_b <= 64u * 1024u;
     // the kernel walks a WIDE tree (8-wide in LDS, quantised 4-wide in HBM): one stacked group per level (+ the row the
     // branch-free push writes before it knows whether it counts)
-    const uint32_t rows = (cfg.scene_lds ? sc.wide_levels : (sc.wnodes8q ? sc.wide8q_levels : sc.wide4_levels)) + 1u;
+    const uint32_t rows = wf_stack_rows(sc, cfg.scene_lds);
     args.stack_rows = rows;
     uint32_t fixed_b = (rows + (args.nlos_on ? 0u : LdsStack::kParkRows)) * kBlock * 4 + 64;
     if (cfg.scene_lds) fixed_b += scene_b;
@@ -735,7 +735,7 @@ bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_
     const int reg_cap = (cfg.rough || cfg.fixed || args.nlos_on) ? 3 : (int)MTR_FUSED_MIN_WAVES;
     auto lds_of = [&](uint32_t g) { return (size_t)fixed_b + align16(g * 32) + (cfg.fixed ? align16(g * 16) : 0u) + 2 * align16(g * 4) + (cfg.hist_lds ? (size_t)g * row_bytes : 0) + 16; };
     auto per_cu_of = [&](uint32_t g) { const int p = (int)(kLdsMax / lds_of(g)); return p > reg_cap ? reg_cap : p; };
-    if (cfg.hist_lds && !mtr::knob("MTR_FUSED_OLD_PLAN")) {
+    if (cfg.hist_lds) {
         uint32_t best = G;
         for (uint32_t g = G; g-- > 1u;) if (per_cu_of(g) > per_cu_of(best)) best = g;
         G = best;
@@ -751,7 +751,6 @@ bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_
     // persistent grid: as many workgroups as can be resident, each with at least g_want pixels
     int per_cu = per_cu_of(G);
     if (per_cu < 1) per_cu = 1;
-    if (mtr::knob("MTR_FUSED_OLD_PLAN")) { per_cu = (int)(kLdsMax / cfg.lds_bytes); if (per_cu > 8) per_cu = 8; if (cfg.rough && per_cu > 3) per_cu = 3; }
     if (const char *e = mtr::knob("MTR_FUSED_PER_CU")) { const int v = atoi(e); if (v >= 1 && v < per_cu) per_cu = v; }     // experiments
     if (mtr::knob("MTR_FUSED_VERBOSE")) fprintf(stderr, "fused_plan: G %u, row %u B, lds %zu B, per_cu %d, traits %u, rough %d, fixed %d\n", G, row_bytes, (size_t)cfg.lds_bytes, per_cu, cfg.traits, (int)cfg.rough, (int)cfg.fixed);
     cfg.per_cu = per_cu;

@@ -274,40 +274,6 @@ __device__ __forceinline__ void wave_deposit(float *s_steady, bool has, uint32_t
     }
 }
 
-// TRACE ORDER (WfArgs::q_order): sort key of a ray = (cell of its origin on a 32-cell grid over the scene) << 3 | octant of its direction
-__device__ __forceinline__ uint32_t trace_sort_key(const WfArgs &a, f3 o, f3 d)
-{
-    const uint32_t bx = a.sort_bits[0], by = a.sort_bits[1], bz = a.sort_bits[2];
-    const float cx = fminf(fmaxf((o.x - a.sort_lo[0]) * a.sort_scale[0], 0.0f), (float)((1u << bx) - 1u));
-    const float cy = fminf(fmaxf((o.y - a.sort_lo[1]) * a.sort_scale[1], 0.0f), (float)((1u << by) - 1u));
-    const float cz = fminf(fmaxf((o.z - a.sort_lo[2]) * a.sort_scale[2], 0.0f), (float)((1u << bz) - 1u));
-    const uint32_t cell = (((uint32_t)cx << by) | (uint32_t)cy) << bz | (uint32_t)cz;
-    return (cell << 3) | (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
-}
-// counting sort of the n keys (one byte each, LDS) of a segment's list: order[j] = list position of the j-th ray in key order.
-// Called by the whole workgroup; s_hist: 260 words of LDS.  (Within one key the order is that of the atomics: it only decides which
-// lane traces which ray.)
-__device__ __forceinline__ void trace_sort(const uint8_t *s_keys, uint32_t n, uint32_t *s_hist, uint16_t *order, int tid)
-{
-    s_hist[tid] = 0u;
-    __syncthreads();
-    for (uint32_t i = tid; i < n; i += kBlock) atomicAdd(&s_hist[s_keys[i]], 1u);
-    __syncthreads();
-    const uint32_t c = s_hist[tid];
-    uint32_t incl = c;
-    const uint32_t lane = (uint32_t)tid & 63u;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o); if (lane >= (uint32_t)o) incl += v; }
-    if (lane == 63u) s_hist[256 + (tid >> 6)] = incl;
-    __syncthreads();
-    uint32_t base = 0u;
-    for (int w = 0; w < (tid >> 6); ++w) base += s_hist[256 + w];
-    __syncthreads();
-    s_hist[tid] = base + incl - c;                       // exclusive prefix = the key's cursor
-    __syncthreads();
-    for (uint32_t i = tid; i < n; i += kBlock) order[atomicAdd(&s_hist[s_keys[i]], 1u)] = (uint16_t)i;
-}
-
 // time-bin contribution -> 16-byte record appended to its pixel's list; list full -> f32 atomics to HBM.
 // The list tails of the segment's pixels live in LDS for the duration of the launch.
 struct RecordSink {
@@ -475,7 +441,6 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_TRACE_WAVES_LDS : (
         bool pending = false;                                   // a finished ray whose result is not written yet
         const float4 *qr = any_hit ? a.r_shadow + 2 * (size_t)sg * a.seg
                                    : a.q_ray + 2 * ((size_t)par * a.n_slots + (size_t)sg * a.seg);   // rays in list order
-        const uint16_t *ord = any_hit ? (a.q_order_sh ? a.q_order_sh + (size_t)sg * a.seg : nullptr) : (a.q_order ? a.q_order + (size_t)sg * a.seg : nullptr);
         st.reset();
         for (;;) {
             const bool idle = tr.cur == kTravDone;
@@ -507,8 +472,7 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_TRACE_WAVES_LDS : (
                 base = __shfl(base, leader);
                 const uint32_t idx = base + (uint32_t)__popcll(m_idle & ((1ull << lane_id) - 1ull));
                 if (idle && idx < n_live) {
-                    // TRACE ORDER: the idx-th ray to trace sits at list position ord[idx] (bounce 0's camera rays are coherent as they are)
-                    pos = (!FIRST && ord) ? (uint32_t)ord[idx] : idx;
+                    pos = idx;
                     if (FIRST) {
                         uint32_t pixel, s, pl;
                         slot_to_lane(a, sg * a.seg + idx, pixel, s, pl);
@@ -630,9 +594,6 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_SHADE_WAVES_LDS : M
     wf_setup<STACK, SCENE_LDS>(a.sc, smem, tid, sv, st, off);
     uint32_t *s_rec = (uint32_t *)(smem + off);                 // [G] record-list tails of the segment's pixels
     float *s_steady = (float *)(smem + off + al16(a.G * 4u));   // [G][4] radiance sums of the paths that end here
-    uint8_t *s_sortkey = (uint8_t *)(smem + off + al16(a.G * 4u) + al16(a.G * 16u));      // [seg] TRACE ORDER: keys of the next live list
-    uint8_t *s_sortkey_sh = s_sortkey + al16(a.seg);            // [seg] ... of the shadow list (DEFER)
-    uint32_t *s_hist = (uint32_t *)(s_sortkey_sh + (DEFER ? al16(a.seg) : 0u));           // [260]
     const PlanesT<!SCENE_LDS> P{ (float4 *)a.planes, a.n_slots };
     const uint32_t par = a.parity;
     uint32_t n_closest = 0, n_shadow = 0, n_bounce = 0, n_splats = 0, n_over = 0, n_alive = 0;
@@ -755,7 +716,6 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_SHADE_WAVES_LDS : M
                             // withheld from shade_finish: `occluded` only gates the commit there
                             const uint32_t pos = wave_append(s_shadow_p, true);
                             sh_pos = pos;          // (the occlusion kernel needs no slot: its result goes to the ray's list position)
-                            if (a.q_order_sh) s_sortkey_sh[pos] = (uint8_t)trace_sort_key(a, shadow.o, shadow.d);
                             r_sh[2 * (size_t)pos] = make_float4(shadow.o.x, shadow.o.y, shadow.o.z, shadow.tmax);
                             r_sh[2 * (size_t)pos + 1] = make_float4(shadow.d.x, shadow.d.y, shadow.d.z, 0.0f);
                             P.st(Q_PEND, slot, make_float4(pd.Lr.x, pd.Lr.y, pd.Lr.z, pd.opl));
@@ -782,7 +742,6 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_SHADE_WAVES_LDS : M
                     const uint32_t pos = wave_append(s_next_p, alive);
                     if (alive) {
                         q_next[pos] = (sh_pos << 16) | (slot - sg * a.seg);
-                        if (a.q_order) s_sortkey[pos] = (uint8_t)trace_sort_key(a, ray_o, ray_d);
                         // (.w: not the ray's tmax, which is infinite, but where this vertex's hit record lives — the next vertex's prev_pos)
                         r_next[2 * (size_t)pos] = make_float4(ray_o.x, ray_o.y, ray_o.z, __uint_as_float(e >> 16));
                         r_next[2 * (size_t)pos + 1] = make_float4(ray_d.x, ray_d.y, ray_d.z, ray_eta);
@@ -795,8 +754,6 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_SHADE_WAVES_LDS : M
             }
         }
         __syncthreads();
-        if (a.q_order) trace_sort(s_sortkey, *s_next_p, s_hist, a.q_order + (size_t)sg * a.seg, tid);
-        if (DEFER && a.q_order_sh) { __syncthreads(); trace_sort(s_sortkey_sh, *s_shadow_p, s_hist, a.q_order_sh + (size_t)sg * a.seg, tid); }
         if (tid == 0) { wf_segment_survivors(a, sg, *s_next_p, DEFER ? *s_zombie_p : 0u); if (DEFER) a.seg_shadow[sg] = *s_shadow_p; }
         for (uint32_t t = tid; t < npx; t += kBlock) a.rec_count[pl0 + t] = s_rec[t];
         for (uint32_t t = tid; t < 4 * npx; t += kBlock) {        // this workgroup owns the segment's pixels in this launch
@@ -1334,6 +1291,11 @@ __global__ void __launch_bounds__(kBlock) k_wf_polar_scatter(const WfArgs a)
     }
 }
 
+// LDS of the bounce kernels behind the stack and the staged scene (wf_plan), one size for all of them: the record-list tails and
+// the steady sums of the segment's pixels (k_wf_shade, the NLOS and polarized bounces) and one byte per list position (k_wf_trace:
+// hit material types / occlusion flags)
+uint32_t bounce_lds_tail(const WfArgs &a) { return al16(a.G * 4u) + al16(a.G * 16u) + al16(a.seg); }
+
 template <int STACK, bool SL>
 hipError_t launch_set(const WfArgs &a, WfKernel which, int grid, size_t lds, hipStream_t stream)
 {
@@ -1344,7 +1306,7 @@ hipError_t launch_set(const WfArgs &a, WfKernel which, int grid, size_t lds, hip
             // rays walk the tree together — and flat_walk_device's uniform stages cost them more than the walk: config 2 in this
             // organisation 82.4 -> 87.4 ms with it, measured in round 6; a flat k_wf_trace changed nothing, 82.4 against 81 - 83)
             void (*ks)(const WfArgs) = a.first_bounce ? k_wf_shade<STACK, true, false, kTrCornell, true> : k_wf_shade<STACK, true, false, kTrCornell>;
-            lds += al16(a.G * 4u) + al16(a.G * 16u) + al16(a.seg) + (a.q_order ? 1056u : 0u);       // (+ 260 words: trace_sort's histogram)
+            lds += bounce_lds_tail(a);
             hipError_t e = hipFuncSetAttribute((const void *)ks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL(ks, dim3(grid), dim3(kBlock), lds, stream, a);
@@ -1352,7 +1314,7 @@ hipError_t launch_set(const WfArgs &a, WfKernel which, int grid, size_t lds, hip
         }
     }
     if (which == WfKernel::PolarBounce) {            // polarized bounce: the LDS of k_wf_nlos_bounce (record-list tails, steady sums)
-        lds += al16(a.G * 4u) + al16(a.G * 16u) + al16(a.seg);
+        lds += bounce_lds_tail(a);
         void (*kp)(const WfArgs) = k_wf_polar_bounce<STACK, SL>;
         hipError_t e = hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -1364,8 +1326,7 @@ hipError_t launch_set(const WfArgs &a, WfKernel which, int grid, size_t lds, hip
                             : which == WfKernel::NlosBounce ? (ext ? k_wf_nlos_bounce<STACK, SL, true> : k_wf_nlos_bounce<STACK, SL, false>)
                             : a.first_bounce ? (ext ? k_wf_shade<STACK, SL, true, 0u, true> : k_wf_shade<STACK, SL, false, 0u, true>)
                             : (ext ? k_wf_shade<STACK, SL, true> : k_wf_shade<STACK, SL, false>);
-    lds += al16(a.G * 4u) + al16(a.G * 16u) + al16(a.seg);        // k_wf_shade: record-list tails, steady sums, sort keys of the next live list; k_wf_trace: hit material types
-    if (which == WfKernel::Shade && a.q_order) lds += (SL ? 0u : al16(a.seg)) + 1056u;      // k_wf_shade, TRACE ORDER experiment: + sort keys of the shadow list (scenes in HBM), trace_sort's histogram
+    lds += bounce_lds_tail(a);
     hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, stream, a);
