@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 16
+#define MTR_ABI_VERSION 17
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -439,8 +439,12 @@ int  mtr_render_plan(mtr_scene *, const mtr_render_params *, uint32_t *mode_out,
  * Sampling is detached (Russian-roulette probabilities, BSDF and emitter sampling are constants); a contribution's transient
  * weight is read at its own time bin (film_bin of its optical path length), which departs from the reference's single read at the
  * vertex distance — DESIGN.md §2.  A render split into passes (pixel / sample ranges, spp_scale) has the sum of its passes'
- * gradients.  Only transient_path with an RGB transient_hdr_film: the NLOS tier, a phasor film, an exhaustive_scan film and
- * MTR_FLAG_POLARIZED are MTR_ERR_UNSUPPORTED.  params.mode, n_bands and the film flags are ignored.  Synchronises the stream. */
+ * gradients.  Only an RGB transient_hdr_film: a phasor film, an exhaustive_scan film and MTR_FLAG_POLARIZED are
+ * MTR_ERR_UNSUPPORTED.  params.mode, n_bands and the film flags are ignored.  Synchronises the stream.
+ * (ABI 17) A scene with a NLOS description (transient_nlos_path, Single or Confocal capture; Exhaustive: MTR_ERR_UNSUPPORTED) is
+ * differentiated as well: grad_materials as above (hidden geometry and relay wall), and grad_emitters is (1, 3) and must not be
+ * NULL: d loss / d irradiance of the projector (mtr_nlos_desc.laser_irradiance), the scene's one emitter.  The scene's tables must
+ * fit LDS (every NLOS scene mtr_render runs in the fused organisation does), else MTR_ERR_UNSUPPORTED. */
 int  mtr_render_grad(mtr_scene *, const mtr_render_params *params,
                      const float *grad_steady_hw3, const float *grad_transient_hwt3,
                      float *grad_materials, float *grad_emitters);
@@ -456,7 +460,8 @@ int  mtr_render_grad(mtr_scene *, const mtr_render_params *params,
  * diffuse materials' part alone and is no parameter (the Python layer gives it no key).  grad_materials of textured materials stay 0.
  * The sums are f64 in one of two tiers (mtr_render_grad_tex_tier): in the workgroups' LDS slabs when all texel words fit beside
  * the material / emitter words (bitwise reproducible), by f64 global atomics otherwise (the f32 result can differ in its last
- * bit from run to run: arrival order). */
+ * bit from run to run: arrival order).
+ * (ABI 17) On a NLOS scene a non-NULL grad_texels is MTR_ERR_UNSUPPORTED: texel gradients are for transient_path. */
 int  mtr_render_grad_tex(mtr_scene *, const mtr_render_params *params,
                          const float *grad_steady_hw3, const float *grad_transient_hwt3,
                          float *grad_materials, float *grad_emitters, float *grad_texels);

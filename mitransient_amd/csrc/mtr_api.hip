@@ -866,24 +866,35 @@ int mtr_render_plan(mtr_scene *s, const mtr_render_params *p, uint32_t *mode_out
 static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_s, const float *g_t,
                        float *grad_materials, float *grad_emitters, float *grad_texels)
 {
-    if (!s || !p || !g_s || !g_t || !grad_materials || (s->dev.n_ems && !grad_emitters))
+    if (!s || !p || !g_s || !g_t || !grad_materials || ((s->dev.n_ems || s->nlos.on) && !grad_emitters))
         return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_render_grad: NULL argument");
     mtr_ctx *c = s->ctx;
     const Film &f = s->film;
     if (int r = check_render_ranges(c, f, p, "mtr_render_grad", "render in passes")) return r;
-    if (s->nlos.on || f.n_freq || f.lasers > 1u || (p->flags & MTR_FLAG_POLARIZED))
-        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: transient_path with a plain transient_hdr_film (RGB) only: "
-                                            "no NLOS tier, phasor film, exhaustive_scan or polarized transport");
+    if (f.n_freq || f.lasers > 1u || (p->flags & MTR_FLAG_POLARIZED))
+        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: a plain transient_hdr_film (RGB) only: "
+                                            "no phasor film, exhaustive_scan or polarized transport");
+    const bool nlos = s->nlos.on;
+    if (nlos) {
+        if (s->nlos.k.capture_type == MTR_CAPTURE_EXHAUSTIVE)
+            return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: the NLOS tier with a Single or Confocal capture only (no Exhaustive capture)");
+        if (grad_texels) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad_tex: texel gradients are for transient_path only (not the NLOS tier)");
+        if (s->nlos.k.film_w != f.width || s->nlos.k.film_h != f.height)
+            return fail(c, MTR_ERR_INVALID, "mtr_render_grad: film size changed after mtr_scene_set_nlos; call it again");
+    }
     HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t n_m = s->dev.n_mats, n_e = s->dev.n_ems, slab_n = 3u * (n_m + n_e);
+    // (the NLOS tier: the laser is the one "emitter" of the gradient; the scene's emitter table is empty)
+    const uint32_t n_m = s->dev.n_mats, n_e = nlos ? 1u : s->dev.n_ems, slab_n = 3u * (n_m + n_e);
     const uint32_t n_pixels = p->pixel_end - p->pixel_begin, chunk = p->spp_end - p->spp_begin;
     const uint64_t n_lanes = (uint64_t)n_pixels * chunk;
     size_t lds = 0; bool scene_lds = false;
     const uint32_t n_tx = s->n_texels;
     const uint32_t tier = grad_texels ? grad_tex_tier(s->dev, n_tx) : MTR_GRAD_TEX_NONE;
     const uint32_t slab_tx = tier == MTR_GRAD_TEX_SLAB ? n_tx : 0u;
-    const uint32_t grid = n_lanes ? grad_grid(s->dev, n_lanes, c->n_cu, &lds, &scene_lds, slab_tx) : 0u;
-    if (n_lanes && grid == 0u) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: the gradient slab and traversal stack exceed LDS");
+    const uint32_t grid = n_lanes ? grad_grid(s->dev, n_lanes, c->n_cu, &lds, &scene_lds, slab_tx, nlos) : 0u;
+    if (n_lanes && grid == 0u)
+        return fail(c, MTR_ERR_UNSUPPORTED, nlos ? "mtr_render_grad: the NLOS tier needs a scene whose tables, gradient slab and traversal stack fit LDS"
+                                                 : "mtr_render_grad: the gradient slab and traversal stack exceed LDS");
     if (grid == 0u) {
         HIP_TRY(c, hipMemsetAsync(grad_materials, 0, (size_t)n_m * 3u * sizeof(float), c->stream));
         if (n_e) HIP_TRY(c, hipMemsetAsync(grad_emitters, 0, (size_t)n_e * 3u * sizeof(float), c->stream));
@@ -891,13 +902,20 @@ static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_
         return MTR_OK;
     }
     // the traced emitter table carries unit radiance (a contribution without its radiance factor); the true radiance goes alongside
-    std::vector<Emitter> ems(n_e);
+    // (the NLOS tier: the walk runs with unit irradiance, and the laser's true irradiance is the one entry of `rad`)
+    std::vector<Emitter> ems(nlos ? 0u : n_e);
     std::vector<float> rad(3u * (size_t)n_e + 3u, 0.0f);
-    if (n_e) HIP_TRY(c, hipMemcpy(ems.data(), s->dev.ems, n_e * sizeof(Emitter), hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n_e; ++i)
+    NlosConst nlos_unit{};
+    if (nlos) {
+        nlos_unit = s->nlos.k;
+        rad[0] = nlos_unit.l_irr.x; rad[1] = nlos_unit.l_irr.y; rad[2] = nlos_unit.l_irr.z;
+        nlos_unit.l_irr = mk(1, 1, 1);
+    }
+    if (!ems.empty()) HIP_TRY(c, hipMemcpy(ems.data(), s->dev.ems, n_e * sizeof(Emitter), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ems.size(); ++i)
         for (int k = 0; k < 3; ++k) { rad[3u * i + k] = ems[i].radiance[k]; ems[i].radiance[k] = 1.0f; }
     const size_t partial_b = ((size_t)grid * (slab_n + 3u * slab_tx) * sizeof(double) + 255u) & ~(size_t)255u;
-    const size_t ems_b = ((size_t)n_e * sizeof(Emitter) + 255u) & ~(size_t)255u;
+    const size_t ems_b = ((size_t)ems.size() * sizeof(Emitter) + 255u) & ~(size_t)255u;
     const size_t acc_b = tier == MTR_GRAD_TEX_GLOBAL ? (size_t)n_tx * 3u * sizeof(double) : 0u;      // the global tier's f64 sums
     const size_t ws_b = ems_b + ((rad.size() * sizeof(float) + 255u) & ~(size_t)255u) + partial_b + acc_b;
     unsigned char *ws = nullptr;
@@ -908,15 +926,15 @@ static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_
     double *d_acc = acc_b ? (double *)((unsigned char *)d_partial + partial_b) : nullptr;
     hipError_t e = hipSuccess;
     if (d_acc) e = hipMemsetAsync(d_acc, 0, acc_b, c->stream);
-    if (n_e && e == hipSuccess) e = hipMemcpy(d_ems, ems.data(), n_e * sizeof(Emitter), hipMemcpyHostToDevice);
+    if (!ems.empty() && e == hipSuccess) e = hipMemcpy(d_ems, ems.data(), ems.size() * sizeof(Emitter), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_rad, rad.data(), rad.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        const RenderConst rc = make_render_const(*p, f, n_e);
+        const RenderConst rc = make_render_const(*p, f, s->dev.n_ems);
         GradConst gc;
         gc.g_s = g_s; gc.g_t = g_t; gc.em_radiance = d_rad;
         gc.steady_scale = rc.sample_scale; gc.transient_scale = rc.sample_scale;
         e = launch_grad(s->dev, d_ems, s->cam, f, rc, gc, p->pixel_begin, n_pixels, p->spp_begin, chunk, d_partial, grid, lds,
-                        scene_lds, grad_materials, grad_emitters, c->stream, tier, n_tx, d_acc, grad_texels);
+                        scene_lds, grad_materials, grad_emitters, c->stream, tier, n_tx, d_acc, grad_texels, nlos ? &nlos_unit : nullptr);
     }
     const hipError_t e_sync = hipStreamSynchronize(c->stream);
     (void)hipFree(ws);

@@ -18,8 +18,16 @@
 // PATH REPLAY in the time domain: a lane traces its path once to sum A = sum_c w_c (.) c, then again from the same seed,
 // subtracting each term as it is re-emitted; at every diffuse vertex the remaining sum (this vertex's emitter-sampling term and
 // every later term) divided by the vertex's albedo goes to its material.  Nothing per path is kept in memory between the walks.
+//
+// transient_nlos_path (ABI 17): the same replay over nlos_bounce (mtr_nlos.h), grad_nlos_walk below.  A term is one
+// emitter_nee_sample splat  Lr = beta (.) bsdf(c) [(.) bsdf(c2) / pdf_ls] (.) w_projector  (transientnlospath.py:432-564): its albedo
+// factors are the vertices whose weight is in beta, c itself and — with laser sampling — the laser spot c2; its irradiance factor
+// is the projector's `irradiance` (the walk runs with UNIT irradiance, the true one goes alongside as the one "emitter").  Every
+// diffuse vertex receives R / a as above; c2's material receives its own term over its albedo.  Detached as well: the laser-target
+// and hidden-geometry sampling, the method coin and the dr.epsilon cut-offs (:539-540).
 #pragma once
 #include "mtr_core.h"
+#include "mtr_nlos.h"
 
 namespace mtr {
 
@@ -158,6 +166,71 @@ MTR_HD void grad_lane(const SceneView &sc, const Camera &cam, const Film &film, 
     const d3 zero = { 0.0, 0.0, 0.0 };
     const d3 A = grad_walk<ROUGH, false>(p, sc, film, rc, gc, st, acc, zero);
     grad_walk<ROUGH, true>(p, sc, film, rc, gc, st, acc, A, tex);
+}
+
+// d loss / d a of a `diffuse` material with a constant reflectance from the sum r its factor is part of: r / a per channel, 0 for
+// a zero channel (never NaN) and for any other material
+MTR_HD bool grad_over_albedo(const mtr_material &m, double rx, double ry, double rz, f3 &g)
+{
+    if (m.type != MTR_BSDF_DIFFUSE || m.albedo_texture != 0u) return false;
+    g = mk(m.a[0] != 0.0f ? (float)(rx / (double)m.a[0]) : 0.0f, m.a[1] != 0.0f ? (float)(ry / (double)m.a[1]) : 0.0f,
+           m.a[2] != 0.0f ? (float)(rz / (double)m.a[2]) : 0.0f);
+    return true;
+}
+
+// nlos_bounce's hook (mtr_nlos.h: NoNlosHook) of the replay.  replay false: *R gathers A = sum_c w_c (.) c.  replay true: *R starts at
+// A; a vertex whose BSDF factor enters its own term and every later one receives R / a, a term is subtracted as it is met, the
+// laser spot's material receives the term over its albedo and the laser (emitter 0) the term without its irradiance.
+template <class Acc>
+struct NlosGradHook {
+    static constexpr bool kOn = true;
+    const SceneView *sc; const Film *film; const GradConst *gc; Acc *acc; d3 *R;
+    uint32_t fx, fy; bool replay;
+    MTR_HD void vertex(uint32_t m, bool active_next) const
+    {
+        if (!replay) return;
+        acc->vertex(m, 0.0f, active_next);
+        f3 g;
+        if (active_next && grad_over_albedo(sc->mats[m], R->x, R->y, R->z, g)) acc->add_mat(m, g);
+    }
+    MTR_HD void term(f3 cu, float opl, uint32_t m, bool at_laser_spot) const
+    {
+        const float *L = gc->em_radiance;
+        const f3 w = grad_weight(*gc, *film, fx, fy, opl);
+        const double cx = (double)w.x * (double)(cu.x * L[0]), cy = (double)w.y * (double)(cu.y * L[1]),
+                     cz = (double)w.z * (double)(cu.z * L[2]);
+        if (!replay) { R->x += cx; R->y += cy; R->z += cz; return; }
+        f3 g;
+        if (at_laser_spot && grad_over_albedo(sc->mats[m], cx, cy, cz, g)) acc->add_mat(m, g);
+        R->x -= cx; R->y -= cy; R->z -= cz;
+        acc->add_em(0u, mk(w.x * cu.x, w.y * cu.y, w.z * cu.z));
+        acc->term(1u, m, opl, cu);
+    }
+};
+
+// One walk of a lane's NLOS path (TransientNLOSPath.sample, :740-918, through nlos_bounce): `replay` as REPLAY of grad_walk.
+// nc carries unit irradiance; reload: nlos_bounce's (a kernel re-reads nc / film / rc after every traversal).
+template <bool EXT, class Stack, class Acc, class Reload = NoReload>
+MTR_HD d3 grad_nlos_walk(Path p, bool replay, const SceneView &sc, const NlosConst &nc, const Film &film, const RenderConst &rc,
+                         const GradConst &gc, Stack &st, Acc &acc, d3 R, const Reload &reload = Reload())
+{
+    NullGradSink ns;
+    BounceStats bs{ 0u, 0u };
+    const NlosGradHook<Acc> hook{ &sc, &film, &gc, &acc, &R, p.px - film.crop_x, p.py - film.crop_y, replay };
+    bool alive = true;
+    while (alive) alive = nlos_bounce<EXT, 0u>(p, sc, nc, film, rc, st, ns, bs, reload, hook);
+    return R;
+}
+
+// lane (pixel, s) of a NLOS render: both walks through ONE copy of the loop (four traversals per bounce are inlined in it)
+template <bool EXT, class Stack, class Acc, class Reload = NoReload>
+MTR_HD void grad_nlos_lane(const SceneView &sc, const NlosConst &nc, const Film &film, const RenderConst &rc, const GradConst &gc,
+                           uint32_t pixel, uint32_t s, Stack &st, Acc &acc, const Reload &reload = Reload())
+{
+    Path p;
+    nlos_begin(p, nc, film, rc, pixel, s);
+    d3 R = { 0.0, 0.0, 0.0 };
+    for (int pass = 0; pass < 2; ++pass) R = grad_nlos_walk<EXT>(p, pass != 0, sc, nc, film, rc, gc, st, acc, R, reload);
 }
 
 } // namespace mtr

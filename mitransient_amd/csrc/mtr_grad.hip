@@ -14,46 +14,20 @@
 //   global tier    bitmaps whose words do not fit: global_atomic_add_f64 into a zeroed (n_texels, 3) f64 buffer
 //                  (k_grad_paths<.., true, kTexGlobal>, zero words skipped), converted to f32 by k_grad_tex_store.
 // A launch without texel gradients runs the kernels it ran before (TEX = kTexNone: no texel code in them).
+// The NLOS tier (ABI 17; mtr_grad_nlos.hip, a translation unit of its own so that the kernels here keep their instructions):
+// k_grad_paths_nlos<EXT> walks grad_nlos_lane over the scene staged in LDS (every NLOS scene
+// the project runs fits; one that does not is refused).  The laser is the slab's one "emitter": its three words sit behind the
+// materials', and k_grad_reduce stores them to grad_emitters[0].  The ~110 dwords of NlosConst are re-read from the kernarg segment
+// after every traversal (kernarg_copy, as k_fused<NLOS> does) instead of living in scalar registers through four walks per bounce.
 #include "mtr_kernels.h"
 #include "mtr_grad.h"
+#include "mtr_grad_args.h"
 
 #include <hip/hip_runtime.h>
 
 namespace mtr {
 
 namespace {
-
-struct GradArgs {
-    SceneDev sc;
-    const Emitter *ems_unit;      // the scene's emitter table with unit radiance
-    Camera cam; Film film; RenderConst rc; GradConst gc;
-    uint32_t pixel_begin, spp_begin, spp_chunk;
-    uint64_t n_lanes;
-    uint32_t n_mats, n_ems;       // slab: materials first, then emitters, 3 doubles each
-    uint32_t stack_rows;
-    double *partial;              // [gridDim.x][slab]
-    float *grad_mats, *grad_ems;  // k_grad_reduce's outputs
-    uint32_t n_rows;              // rows of `partial`
-    // texel gradients (appended: the fields above keep their places in the argument block of the kernels without texel code)
-    uint32_t n_texels;            // texels of all textures (slab tier: 3 more doubles each behind the emitters' words)
-    double *tex_acc;              // global tier: (n_texels, 3) f64, zeroed before the launch
-    float *grad_texels;           // (n_texels, 3) f32: k_grad_reduce_tex's / k_grad_tex_store's output
-};
-
-// LDS slab of the workgroup's gradients
-struct SlabAcc {
-    double *slab; uint32_t n_mats;
-    __device__ __forceinline__ void add3(double *p, f3 g)
-    {
-        if (g.x != 0.0f) atomicAdd(p, (double)g.x);
-        if (g.y != 0.0f) atomicAdd(p + 1, (double)g.y);
-        if (g.z != 0.0f) atomicAdd(p + 2, (double)g.z);
-    }
-    __device__ __forceinline__ void add_mat(uint32_t m, f3 g) { add3(slab + 3u * m, g); }
-    __device__ __forceinline__ void add_em(uint32_t e, f3 g) { add3(slab + 3u * (n_mats + e), g); }
-    __device__ __forceinline__ void vertex(uint32_t, float, bool) {}
-    __device__ __forceinline__ void term(uint32_t, uint32_t, float, f3) {}
-};
 
 // the texel hooks of grad_walk (mtr_grad.h)
 struct TexelSlab {                  // slab tier: LDS atomics into the workgroup's slab
@@ -187,17 +161,18 @@ uint32_t grad_tex_tier(const SceneDev &sc, uint32_t n_texels)
     return lds <= 160u * 1024u ? MTR_GRAD_TEX_SLAB : MTR_GRAD_TEX_GLOBAL;
 }
 
-uint32_t grad_grid(const SceneDev &sc, uint64_t n_lanes, int n_cu, size_t *lds_out, bool *scene_lds_out, uint32_t slab_texels)
+uint32_t grad_grid(const SceneDev &sc, uint64_t n_lanes, int n_cu, size_t *lds_out, bool *scene_lds_out, uint32_t slab_texels, bool nlos)
 {
-    const uint32_t slab_n = 3u * (sc.n_mats + sc.n_ems) + 3u * slab_texels;
+    const uint32_t slab_n = 3u * (sc.n_mats + (nlos ? 1u : sc.n_ems)) + 3u * slab_texels;
     const uint32_t scene_b = lds_scene_bytes(sc);
     const bool scene_lds = sc.wnodes != nullptr && scene_b <= 64u * 1024u;
     const uint32_t rows = wf_stack_rows(sc, scene_lds);
     const size_t lds = al16(slab_n * 8u) + (size_t)rows * kBlock * 4u + (scene_lds ? scene_b : 0u);
     *lds_out = lds; *scene_lds_out = scene_lds;
-    if (lds > 160u * 1024u) return 0u;
+    if (lds > 160u * 1024u || (nlos && !scene_lds)) return 0u;
     uint32_t per_cu = (uint32_t)((160u * 1024u) / lds);
-    if (per_cu > 8u) per_cu = 8u;
+    const uint32_t most = nlos ? (uint32_t)kGradNlosPerCu : 8u;
+    if (per_cu > most) per_cu = most;
     const uint64_t want = (n_lanes + kBlock - 1) / kBlock;
     const uint64_t cap = (uint64_t)n_cu * per_cu;
     return (uint32_t)(want < cap ? want : cap);
@@ -206,7 +181,7 @@ uint32_t grad_grid(const SceneDev &sc, uint64_t n_lanes, int n_cu, size_t *lds_o
 hipError_t launch_grad(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
                        const GradConst &gc, uint32_t pixel_begin, uint32_t n_pixels, uint32_t spp_begin, uint32_t spp_chunk,
                        double *partial, uint32_t grid, size_t lds, bool scene_lds, float *grad_mats, float *grad_ems, hipStream_t stream,
-                       uint32_t tex_tier, uint32_t n_texels, double *tex_acc, float *grad_texels)
+                       uint32_t tex_tier, uint32_t n_texels, double *tex_acc, float *grad_texels, const NlosConst *nlos_unit)
 {
     GradArgs a{};
     a.sc = sc; a.ems_unit = ems_unit; a.cam = cam; a.film = film; a.rc = rc; a.gc = gc;
@@ -217,6 +192,15 @@ hipError_t launch_grad(const SceneDev &sc, const Emitter *ems_unit, const Camera
     a.partial = partial; a.grad_mats = grad_mats; a.grad_ems = grad_ems; a.n_rows = grid;
     a.n_texels = n_texels; a.tex_acc = tex_acc; a.grad_texels = grad_texels;
     const bool ext = sc.has_rough != 0u;
+    if (nlos_unit) {
+        if (tex_tier != MTR_GRAD_TEX_NONE || !scene_lds) return hipErrorInvalidValue;
+        a.n_ems = 1u;                                   // the laser
+        hipError_t e = launch_grad_paths_nlos(a, *nlos_unit, ext, (int)grid, lds, stream);
+        if (e != hipSuccess) return e;
+        const uint32_t slab_n = 3u * (sc.n_mats + 1u);
+        hipLaunchKernelGGL(k_grad_reduce, dim3((slab_n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+        return hipGetLastError();
+    }
     if (tex_tier != MTR_GRAD_TEX_NONE) {
         if (!ext || !grad_texels || (tex_tier == MTR_GRAD_TEX_GLOBAL && !tex_acc)) return hipErrorInvalidValue;
         hipError_t e;

@@ -1,0 +1,51 @@
+// mtr_grad_args.h — the argument block and the LDS slab of the gradient kernels (mtr_grad.hip, mtr_grad_nlos.hip)
+#pragma once
+#include "mtr_kernels.h"
+#include "mtr_grad.h"
+
+#include <hip/hip_runtime.h>
+
+namespace mtr {
+
+struct GradArgs {
+    SceneDev sc;
+    const Emitter *ems_unit;      // the scene's emitter table with unit radiance
+    Camera cam; Film film; RenderConst rc; GradConst gc;
+    uint32_t pixel_begin, spp_begin, spp_chunk;
+    uint64_t n_lanes;
+    uint32_t n_mats, n_ems;       // slab: materials first, then emitters, 3 doubles each
+    uint32_t stack_rows;
+    double *partial;              // [gridDim.x][slab]
+    float *grad_mats, *grad_ems;  // k_grad_reduce's outputs
+    uint32_t n_rows;              // rows of `partial`
+    // texel gradients (appended: the fields above keep their places in the argument block of the kernels without texel code)
+    uint32_t n_texels;            // texels of all textures (slab tier: 3 more doubles each behind the emitters' words)
+    double *tex_acc;              // global tier: (n_texels, 3) f64, zeroed before the launch
+    float *grad_texels;           // (n_texels, 3) f32: k_grad_reduce_tex's / k_grad_tex_store's output
+};
+
+// ... and the NLOS tier's constants behind them (kernarg_copy reads them by offset)
+struct GradNlosArgs {
+    GradArgs g;
+    NlosConst nlos;               // with unit irradiance: gc.em_radiance points at the true one
+};
+
+// LDS slab of the workgroup's gradients
+struct SlabAcc {
+    double *slab; uint32_t n_mats;
+    __device__ __forceinline__ void add3(double *p, f3 g)
+    {
+        if (g.x != 0.0f) atomicAdd(p, (double)g.x);
+        if (g.y != 0.0f) atomicAdd(p + 1, (double)g.y);
+        if (g.z != 0.0f) atomicAdd(p + 2, (double)g.z);
+    }
+    __device__ __forceinline__ void add_mat(uint32_t m, f3 g) { add3(slab + 3u * m, g); }
+    __device__ __forceinline__ void add_em(uint32_t e, f3 g) { add3(slab + 3u * (n_mats + e), g); }
+    __device__ __forceinline__ void vertex(uint32_t, float, bool) {}
+    __device__ __forceinline__ void term(uint32_t, uint32_t, float, f3) {}
+};
+
+// k_grad_paths_nlos<EXT> (mtr_grad_nlos.hip) over the lanes of `a`; launch_grad runs k_grad_reduce behind it
+hipError_t launch_grad_paths_nlos(const GradArgs &a, const NlosConst &nlos_unit, bool ext, int grid, size_t lds, hipStream_t stream);
+
+} // namespace mtr

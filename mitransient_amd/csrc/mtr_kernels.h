@@ -197,10 +197,16 @@ hipError_t launch_develop(const Film &film, const float *t4, float *t3, const fl
 struct GradConst;
 constexpr uint32_t kGradTexSlabBytes = 8u * 1024u;
 uint32_t grad_tex_tier(const SceneDev &sc, uint32_t n_texels);
-uint32_t grad_grid(const SceneDev &sc, uint64_t n_lanes, int n_cu, size_t *lds_out, bool *scene_lds_out, uint32_t slab_texels = 0u);
+// nlos (grad_grid) / nlos_unit (launch_grad: the scene's NlosConst with unit irradiance, gc.em_radiance = the true one): the NLOS
+// tier — the laser takes the slab's three emitter words (grad_ems is (1, 3)), the scene must fit LDS, and at most kGradNlosPerCu
+// workgroups per compute unit are asked for (the kernel's launch bound)
+constexpr int kGradNlosPerCu = 3;
+uint32_t grad_grid(const SceneDev &sc, uint64_t n_lanes, int n_cu, size_t *lds_out, bool *scene_lds_out, uint32_t slab_texels = 0u,
+                   bool nlos = false);
 hipError_t launch_grad(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
                        const GradConst &gc, uint32_t pixel_begin, uint32_t n_pixels, uint32_t spp_begin, uint32_t spp_chunk,
                        double *partial, uint32_t grid, size_t lds, bool scene_lds, float *grad_mats, float *grad_ems, hipStream_t stream,
-                       uint32_t tex_tier = 0u, uint32_t n_texels = 0u, double *tex_acc = nullptr, float *grad_texels = nullptr);
+                       uint32_t tex_tier = 0u, uint32_t n_texels = 0u, double *tex_acc = nullptr, float *grad_texels = nullptr,
+                       const NlosConst *nlos_unit = nullptr);
 
 } // namespace mtr

@@ -169,11 +169,21 @@ MTR_HD bool nlos_bsdf_smooth(const mtr_material &m) { return m.type == MTR_BSDF_
 // `reload()` runs after every traversal: a caller that can re-read nc / film / rc (k_fused: from the kernarg segment, kernarg_copy)
 // does so there instead of holding ~100 uniform values in (spilled) scalar registers across the walks — path_bounce's `refresh`
 struct NoReload { MTR_HD void operator()() const {} };
+// The hook of the gradient replay (mtr_grad.h: grad_nlos_walk).  vertex(material, active_next) sees every bounce's vertex before
+// its terms; term(Lr, opl, material, at_laser_spot) sees every emitter_nee_sample term BEFORE the sample scale, with its optical
+// path length and the material of the vertex that was connected to the laser (at_laser_spot: that vertex is the laser spot c2 of
+// emitter_laser_targets_sample, not the bounce's own).  The default does nothing: callers that pass no hook are what they were.
+struct NoNlosHook {
+    static constexpr bool kOn = false;       // compiles the calls out
+    MTR_HD void vertex(uint32_t, bool) const {}
+    MTR_HD void term(f3, float, uint32_t, bool) const {}
+};
 // TR (here and below): scene traits (mtr_core.h) — kTrNoLobes takes the rough lobes' code out of the extended instantiations
-template <bool EXT, uint32_t TR = 0u, class Stack, class Sink, class Reload = NoReload>
+template <bool EXT, uint32_t TR = 0u, class Stack, class Sink, class Reload = NoReload, class Hook = NoNlosHook>
 MTR_HD f3 nlos_emitter_nee(Path &p, const HitCtx &c, const mtr_material &mat, f3 albedo, f3 beta, float distance, uint32_t depth,
                            bool focus_laser, uint32_t laser, const SceneView &sc, const NlosConst &nc, const Film &film,
-                           const RenderConst &rc, Stack &st, Sink &sink, BounceStats &stats, const Reload &reload = Reload())
+                           const RenderConst &rc, Stack &st, Sink &sink, BounceStats &stats, const Reload &reload = Reload(),
+                           Hook hook = Hook())
 {
     // visibility of the emitter origin (:441)
     const Ray sr = spawn_ray_to(c.sp, c.gn, nc.l_origin);
@@ -198,6 +208,7 @@ MTR_HD f3 nlos_emitter_nee(Path &p, const HitCtx &c, const mtr_material &mat, f3
     if ((nc.flags & MTR_NLOS_DISCARD_DIRECT) && !(depth > 2)) return mk(0, 0, 0);             // :491-492
     const f3 Lr = mk((beta.x * bv.x) * w.x, (beta.y * bv.y) * w.y, (beta.z * bv.z) * w.z);    // :493
     if (nc.flags & MTR_NLOS_ACCOUNT_FIRST_LAST) distance += ds_dist * p.eta;                   // :497-498
+    if constexpr (Hook::kOn) hook.term(Lr, distance, c.mat, focus_laser);
     const uint32_t fx = p.px - film.crop_x, fy = p.py - film.crop_y;
     const float vr = Lr.x * rc.sample_scale, vg = Lr.y * rc.sample_scale, vb = Lr.z * rc.sample_scale;
     if ((fx < film.width) & (fy < film.height) && (vr != 0.0f || vg != 0.0f || vb != 0.0f)) {
@@ -208,10 +219,10 @@ MTR_HD f3 nlos_emitter_nee(Path &p, const HitCtx &c, const mtr_material &mat, f3
 }
 
 // emitter_laser_targets_sample (:511-564)
-template <bool EXT, uint32_t TR = 0u, class Stack, class Sink, class Reload = NoReload>
+template <bool EXT, uint32_t TR = 0u, class Stack, class Sink, class Reload = NoReload, class Hook = NoNlosHook>
 MTR_HD f3 nlos_laser_targets(Path &p, const HitCtx &c, const mtr_material &mat, f3 albedo, f3 lt, uint32_t depth, uint32_t laser,
                              const SceneView &sc, const NlosConst &nc, const Film &film, const RenderConst &rc,
-                             Stack &st, Sink &sink, BounceStats &stats, const Reload &reload = Reload())
+                             Stack &st, Sink &sink, BounceStats &stats, const Reload &reload = Reload(), Hook hook = Hook())
 {
     f3 dd = lt - c.sp;
     const float dl = sqrtf(dot(dd, dd));
@@ -233,7 +244,7 @@ MTR_HD f3 nlos_laser_targets(Path &p, const HitCtx &c, const mtr_material &mat, 
     const float pdf_ls = (dl * dl) / wlz;                                                      // :546-551
     const f3 b2 = mk(p.beta.x * (bs.x / pdf_ls), p.beta.y * (bs.y / pdf_ls), p.beta.z * (bs.z / pdf_ls));
     return nlos_emitter_nee<EXT, TR>(p, c2, sc.mats[c2.mat], material_albedo<EXT>(sc, sc.mats[c2.mat], h2), b2, p.dist + dl * p.eta, depth + 1, true,
-                                 laser, sc, nc, film, rc, st, sink, stats, reload);
+                                 laser, sc, nc, film, rc, st, sink, stats, reload, hook);
 }
 
 // hidden_geometry_sample (:637-670) incl. _sample_hidden_geometry_position (:385-430)
@@ -276,9 +287,10 @@ MTR_HD f3 nlos_laser_target(const NlosConst &nc, uint32_t px, uint32_t py)
 }
 
 // One iteration of TransientNLOSPath.sample (:740-918).  Returns active_next.
-template <bool EXT = false, uint32_t TR = 0u, class Stack, class Sink, class Reload = NoReload>
+// hook: the gradient replay's (NoNlosHook above); an Exhaustive capture has no gradients and does not call it
+template <bool EXT = false, uint32_t TR = 0u, class Stack, class Sink, class Reload = NoReload, class Hook = NoNlosHook>
 MTR_HD bool nlos_bounce(Path &p, const SceneView &sc, const NlosConst &nc, const Film &film, const RenderConst &rc,
-                        Stack &st, Sink &sink, BounceStats &stats, const Reload &reload = Reload())
+                        Stack &st, Sink &sink, BounceStats &stats, const Reload &reload = Reload(), Hook hook = Hook())
 {
     const Hit h = traverse<false>(sc, p.ray.o, p.ray.d, p.ray.tmax, st);
     reload();
@@ -292,6 +304,7 @@ MTR_HD bool nlos_bounce(Path &p, const SceneView &sc, const NlosConst &nc, const
     if (valid) c = hit_ctx<EXT>(sc, p.ray.d, h);
     const mtr_material &mat = sc.mats[c.mat];
     const f3 albedo = valid ? material_albedo<EXT>(sc, mat, h) : mk(0, 0, 0);
+    if constexpr (Hook::kOn) hook.vertex(c.mat, active_next);
     // the only emitter is the projector (not a surface): Le = 0 (:757-777)
     if (active_next && nlos_bsdf_smooth<EXT, TR>(mat)) {                                 // active_em :785-786
         if ((nc.flags & MTR_NLOS_LASER_SAMPLING) && nc.capture_type == MTR_CAPTURE_EXHAUSTIVE) {
@@ -306,9 +319,9 @@ MTR_HD bool nlos_bounce(Path &p, const SceneView &sc, const NlosConst &nc, const
             const float nlf = (float)nl;
             Lr = mk(Lr.x / nlf, Lr.y / nlf, Lr.z / nlf);
         } else if (nc.flags & MTR_NLOS_LASER_SAMPLING)                                            // emitter_laser_sample: depth + 1
-            Lr = nlos_laser_targets<EXT, TR>(p, c, mat, albedo, nlos_laser_target(nc, p.px, p.py), p.depth + 1u, 0u, sc, nc, film, rc, st, sink, stats, reload);
+            Lr = nlos_laser_targets<EXT, TR>(p, c, mat, albedo, nlos_laser_target(nc, p.px, p.py), p.depth + 1u, 0u, sc, nc, film, rc, st, sink, stats, reload, hook);
         else
-            Lr = nlos_emitter_nee<EXT, TR>(p, c, mat, albedo, p.beta, p.dist, p.depth, false, 0u, sc, nc, film, rc, st, sink, stats, reload);
+            Lr = nlos_emitter_nee<EXT, TR>(p, c, mat, albedo, p.beta, p.dist, p.depth, false, 0u, sc, nc, film, rc, st, sink, stats, reload, hook);
     }
     // hidden-geometry / BSDF sampling (:797-833)
     const bool hg = (nc.flags & MTR_NLOS_HG_SAMPLING) != 0;

@@ -4,8 +4,8 @@ Mirrors mitransient/integrators/common.py — ``__init__`` (:22-30), ``prepare``
 ``render`` (:122-213), ``add_transient_f`` (:411-422), ``check_transient_`` (:424-447) —
 with the Dr.Jit trace replaced by launches of the HIP library: ``sample_rays`` +
 ``sample`` + the film splats of one pass are ONE call to ``mtr_render``.
-``render_backward`` (:325-409) is the reverse mode over the constant diffuse reflectances and emitter radiances (one call to
-``mtr_render_grad`` per pass); ``render_forward`` (:215-323) is not available.
+``render_backward`` (:325-409) is the reverse mode over the constant diffuse reflectances and emitter radiances — with
+``transient_nlos_path``, the projector's irradiance — (one call to ``mtr_render_grad`` per pass); ``render_forward`` (:215-323) is not available.
 """
 from __future__ import annotations
 
@@ -327,8 +327,18 @@ class TransientADIntegrator:
         v = variant.get() or ""
         if not v.endswith("_ad_rgb"):
             raise ValueError(f"{v}: differentiable rendering is available in the *_ad_rgb variants only")
-        if isinstance(self, TransientNLOSPath):
-            raise ValueError("transient_nlos_path: differentiable rendering is available with transient_path only")
+        nlos = isinstance(self, TransientNLOSPath)
+        if nlos:
+            from ..emitters import Projector
+            ems = scene.emitters()
+            if len(ems) != 1 or not isinstance(ems[0], Projector):
+                raise ValueError("transient_nlos_path: differentiable rendering needs a scene whose only emitter is a projector")
+            if int(self.capture_type) == 3:
+                raise ValueError("transient_nlos_path: differentiable rendering is not available for an Exhaustive capture "
+                                 "(Single and Confocal are)")
+            for k, val in (params or {}).items():
+                if getattr(val, "requires_grad", False) and k.endswith(".data"):
+                    raise ValueError(f"{k}: texel gradients are available with transient_path only (not transient_nlos_path)")
         if isinstance(sensor, int):
             sensor = scene.sensors()[sensor]
         film = sensor.film()
@@ -348,8 +358,8 @@ class TransientADIntegrator:
                 continue
             if k not in keys:
                 raise ValueError(f"{k}: not a differentiable parameter (the constant reflectance of a diffuse BSDF, the texels of a "
-                                 f"bitmap that only diffuse reflectances use and the constant radiance of an area / angulararea "
-                                 f"emitter are: {sorted(keys)})")
+                                 f"bitmap that only diffuse reflectances use, the constant radiance of an area / angulararea "
+                                 f"emitter and the constant irradiance of a NLOS scene's projector are: {sorted(keys)})")
             if keys[k][0] == "texture":
                 if tuple(val.shape) != tuple(scene.data(sensor).textures[keys[k][1]].shape):
                     raise ValueError(f"{k}: expected texels of shape {tuple(scene.data(sensor).textures[keys[k][1]].shape)}, "

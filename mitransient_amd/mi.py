@@ -153,6 +153,7 @@ class Scene:
         # objects that were loaded on their own (mi.load_dict(shape) / mi.load_dict(projector)) keep their identity,
         # so that mitransient.nlos.focus_emitter_* edits made later are seen by the render
         self.shape_objs_, self.emitters_, self.sensors_ = {}, [], []
+        self.emitter_names_ = []               # the projectors' keys in the scene dictionary (<emitter id>.irradiance.value)
         flat = {}
         for k, v in d.items():
             if isinstance(v, Shape):
@@ -160,10 +161,12 @@ class Scene:
                 flat[k] = v.dict_
             elif isinstance(v, Projector):
                 self.emitters_.append(v)
+                self.emitter_names_.append(k)
             elif isinstance(v, dict) and v.get("type") == "projector":
                 e = Projector(Properties("projector", v))
                 e.dict_ = v
                 self.emitters_.append(e)
+                self.emitter_names_.append(k)
             elif isinstance(v, dict) and v.get("type") in _SHAPE_TYPES:
                 self.shape_objs_[k] = _load_shape(v)
                 flat[k] = v
@@ -254,12 +257,27 @@ class Scene:
         from .scene import param_locations, rgb3
         if self.geometry_ is not None:
             return {}
-        return {k: list(self.param_values_.get(k, rgb3(v))) for k, (_, _, v) in param_locations(self.dict_).items()}
+        out = {k: list(self.param_values_.get(k, rgb3(v))) for k, (_, _, v) in param_locations(self.dict_).items()}
+        k = self.laser_key()
+        if k is not None:
+            out[k] = [float(x) for x in self.emitters_[0].irradiance]
+        return out
+
+    def laser_key(self):
+        """``<emitter id>.irradiance.value`` of a NLOS scene's projector (the one emitter of transient_nlos_path), else None"""
+        from .integrators.transientnlospath import TransientNLOSPath
+        if isinstance(self.integrator_, TransientNLOSPath) and len(self.emitters_) == 1:
+            return f"{self.emitter_names_[0]}.irradiance.value"
+        return None
 
     def grad_keys(self, sensor=0):
         """{key: ("material" | "emitter", index)}: the parameters mtr_render_grad differentiates, resolved to the flattened
-        tables"""
-        return self.data(sensor).grad_keys
+        tables; a NLOS scene's laser is its one "emitter" (grad_emitters of mtr_render_grad is (1, 3))"""
+        sd = self.data(sensor)
+        k = self.laser_key()
+        if k is None or sd.nlos is None:
+            return sd.grad_keys
+        return {**sd.grad_keys, k: ("emitter", 0)}
 
     def texture_locations_(self):
         from .scene import texture_locations
@@ -372,6 +390,10 @@ class Scene:
             v = np.repeat(v, 3)
         if v.size != 3:
             raise ValueError(f"{key}: expected 3 values, got {v.size}")
+        if key == self.laser_key():
+            # the projector object takes it: the NLOS description is rebuilt from the live objects on the next render (gpu_handle)
+            self.emitters_[0].irradiance = [float(np.float32(x)) for x in v]
+            return
         self.ensure_own_records([key])
         self.param_values_[key] = [float(np.float32(x)) for x in v]
         lib = _cabi.load_library()

@@ -7,7 +7,9 @@ Size = width x height x temporal_bins x spp (the second default is BASELINE conf
 backward pass differentiates every key of mi.traverse (three albedos, one radiance).  Times are medians of wall-clock time
 around a synchronised call, after one warm-up call.  --textures: per bitmap size W x H, the same box with that bitmap on its back
 wall and floor — the backward pass with the constant keys alone (mtr_render_grad on the textured scene) and with the texels
-as well (mtr_render_grad_tex; the tier it ran is reported)."""
+as well (mtr_render_grad_tex; the tier it ran is reported).
+--scene nlos: scenes.nlos_z (confocal; default size 256x256x4096x512, BASELINE config 4's per-GPU share) instead of the Cornell box:
+render_backward over the two albedos and the laser's irradiance against the primal (fused, the NLOS tier's organisation)."""
 import argparse
 import json
 import os
@@ -37,7 +39,10 @@ def main():
     ap.add_argument("--sizes", default="256x256x400x64,512x512x1024x1024")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--textures", default="")
+    ap.add_argument("--scene", default="cornell", choices=["cornell", "nlos"])
     args = ap.parse_args()
+    if args.scene == "nlos":
+        return main_nlos(args)
     import torch
     import mitransient_amd as mitr
     import mitransient_amd.mi as mi
@@ -87,6 +92,32 @@ def main():
             r2["grad_with_texels_ms"] = timed(lambda: ti.render_backward(ts, q, grad_in=(g_s, g_t), seed=1, spp=spp), args.reps)
             r2["texels_over_constant"] = r2["grad_with_texels_ms"] / r2["grad_constant_keys_ms"]
             print(json.dumps(r2), flush=True)
+        del g_t
+
+
+def main_nlos(args):
+    import torch
+    import mitransient_amd as mitr
+    import mitransient_amd.mi as mi
+    torch.cuda.set_device(0)
+    mi.set_variant("llvm_ad_rgb")
+    sizes = args.sizes if args.sizes != "256x256x400x64,512x512x1024x1024" else "256x256x4096x512"
+    for size in sizes.split(","):
+        W, H, T, spp = (int(x) for x in size.split("x"))
+        from mitransient_amd.scenes import nlos_z
+        scene = nlos_z(width=W, height=H, temporal_bins=T, bin_width_opl=8.0 / T, spp=spp)
+        integ = scene.integrator()
+        g = torch.Generator(device="cuda").manual_seed(0)
+        g_s = torch.randn((H, W, 3), device="cuda", generator=g)
+        g_t = torch.randn((H, W, T, 3), device="cuda", generator=g)
+        p = mi.traverse(scene)
+        for k in scene.grad_keys():
+            p[k] = torch.tensor(p[k], requires_grad=True)
+        res = {"scene": "nlos_z", "size": size, "keys": sorted(scene.grad_keys())}
+        res["primal_ms"] = timed(lambda: integ.render(scene, spp=spp, seed=0), args.reps)
+        res["grad_ms"] = timed(lambda: integ.render_backward(scene, p, grad_in=(g_s, g_t), seed=1, spp=spp), args.reps)
+        res["ratio"] = res["grad_ms"] / res["primal_ms"]
+        print(json.dumps(res), flush=True)
         del g_t
 
 
