@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 17
+#define MTR_ABI_VERSION 18
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -470,6 +470,29 @@ int  mtr_render_grad_tex(mtr_scene *, const mtr_render_params *params,
 #define MTR_GRAD_TEX_SLAB   1u   /* texel words in the f64 LDS slab, summed by the reduction pass */
 #define MTR_GRAD_TEX_GLOBAL 2u   /* f64 global atomics into a device buffer, converted to f32 by a small pass */
 int  mtr_render_grad_tex_tier(const mtr_scene *, uint32_t *tier);
+
+/* (ABI 18) Forward-mode derivatives of transient_path: TransientADIntegrator.render_forward (common.py:215-323), the transpose of
+ * mtr_render_grad_tex.  For the lanes of `params` the tangent of the DEVELOPED film of the seeded estimator is STORED to
+ *   steady_hw3     : device f32 (H, W, 3)     the crop window at the top-left corner, as grad_steady_hw3
+ *   transient_hwt3 : device f32 (H, W, T, 3)
+ * for the tangents
+ *   tan_materials : device f32 (n_materials, 3)  of the reflectance of every plain `diffuse` material (others: not read)
+ *   tan_emitters  : device f32 (n_emitters, 3)   of the radiance of every `area` / `angulararea` emitter
+ *   tan_texels    : device f32 (n_texels, 3)     of every texel, in the layout of mtr_scene_texture_layout; NULL: none
+ * Sampling is detached as in mtr_render_grad, so that  sum g . (J v) = sum (J^T g) . v  holds between the two entry points.  A path
+ * is walked once; its log-derivative (f64) gains  da / a  per channel at every `diffuse` vertex whose BSDF factor enters later
+ * terms (a channel whose albedo is exactly 0 adds nothing: 0, never NaN), and a term c_unit (.) L_e has the tangent
+ * c_unit (.) (L_e (.) D + dL_e), rounded to f32 once and splatted like the term itself.
+ * A pixel range renders those pixels' rows and leaves every other pixel of the outputs untouched.  Synchronises the stream.
+ * MTR_ERR_UNSUPPORTED (nothing is written): a sample sub-range or a pass of a split render (spp_scale), a NLOS scene, a phasor or
+ * exhaustive_scan film, MTR_FLAG_POLARIZED. */
+int  mtr_render_fwd(mtr_scene *, const mtr_render_params *params,
+                    const float *tan_materials, const float *tan_emitters, const float *tan_texels /* or NULL */,
+                    float *steady_hw3, float *transient_hwt3);
+/* (ABI 18) Which tier mtr_render_fwd runs (for tests and tools): a function of the scene and its film alone. */
+#define MTR_FWD_ROWS   1u   /* a pixel's tangent row lives in LDS and is stored once, developed: no global atomics */
+#define MTR_FWD_GLOBAL 2u   /* the row does not fit LDS beside the scene and the stack: f32 global atomics onto zeroed outputs */
+int  mtr_render_fwd_tier(const mtr_scene *, const mtr_render_params *params, uint32_t *tier);
 
 /* Zero the context's device counters on the context stream (then issue every mtr_render of the render with
  * MTR_FLAG_KEEP_COUNTERS and read the sums once with mtr_counters_read). */

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MITRANSIENT_AMD_LIB") or os.path.join(_HERE, "csrc", "libmitransient_amd.so")   # env override: kernel A/B experiments
 
-MTR_ABI_VERSION = 17
+MTR_ABI_VERSION = 18
 MTR_TRAIT_DIFFUSE, MTR_TRAIT_ONE_RECT_EMITTER, MTR_TRAIT_LEAF_PAIR, MTR_TRAIT_FLAT_TOP, MTR_TRAIT_FLAT_LEAVES, MTR_TRAIT_NO_LOBES, MTR_TRAIT_GREY = 1, 2, 4, 8, 16, 32, 64      # mtr_scene_traits
 MTR_SPLAT_FILM_ZERO = 0x100      # mtr_splat_add: OR into `variant` when the film is all-zero on entry
 
@@ -31,6 +31,7 @@ MTR_FLAG_POLARIZED = 256           # (ABI 14) the *_mono_polarized variants: Sto
 MTR_MODE_AUTO, MTR_MODE_FUSED, MTR_MODE_WAVEFRONT = 0, 1, 2
 MTR_RECT_ANALYTIC, MTR_RECT_FLIP_NORMALS = 1, 2
 MTR_GRAD_TEX_NONE, MTR_GRAD_TEX_SLAB, MTR_GRAD_TEX_GLOBAL = 0, 1, 2     # mtr_render_grad_tex_tier
+MTR_FWD_ROWS, MTR_FWD_GLOBAL = 1, 2     # mtr_render_fwd_tier
 
 _f3 = C.c_float * 3
 _f16 = C.c_float * 16
@@ -157,6 +158,7 @@ EXPORTS = [
     "mtr_ctx_trim", "mtr_film_clear", "mtr_render", "mtr_render_plan", "mtr_counters_reset", "mtr_counters_read", "mtr_film_develop", "mtr_splat_add", "mtr_debug_set_splat_log",
     "mtr_render_grad", "mtr_scene_set_colors",
     "mtr_render_grad_tex", "mtr_render_grad_tex_tier", "mtr_scene_set_texture", "mtr_scene_texture_layout",
+    "mtr_render_fwd", "mtr_render_fwd_tier",
 ]
 
 _lib = None
@@ -212,6 +214,8 @@ def load_library() -> C.CDLL:
     lib.mtr_render_grad_tex_tier.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.mtr_scene_set_texture.argtypes = [vp, C.c_uint32, vp]
     lib.mtr_scene_texture_layout.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.mtr_render_fwd.argtypes = [vp, C.POINTER(mtr_render_params), vp, vp, vp, vp, vp]      # (ABI 18)
+    lib.mtr_render_fwd_tier.argtypes = [vp, C.POINTER(mtr_render_params), C.POINTER(C.c_uint32)]
     if lib.mtr_abi_version() != MTR_ABI_VERSION:
         raise MitransientAMDError("libmitransient_amd.so ABI version mismatch; rebuild")
     _lib = lib

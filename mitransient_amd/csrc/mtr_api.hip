@@ -10,6 +10,7 @@
 #include "mtr_kernels.h"
 #include "mtr_polar.h"
 #include "mtr_grad.h"
+#include "mtr_fwd_args.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -953,6 +954,73 @@ int mtr_render_grad_tex(mtr_scene *s, const mtr_render_params *p, const float *g
                         float *grad_materials, float *grad_emitters, float *grad_texels)
 {
     return render_grad(s, p, g_s, g_t, grad_materials, grad_emitters, grad_texels);
+}
+
+// mtr_render_fwd (ABI 18): the refusals, shared with mtr_render_fwd_tier
+static int check_render_fwd(mtr_scene *s, const mtr_render_params *p)
+{
+    mtr_ctx *c = s->ctx;
+    const Film &f = s->film;
+    if (int r = check_render_ranges(c, f, p, "mtr_render_fwd", "a forward-mode render runs in one pass")) return r;
+    if (f.n_freq || f.lasers > 1u || (p->flags & MTR_FLAG_POLARIZED))
+        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_fwd: a plain transient_hdr_film (RGB) only: "
+                                            "no phasor film, exhaustive_scan or polarized transport");
+    if (s->nlos.on) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_fwd: transient_path only (not the NLOS tier)");
+    if (p->spp_begin != 0u || p->spp_end != p->spp_total || (p->spp_scale != 0u && p->spp_scale != p->spp_total))
+        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_fwd: every sample of a pixel in one call (no sample sub-range, no pass of a split "
+                                            "render): a pixel's developed row is stored once");
+    return MTR_OK;
+}
+
+int mtr_render_fwd_tier(const mtr_scene *s, const mtr_render_params *p, uint32_t *tier)
+{
+    if (!s || !p || !tier) return MTR_ERR_INVALID;
+    if (int r = check_render_fwd(const_cast<mtr_scene *>(s), p)) return r;
+    *tier = fwd_tier(s->dev, s->film);
+    return MTR_OK;
+}
+
+int mtr_render_fwd(mtr_scene *s, const mtr_render_params *p, const float *tan_materials, const float *tan_emitters,
+                   const float *tan_texels, float *steady_hw3, float *transient_hwt3)
+{
+    if (!s || !p || !tan_materials || (s->dev.n_ems && !tan_emitters) || !steady_hw3 || !transient_hwt3)
+        return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_render_fwd: NULL argument");
+    mtr_ctx *c = s->ctx;
+    const Film &f = s->film;
+    if (int r = check_render_fwd(s, p)) return r;
+    const uint32_t n_pixels = p->pixel_end - p->pixel_begin;
+    if (n_pixels == 0u) return MTR_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    FwdPlan pl{};
+    if (!fwd_plan(s->dev, f, n_pixels, p->spp_total, c->n_cu, pl))
+        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_fwd: the traversal stack and the staged scene exceed LDS");
+    // the traced emitter table carries unit radiance; the true radiance goes alongside (as mtr_render_grad)
+    const uint32_t n_e = s->dev.n_ems;
+    std::vector<Emitter> ems(n_e);
+    std::vector<float> rad(3u * (size_t)n_e + 3u, 0.0f);
+    if (n_e) HIP_TRY(c, hipMemcpy(ems.data(), s->dev.ems, n_e * sizeof(Emitter), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ems.size(); ++i)
+        for (int k = 0; k < 3; ++k) { rad[3u * i + k] = ems[i].radiance[k]; ems[i].radiance[k] = 1.0f; }
+    const size_t ems_b = ((size_t)n_e * sizeof(Emitter) + 255u) & ~(size_t)255u;
+    unsigned char *ws = nullptr;
+    HIP_TRY(c, hipMalloc((void **)&ws, ems_b + rad.size() * sizeof(float)));
+    Emitter *d_ems = (Emitter *)ws;
+    float *d_rad = (float *)(ws + ems_b);
+    hipError_t e = hipSuccess;
+    if (n_e) e = hipMemcpy(d_ems, ems.data(), n_e * sizeof(Emitter), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rad, rad.data(), rad.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const RenderConst rc = make_render_const(*p, f, n_e);
+        FwdConst fc;
+        fc.em_radiance = d_rad; fc.tan_mats = tan_materials; fc.tan_ems = n_e ? tan_emitters : d_rad;
+        fc.tan_texels = (s->n_texels && s->dev.texels) ? tan_texels : nullptr;
+        e = launch_fwd(s->dev, d_ems, s->cam, f, rc, fc, p->pixel_begin, p->pixel_end, p->spp_total, pl, steady_hw3, transient_hwt3, c->stream);
+    }
+    const hipError_t e_sync = hipStreamSynchronize(c->stream);
+    (void)hipFree(ws);
+    HIP_TRY(c, e);
+    HIP_TRY(c, e_sync);
+    return MTR_OK;
 }
 
 int mtr_counters_reset(mtr_ctx *c)

@@ -165,6 +165,10 @@ class DistributedRenderer:
         raise ValueError("DistributedRenderer: differentiable rendering is available on one GPU only (render_backward of the "
                          "scene's integrator)")
 
+    def render_forward(self, *a, **k):
+        raise NotImplementedError("DistributedRenderer: forward-mode differentiation is available on one GPU only (render_forward "
+                                  "of the scene's integrator)")
+
     def render(self, spp: int, seed: int = 0, sensor: int = 0):
         import torch
         import torch.distributed as dist

@@ -5,7 +5,8 @@ Mirrors mitransient/integrators/common.py — ``__init__`` (:22-30), ``prepare``
 with the Dr.Jit trace replaced by launches of the HIP library: ``sample_rays`` +
 ``sample`` + the film splats of one pass are ONE call to ``mtr_render``.
 ``render_backward`` (:325-409) is the reverse mode over the constant diffuse reflectances and emitter radiances — with
-``transient_nlos_path``, the projector's irradiance — (one call to ``mtr_render_grad`` per pass); ``render_forward`` (:215-323) is not available.
+``transient_nlos_path``, the projector's irradiance — (one call to ``mtr_render_grad`` per pass); ``render_forward`` (:215-323) is the forward mode over the same parameters of
+``transient_path`` (one call to ``mtr_render_fwd``).
 """
 from __future__ import annotations
 
@@ -17,6 +18,30 @@ from ..films.transient_hdr_film import TransientHDRFilm
 from ..runtime import get_context
 from ..scene import Properties
 from ..tensor import TensorXf
+
+
+def _dual_tangent(v):
+    """the tangent of a ``torch.autograd.forward_ad`` dual tensor (inside its dual_level), else None"""
+    try:
+        import torch
+        if not isinstance(v, torch.Tensor):
+            return None
+        return torch.autograd.forward_ad.unpack_dual(v).tangent
+    except Exception:
+        return None
+
+
+def _wants_grad(v):
+    """a value of ``params`` that is differentiated: it requires grad (reverse mode) or is a dual tensor (forward mode)"""
+    return bool(getattr(v, "requires_grad", False)) or _dual_tangent(v) is not None
+
+
+class _Seed:
+    """stands for a value of ``params`` in check_grad_ when render_forward is given its tangent explicitly"""
+    requires_grad = True
+
+    def __init__(self, shape):
+        self.shape = tuple(shape)
 
 
 class TransientADIntegrator:
@@ -316,8 +341,75 @@ class TransientADIntegrator:
         self.total_counters = {k: v for k, v in self.last_counters.items() if k != "reserved"}
         return self.total_counters
 
-    def render_forward(self, *a, **k):
-        raise NotImplementedError("forward-mode differentiation (common.py:215-323) is not available; use render_backward")
+    # -- common.py:215-323 -----------------------------------------------------
+    def render_forward(self, scene, params, sensor=0, seed=0, spp=0, tangents=None):
+        """The tangent ``(steady (ch, cw, 3), transient (H, W, T, 3))`` of what ``render`` returns, for the seeded estimator with
+        sampling detached — the transpose of ``render_backward``.  ``tangents``: ``{key: tensor}`` over the keys
+        ``render_backward`` differentiates, ``(3,)`` (a 1-element value: all three channels) or the ``(H, W, 3)`` texels of a
+        ``.data`` key; ``None``: the tangents of the values of ``params`` that are ``torch.autograd.forward_ad`` dual tensors.
+        Every refusal is a ``NotImplementedError`` raised before any GPU work."""
+        import numpy as np
+        import torch
+        from .transientnlospath import TransientNLOSPath
+        if isinstance(self, TransientNLOSPath):
+            raise NotImplementedError("transient_nlos_path: forward-mode differentiation is available with transient_path only "
+                                      "(use render_backward)")
+        if tangents is None:
+            tangents = {k: t for k, t in ((k, _dual_tangent(v)) for k, v in (params or {}).items()) if t is not None}
+        probe = {k: v for k, v in (params or {}).items() if _wants_grad(v)}
+        probe.update({k: _Seed(getattr(t, "shape", ())) for k, t in tangents.items()})
+        try:
+            keys = self.check_grad_(scene, sensor, probe)
+        except ValueError as e:
+            raise NotImplementedError(f"render_forward: {e}") from e
+        if isinstance(sensor, int):
+            sensor = scene.sensors()[sensor]
+        film = sensor.film()
+        sampler = sensor.sampler().clone()
+        if spp != 0:
+            sampler.set_sample_count(spp)
+        spp = sampler.sample_count()
+        cw, ch = film.crop_size()
+        if cw * ch * spp > self.max_wavefront_size:
+            raise NotImplementedError("render_forward: a render of more than 2^32 lanes runs in several passes; forward-mode "
+                                      "differentiation needs one (common.py:237-240)")
+        sd = scene.data(sensor)
+        first = np.cumsum([0] + [int(t.shape[0] * t.shape[1]) for t in sd.textures])
+        n_m, n_e = max(1, sd.n_materials), max(1, sd.n_emitters)
+        tm = np.zeros((n_m, 3), np.float32)
+        te = np.zeros((n_e, 3), np.float32)
+        tx = None
+        for k, t in tangents.items():
+            kind, i = keys[k]
+            t = np.asarray(t.detach().cpu() if hasattr(t, "detach") else t, dtype=np.float32)
+            if kind == "texture":
+                if tx is None:
+                    tx = np.zeros((max(1, int(first[-1])), 3), np.float32)
+                tx[int(first[i]):int(first[i + 1])] += t.reshape(-1, 3)
+            else:
+                if t.size not in (1, 3):
+                    raise NotImplementedError(f"render_forward: {k}: a tangent of 1 or 3 elements, got shape {t.shape}")
+                (tm if kind == "material" else te)[i] += t.reshape(-1)
+        if getattr(params, "_dirty", None):
+            params.update()
+        # -- GPU work from here on ------------------------------------------------
+        sampler.set_samples_per_wavefront(spp)
+        sampler.seed(seed, cw * ch * spp)
+        W, H = film.size()
+        T = film.temporal_bins
+        dev = film._device if film._device is not None else torch.device("cuda", torch.cuda.current_device())
+        ctx = get_context(dev.index)
+        ctx.bind_current_stream()
+        handle = scene.gpu_handle(ctx, sensor)
+        d_tm, d_te = torch.from_numpy(tm).to(dev), torch.from_numpy(te).to(dev)
+        d_tx = torch.from_numpy(tx).to(dev) if tx is not None else None
+        steady = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
+        transient = torch.zeros((H, W, T, 3), dtype=torch.float32, device=dev)
+        p = self.render_params(film, sampler.seed_value(), spp)
+        ctx.check(ctx.lib.mtr_render_fwd(handle, C.byref(p), C.c_void_p(d_tm.data_ptr()), C.c_void_p(d_te.data_ptr()),
+                                         C.c_void_p(d_tx.data_ptr()) if d_tx is not None else None,
+                                         C.c_void_p(steady.data_ptr()), C.c_void_p(transient.data_ptr())), "mtr_render_fwd")
+        return TensorXf(steady[:ch, :cw].contiguous()), TensorXf(transient)
 
     # -- common.py:325-409 -----------------------------------------------------
     def check_grad_(self, scene, sensor, params):
@@ -337,7 +429,7 @@ class TransientADIntegrator:
                 raise ValueError("transient_nlos_path: differentiable rendering is not available for an Exhaustive capture "
                                  "(Single and Confocal are)")
             for k, val in (params or {}).items():
-                if getattr(val, "requires_grad", False) and k.endswith(".data"):
+                if _wants_grad(val) and k.endswith(".data"):
                     raise ValueError(f"{k}: texel gradients are available with transient_path only (not transient_nlos_path)")
         if isinstance(sensor, int):
             sensor = scene.sensors()[sensor]
@@ -348,13 +440,13 @@ class TransientADIntegrator:
             raise ValueError("differentiable rendering needs a transient_hdr_film")
         if film.exhaustive_scan:
             raise ValueError("transient_hdr_film with exhaustive_scan: differentiable rendering is not available")
-        wanted = [k for k, val in (params or {}).items() if getattr(val, "requires_grad", False)]
+        wanted = [k for k, val in (params or {}).items() if _wants_grad(val)]
         scene.ensure_own_records([k for k in wanted if k in scene.param_keys()], sensor)
         keys = dict(scene.grad_keys(sensor))
         keys.update({k: ("texture", i) for k, i in scene.texture_keys(sensor).items()})
         seen = {}
         for k, val in (params or {}).items():
-            if not getattr(val, "requires_grad", False):
+            if not _wants_grad(val):
                 continue
             if k not in keys:
                 raise ValueError(f"{k}: not a differentiable parameter (the constant reflectance of a diffuse BSDF, the texels of a "

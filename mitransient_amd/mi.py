@@ -486,17 +486,20 @@ def _tea32(v0, v1, rounds=4):
 
 
 def _grad_values(params):
-    """the (key, tensor) pairs of ``params`` whose value is a torch tensor that requires grad"""
+    """the (key, tensor) pairs of ``params`` whose value is a torch tensor that requires grad or a forward_ad dual tensor"""
     if not params:
         return []
-    return [(k, v) for k, v in params.items() if getattr(v, "requires_grad", False)]
+    from .integrators.common import _wants_grad
+    return [(k, v) for k, v in params.items() if _wants_grad(v)]
 
 
 def render(scene: Scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, spp=0, spp_grad=0):
     """``mi.render``: returns ``(steady (H,W,3), transient (H,W,T,3))`` like the reference's
     TransientADIntegrator.render (common.py:212-213).  When a value of ``params`` is a torch tensor that requires grad, the
     tensors' ``.torch()`` carry a ``grad_fn``: their backward pass is ``integrator.render_backward`` at ``seed_grad`` (0: a TEA
-    scramble of ``seed``, as mitsuba's mi.render) with ``spp_grad`` samples (0: ``spp``)."""
+    scramble of ``seed``, as mitsuba's mi.render) with ``spp_grad`` samples (0: ``spp``).  Inside
+    ``torch.autograd.forward_ad.dual_level()`` the values that are dual tensors give the outputs tangents:
+    ``integrator.render_forward`` at the same ``seed_grad`` / ``spp_grad``."""
     integ = integrator or scene.integrator()
     grads = _grad_values(params)
     if not grads:
@@ -525,8 +528,16 @@ def render(scene: Scene, params=None, sensor=0, integrator=None, seed=0, seed_gr
             g = integ.render_backward(scene, params, grad_in=(g_s, g_t), sensor=sensor, seed=seed_grad, spp=spp_grad)
             # (a 1-element value stands for the three channels: it receives their sum, on its own device like the 3-vector;
             # the (H, W, 3) texels of a `.data` key receive their own shape)
-            return tuple((g[k] if v.numel() == g[k].numel() else g[k].sum()).to(dtype=v.dtype, device=v.device).reshape(v.shape)
+            return tuple(None if k not in g else
+                         (g[k] if v.numel() == g[k].numel() else g[k].sum()).to(dtype=v.dtype, device=v.device).reshape(v.shape)
                          for k, v in grads)
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            # forward mode (torch.autograd.forward_ad): the outputs' tangents are render_forward at seed_grad / spp_grad
+            tan = {k: t for (k, _), t in zip(grads, tangents) if t is not None}
+            d_s, d_t = integ.render_forward(scene, params, sensor=sensor, seed=seed_grad, spp=spp_grad, tangents=tan)
+            return d_s.torch(), d_t.torch()
 
     s, t = _Render.apply(*[v for _, v in grads])
     return TensorXf(s), TensorXf(t)

@@ -9,7 +9,9 @@ around a synchronised call, after one warm-up call.  --textures: per bitmap size
 wall and floor — the backward pass with the constant keys alone (mtr_render_grad on the textured scene) and with the texels
 as well (mtr_render_grad_tex; the tier it ran is reported).
 --scene nlos: scenes.nlos_z (confocal; default size 256x256x4096x512, BASELINE config 4's per-GPU share) instead of the Cornell box:
-render_backward over the two albedos and the laser's irradiance against the primal (fused, the NLOS tier's organisation)."""
+render_backward over the two albedos and the laser's irradiance against the primal (fused, the NLOS tier's organisation).
+--forward: the forward mode instead (mtr_render_fwd, integrator.render_forward with a tangent on every key) against the wavefront
+primal and render_backward of the same build: the three are called in turn, --reps rounds after one warm-up round, medians."""
 import argparse
 import json
 import os
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--textures", default="")
     ap.add_argument("--scene", default="cornell", choices=["cornell", "nlos"])
+    ap.add_argument("--forward", action="store_true")
     args = ap.parse_args()
     if args.scene == "nlos":
         return main_nlos(args)
@@ -61,6 +64,27 @@ def main():
         for k in scene.grad_keys():
             p[k] = torch.tensor(p[k], requires_grad=True)
         res = {"size": size}
+        if args.forward:
+            tan = {k: p[k].detach() * 0.5 for k in scene.grad_keys()}
+            integ.amd_mode = "wavefront"
+            legs = {"primal_wavefront_ms": lambda: integ.render(scene, spp=spp, seed=0),
+                    "grad_ms": lambda: integ.render_backward(scene, p, grad_in=(g_s, g_t), seed=1, spp=spp),
+                    "forward_ms": lambda: integ.render_forward(scene, p, seed=1, spp=spp, tangents=tan)}
+            ts = {k: [] for k in legs}
+            for rep in range(args.reps + 1):                    # (round 0 warms up)
+                for k, fn in legs.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    if rep:
+                        ts[k].append((time.perf_counter() - t0) * 1e3)
+            res.update({k: statistics.median(v) for k, v in ts.items()})
+            res["forward_over_grad"] = res["forward_ms"] / res["grad_ms"]
+            res["forward_over_primal_wavefront"] = res["forward_ms"] / res["primal_wavefront_ms"]
+            print(json.dumps(res), flush=True)
+            del g_t
+            continue
         for mode in ("fused", "wavefront"):
             integ.amd_mode = mode
             res[f"primal_{mode}_ms"] = timed(lambda: integ.render(scene, spp=spp, seed=0), args.reps)
