@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 18
+#define MTR_ABI_VERSION 19
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -402,6 +402,20 @@ int  mtr_scene_set_texture(mtr_scene *, uint32_t index, const float *rgb);
  * of the whole scene (width = height = 0). */
 int  mtr_scene_texture_layout(const mtr_scene *, uint32_t index, uint32_t *first_texel, uint32_t *width, uint32_t *height);
 
+/* (ABI 19) The tint slots of mtr_render_grad_tint / mtr_render_fwd_tint (the reference: `specular_reflectance.value` and
+ * `specular_transmittance.value` of a BSDF are ordinary parameters of mi.traverse, common.py:215-409): one slot per constant tint
+ * the shading code multiplies a lobe by — materials in table order, `specular_reflectance` (which 0, mtr_material.c) of
+ * MTR_BSDF_CONDUCTOR, ROUGHCONDUCTOR, DIELECTRIC, THINDIELECTRIC and ROUGHDIELECTRIC, then `specular_transmittance` (which 1,
+ * mtr_material.c2) of the three dielectric types.  PLASTIC and ROUGHPLASTIC have none: their tint enters lobe sampling.
+ * *n_slots receives the count (0 for a scene with the NLOS tier); slot_material / slot_which (host, n_slots words each, or NULL)
+ * the material index and 0 | 1 of every slot.  A caller maps the tints it exposes as parameters to slots and ignores the others. */
+int  mtr_scene_tint_layout(const mtr_scene *, uint32_t *n_slots, uint32_t *slot_material, uint32_t *slot_which);
+/* (ABI 19) params.update() of a tint: material_c / material_c2 (host, n_materials x 3 each) replace mtr_material.c / .c2 of every
+ * material that has the slot (other materials keep theirs: c2 of an anisotropic roughconductor holds alpha_v); the traits that
+ * depend on colours are decided again, nothing else is rebuilt.  Synchronises the context's stream.  MTR_ERR_UNSUPPORTED for a
+ * scene with the NLOS tier. */
+int  mtr_scene_set_tints(mtr_scene *, const float *material_c, const float *material_c2);
+
 /* TransientImageBlock.clear (transient_image_block.py:56-70): zero the
  * (H,W,T,4) f32 accumulator and the (H,W,4) steady accumulator. */
 int  mtr_film_clear(mtr_ctx *, const mtr_film_desc *, float *transient_hwt4 /*device, may be NULL*/,
@@ -493,6 +507,27 @@ int  mtr_render_fwd(mtr_scene *, const mtr_render_params *params,
 #define MTR_FWD_ROWS   1u   /* a pixel's tangent row lives in LDS and is stored once, developed: no global atomics */
 #define MTR_FWD_GLOBAL 2u   /* the row does not fit LDS beside the scene and the stack: f32 global atomics onto zeroed outputs */
 int  mtr_render_fwd_tier(const mtr_scene *, const mtr_render_params *params, uint32_t *tier);
+
+/* (ABI 19) mtr_render_grad_tex plus the gradients of the specular tints (TransientADIntegrator.render_backward, common.py:325-409,
+ * over `specular_reflectance.value` / `specular_transmittance.value`):
+ *   grad_tints : device f32 (n_slots, 3)  d loss / d tint of every slot of mtr_scene_tint_layout; NULL: exactly mtr_render_grad_tex
+ * A term is multilinear in the tints (no sampling decision reads one), so  d c / d s = c k_s(c) / s  per channel, k_s(c) the vertices
+ * at which s is a factor of c: the continued path carries the tint of the lobe that was SAMPLED at the vertex (reflection when the
+ * new ray leaves on the side it arrived on), the vertex's emitter-sampling term (rough lobes) the tint of the lobe EVALUATED for
+ * the shadow direction — on a roughdielectric the two can differ at one vertex.  A tint channel that is exactly 0 receives 0.
+ * Russian-roulette probabilities are constants.  The sums are f64 in the workgroups' LDS slabs (3 more words per slot), reduced
+ * without global atomics.  With grad_texels as well the texel gradients come from a launch of their own.  Everything
+ * mtr_render_grad refuses is refused; a non-NULL grad_tints on a NLOS scene is MTR_ERR_UNSUPPORTED with nothing written. */
+int  mtr_render_grad_tint(mtr_scene *, const mtr_render_params *params,
+                          const float *grad_steady_hw3, const float *grad_transient_hwt3,
+                          float *grad_materials, float *grad_emitters, float *grad_texels /* or NULL */, float *grad_tints /* or NULL */);
+/* (ABI 19) mtr_render_fwd plus the tangents of the specular tints (common.py:215-323), the transpose of mtr_render_grad_tint:
+ *   tan_tints : device f32 (n_slots, 3)  of every slot of mtr_scene_tint_layout; NULL: exactly mtr_render_fwd
+ * At a vertex on a tinted material the emitter-sampling term uses the log-derivative plus  ds / s  of the evaluated lobe's tint, the
+ * continued path plus that of the sampled lobe's.  Same tiers (mtr_render_fwd_tier), same refusals. */
+int  mtr_render_fwd_tint(mtr_scene *, const mtr_render_params *params,
+                         const float *tan_materials, const float *tan_emitters, const float *tan_texels /* or NULL */,
+                         const float *tan_tints /* or NULL */, float *steady_hw3, float *transient_hwt3);
 
 /* Zero the context's device counters on the context stream (then issue every mtr_render of the render with
  * MTR_FLAG_KEEP_COUNTERS and read the sums once with mtr_counters_read). */

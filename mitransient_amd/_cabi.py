@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MITRANSIENT_AMD_LIB") or os.path.join(_HERE, "csrc", "libmitransient_amd.so")   # env override: kernel A/B experiments
 
-MTR_ABI_VERSION = 18
+MTR_ABI_VERSION = 19
 MTR_TRAIT_DIFFUSE, MTR_TRAIT_ONE_RECT_EMITTER, MTR_TRAIT_LEAF_PAIR, MTR_TRAIT_FLAT_TOP, MTR_TRAIT_FLAT_LEAVES, MTR_TRAIT_NO_LOBES, MTR_TRAIT_GREY = 1, 2, 4, 8, 16, 32, 64      # mtr_scene_traits
 MTR_SPLAT_FILM_ZERO = 0x100      # mtr_splat_add: OR into `variant` when the film is all-zero on entry
 
@@ -159,6 +159,7 @@ EXPORTS = [
     "mtr_render_grad", "mtr_scene_set_colors",
     "mtr_render_grad_tex", "mtr_render_grad_tex_tier", "mtr_scene_set_texture", "mtr_scene_texture_layout",
     "mtr_render_fwd", "mtr_render_fwd_tier",
+    "mtr_scene_tint_layout", "mtr_scene_set_tints", "mtr_render_grad_tint", "mtr_render_fwd_tint",
 ]
 
 _lib = None
@@ -216,6 +217,10 @@ def load_library() -> C.CDLL:
     lib.mtr_scene_texture_layout.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.mtr_render_fwd.argtypes = [vp, C.POINTER(mtr_render_params), vp, vp, vp, vp, vp]      # (ABI 18)
     lib.mtr_render_fwd_tier.argtypes = [vp, C.POINTER(mtr_render_params), C.POINTER(C.c_uint32)]
+    lib.mtr_scene_tint_layout.argtypes = [vp, C.POINTER(C.c_uint32), vp, vp]      # (ABI 19)
+    lib.mtr_scene_set_tints.argtypes = [vp, vp, vp]
+    lib.mtr_render_grad_tint.argtypes = [vp, C.POINTER(mtr_render_params), vp, vp, vp, vp, vp, vp]
+    lib.mtr_render_fwd_tint.argtypes = [vp, C.POINTER(mtr_render_params), vp, vp, vp, vp, vp, vp]
     if lib.mtr_abi_version() != MTR_ABI_VERSION:
         raise MitransientAMDError("libmitransient_amd.so ABI version mismatch; rebuild")
     _lib = lib

@@ -11,6 +11,7 @@
 #include "mtr_polar.h"
 #include "mtr_grad.h"
 #include "mtr_fwd_args.h"
+#include "mtr_tint_args.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -356,6 +357,50 @@ int mtr_scene_set_colors(mtr_scene *s, const float *material_a, const float *emi
     const bool grey = colours_are_grey(mats.data(), (uint32_t)mats.size(), ems.data(), (uint32_t)ems.size(), s->dev.texels != nullptr);
     s->grey_scene = grey;
     s->dev.traits = grey ? (s->dev.traits | kTrGrey) : (s->dev.traits & ~kTrGrey);
+    return MTR_OK;
+}
+
+int mtr_scene_set_tints(mtr_scene *s, const float *material_c, const float *material_c2)
+{
+    if (!s || (s->dev.n_mats && (!material_c || !material_c2)))
+        return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_scene_set_tints: NULL argument");
+    mtr_ctx *c = s->ctx;
+    if (s->nlos.on) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_scene_set_tints: not for the NLOS tier");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // (renders in flight read the tables)
+    std::vector<mtr_material> mats(s->dev.n_mats);
+    std::vector<Emitter> ems(s->dev.n_ems);
+    std::vector<int32_t> slots(2u * mats.size() + 2u, -1);
+    if (!mats.empty()) HIP_TRY(c, hipMemcpy(mats.data(), s->dev.mats, mats.size() * sizeof(mtr_material), hipMemcpyDeviceToHost));
+    if (!ems.empty()) HIP_TRY(c, hipMemcpy(ems.data(), s->dev.ems, ems.size() * sizeof(Emitter), hipMemcpyDeviceToHost));
+    tint_slot_table(mats.data(), (uint32_t)mats.size(), slots.data());
+    for (size_t i = 0; i < mats.size(); ++i)
+        for (int k = 0; k < 3; ++k) {
+            if (slots[2u * i] >= 0) mats[i].c[k] = material_c[3 * i + k];
+            if (slots[2u * i + 1u] >= 0) mats[i].c2[k] = material_c2[3 * i + k];
+        }
+    if (!mats.empty()) HIP_TRY(c, hipMemcpy((void *)s->dev.mats, mats.data(), mats.size() * sizeof(mtr_material), hipMemcpyHostToDevice));
+    const bool grey = colours_are_grey(mats.data(), (uint32_t)mats.size(), ems.data(), (uint32_t)ems.size(), s->dev.texels != nullptr);
+    s->grey_scene = grey;
+    s->dev.traits = grey ? (s->dev.traits | kTrGrey) : (s->dev.traits & ~kTrGrey);
+    return MTR_OK;
+}
+
+int mtr_scene_tint_layout(const mtr_scene *s, uint32_t *n_slots, uint32_t *slot_material, uint32_t *slot_which)
+{
+    if (!s || !n_slots) return MTR_ERR_INVALID;
+    mtr_ctx *c = s->ctx;
+    std::vector<mtr_material> mats(s->dev.n_mats);
+    std::vector<int32_t> slots(2u * mats.size() + 2u, -1);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!mats.empty()) HIP_TRY(c, hipMemcpy(mats.data(), s->dev.mats, mats.size() * sizeof(mtr_material), hipMemcpyDeviceToHost));
+    *n_slots = s->nlos.on ? 0u : tint_slot_table(mats.data(), (uint32_t)mats.size(), slots.data());
+    if (!s->nlos.on)
+        for (size_t i = 0; i < 2u * mats.size(); ++i)
+            if (slots[i] >= 0) {
+                if (slot_material) slot_material[slots[i]] = (uint32_t)(i / 2u);
+                if (slot_which) slot_which[slots[i]] = (uint32_t)(i & 1u);
+            }
     return MTR_OK;
 }
 
@@ -863,9 +908,9 @@ int mtr_render_plan(mtr_scene *s, const mtr_render_params *p, uint32_t *mode_out
     return MTR_OK;
 }
 
-// mtr_render_grad (grad_texels == nullptr) and mtr_render_grad_tex
+// mtr_render_grad (grad_texels == nullptr), mtr_render_grad_tex and mtr_render_grad_tint (grad_tints != nullptr)
 static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_s, const float *g_t,
-                       float *grad_materials, float *grad_emitters, float *grad_texels)
+                       float *grad_materials, float *grad_emitters, float *grad_texels, float *grad_tints = nullptr)
 {
     if (!s || !p || !g_s || !g_t || !grad_materials || ((s->dev.n_ems || s->nlos.on) && !grad_emitters))
         return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_render_grad: NULL argument");
@@ -880,6 +925,7 @@ static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_
         if (s->nlos.k.capture_type == MTR_CAPTURE_EXHAUSTIVE)
             return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: the NLOS tier with a Single or Confocal capture only (no Exhaustive capture)");
         if (grad_texels) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad_tex: texel gradients are for transient_path only (not the NLOS tier)");
+        if (grad_tints) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad_tint: tint gradients are for transient_path only (not the NLOS tier)");
         if (s->nlos.k.film_w != f.width || s->nlos.k.film_h != f.height)
             return fail(c, MTR_ERR_INVALID, "mtr_render_grad: film size changed after mtr_scene_set_nlos; call it again");
     }
@@ -890,13 +936,29 @@ static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_
     const uint64_t n_lanes = (uint64_t)n_pixels * chunk;
     size_t lds = 0; bool scene_lds = false;
     const uint32_t n_tx = s->n_texels;
+    // tint slots (mtr_render_grad_tint): from the material table; the tint kernel carries no texel code, so texel gradients asked
+    // for beside tints come from a launch of their own first (its materials' and emitters' words are stored again below)
+    std::vector<int32_t> slots;
+    uint32_t n_tints = 0u;
+    if (grad_tints) {
+        std::vector<mtr_material> mats(n_m);
+        slots.assign(2u * (size_t)n_m + 2u, -1);
+        if (n_m) HIP_TRY(c, hipMemcpy(mats.data(), s->dev.mats, n_m * sizeof(mtr_material), hipMemcpyDeviceToHost));
+        n_tints = tint_slot_table(mats.data(), n_m, slots.data());
+        if (n_tints == 0u) grad_tints = nullptr;
+    }
+    if (grad_tints && grad_texels) {
+        if (int r = render_grad(s, p, g_s, g_t, grad_materials, grad_emitters, grad_texels)) return r;
+        grad_texels = nullptr;
+    }
     const uint32_t tier = grad_texels ? grad_tex_tier(s->dev, n_tx) : MTR_GRAD_TEX_NONE;
-    const uint32_t slab_tx = tier == MTR_GRAD_TEX_SLAB ? n_tx : 0u;
+    const uint32_t slab_tx = grad_tints ? n_tints : (tier == MTR_GRAD_TEX_SLAB ? n_tx : 0u);     // slab entries behind the emitters'
     const uint32_t grid = n_lanes ? grad_grid(s->dev, n_lanes, c->n_cu, &lds, &scene_lds, slab_tx, nlos) : 0u;
     if (n_lanes && grid == 0u)
         return fail(c, MTR_ERR_UNSUPPORTED, nlos ? "mtr_render_grad: the NLOS tier needs a scene whose tables, gradient slab and traversal stack fit LDS"
                                                  : "mtr_render_grad: the gradient slab and traversal stack exceed LDS");
     if (grid == 0u) {
+        if (grad_tints) HIP_TRY(c, hipMemsetAsync(grad_tints, 0, (size_t)n_tints * 3u * sizeof(float), c->stream));
         HIP_TRY(c, hipMemsetAsync(grad_materials, 0, (size_t)n_m * 3u * sizeof(float), c->stream));
         if (n_e) HIP_TRY(c, hipMemsetAsync(grad_emitters, 0, (size_t)n_e * 3u * sizeof(float), c->stream));
         if (tier != MTR_GRAD_TEX_NONE) HIP_TRY(c, hipMemsetAsync(grad_texels, 0, (size_t)n_tx * 3u * sizeof(float), c->stream));
@@ -918,15 +980,18 @@ static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_
     const size_t partial_b = ((size_t)grid * (slab_n + 3u * slab_tx) * sizeof(double) + 255u) & ~(size_t)255u;
     const size_t ems_b = ((size_t)ems.size() * sizeof(Emitter) + 255u) & ~(size_t)255u;
     const size_t acc_b = tier == MTR_GRAD_TEX_GLOBAL ? (size_t)n_tx * 3u * sizeof(double) : 0u;      // the global tier's f64 sums
-    const size_t ws_b = ems_b + ((rad.size() * sizeof(float) + 255u) & ~(size_t)255u) + partial_b + acc_b;
+    const size_t slots_b = grad_tints ? slots.size() * sizeof(int32_t) : 0u;                         // the tint slot table
+    const size_t ws_b = ems_b + ((rad.size() * sizeof(float) + 255u) & ~(size_t)255u) + partial_b + acc_b + slots_b;
     unsigned char *ws = nullptr;
     HIP_TRY(c, hipMalloc((void **)&ws, ws_b));
     Emitter *d_ems = (Emitter *)ws;
     float *d_rad = (float *)(ws + ems_b);
     double *d_partial = (double *)(ws + ems_b + ((rad.size() * sizeof(float) + 255u) & ~(size_t)255u));
     double *d_acc = acc_b ? (double *)((unsigned char *)d_partial + partial_b) : nullptr;
+    int32_t *d_slots = slots_b ? (int32_t *)((unsigned char *)d_partial + partial_b + acc_b) : nullptr;
     hipError_t e = hipSuccess;
     if (d_acc) e = hipMemsetAsync(d_acc, 0, acc_b, c->stream);
+    if (d_slots && e == hipSuccess) e = hipMemcpy(d_slots, slots.data(), slots_b, hipMemcpyHostToDevice);
     if (!ems.empty() && e == hipSuccess) e = hipMemcpy(d_ems, ems.data(), ems.size() * sizeof(Emitter), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_rad, rad.data(), rad.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
@@ -934,6 +999,10 @@ static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_
         GradConst gc;
         gc.g_s = g_s; gc.g_t = g_t; gc.em_radiance = d_rad;
         gc.steady_scale = rc.sample_scale; gc.transient_scale = rc.sample_scale;
+        if (grad_tints)
+            e = launch_grad_tint(s->dev, d_ems, s->cam, f, rc, gc, p->pixel_begin, n_pixels, p->spp_begin, chunk, d_partial, grid, lds,
+                                 scene_lds, grad_materials, grad_emitters, n_tints, d_slots, grad_tints, c->stream);
+        else
         e = launch_grad(s->dev, d_ems, s->cam, f, rc, gc, p->pixel_begin, n_pixels, p->spp_begin, chunk, d_partial, grid, lds,
                         scene_lds, grad_materials, grad_emitters, c->stream, tier, n_tx, d_acc, grad_texels, nlos ? &nlos_unit : nullptr);
     }
@@ -954,6 +1023,12 @@ int mtr_render_grad_tex(mtr_scene *s, const mtr_render_params *p, const float *g
                         float *grad_materials, float *grad_emitters, float *grad_texels)
 {
     return render_grad(s, p, g_s, g_t, grad_materials, grad_emitters, grad_texels);
+}
+
+int mtr_render_grad_tint(mtr_scene *s, const mtr_render_params *p, const float *g_s, const float *g_t,
+                         float *grad_materials, float *grad_emitters, float *grad_texels, float *grad_tints)
+{
+    return render_grad(s, p, g_s, g_t, grad_materials, grad_emitters, grad_texels, grad_tints);
 }
 
 // mtr_render_fwd (ABI 18): the refusals, shared with mtr_render_fwd_tier
@@ -980,8 +1055,9 @@ int mtr_render_fwd_tier(const mtr_scene *s, const mtr_render_params *p, uint32_t
     return MTR_OK;
 }
 
-int mtr_render_fwd(mtr_scene *s, const mtr_render_params *p, const float *tan_materials, const float *tan_emitters,
-                   const float *tan_texels, float *steady_hw3, float *transient_hwt3)
+// mtr_render_fwd (tan_tints == nullptr) and mtr_render_fwd_tint
+static int render_fwd(mtr_scene *s, const mtr_render_params *p, const float *tan_materials, const float *tan_emitters,
+                      const float *tan_texels, const float *tan_tints, float *steady_hw3, float *transient_hwt3)
 {
     if (!s || !p || !tan_materials || (s->dev.n_ems && !tan_emitters) || !steady_hw3 || !transient_hwt3)
         return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_render_fwd: NULL argument");
@@ -991,6 +1067,14 @@ int mtr_render_fwd(mtr_scene *s, const mtr_render_params *p, const float *tan_ma
     const uint32_t n_pixels = p->pixel_end - p->pixel_begin;
     if (n_pixels == 0u) return MTR_OK;
     HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<int32_t> slots;
+    if (tan_tints) {
+        const uint32_t n_m = s->dev.n_mats;
+        std::vector<mtr_material> mats(n_m);
+        slots.assign(2u * (size_t)n_m + 2u, -1);
+        if (n_m) HIP_TRY(c, hipMemcpy(mats.data(), s->dev.mats, n_m * sizeof(mtr_material), hipMemcpyDeviceToHost));
+        if (tint_slot_table(mats.data(), n_m, slots.data()) == 0u) tan_tints = nullptr;
+    }
     FwdPlan pl{};
     if (!fwd_plan(s->dev, f, n_pixels, p->spp_total, c->n_cu, pl))
         return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_fwd: the traversal stack and the staged scene exceed LDS");
@@ -1002,18 +1086,25 @@ int mtr_render_fwd(mtr_scene *s, const mtr_render_params *p, const float *tan_ma
     for (size_t i = 0; i < ems.size(); ++i)
         for (int k = 0; k < 3; ++k) { rad[3u * i + k] = ems[i].radiance[k]; ems[i].radiance[k] = 1.0f; }
     const size_t ems_b = ((size_t)n_e * sizeof(Emitter) + 255u) & ~(size_t)255u;
+    const size_t rad_b = (rad.size() * sizeof(float) + 255u) & ~(size_t)255u;
     unsigned char *ws = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&ws, ems_b + rad.size() * sizeof(float)));
+    HIP_TRY(c, hipMalloc((void **)&ws, ems_b + rad_b + (tan_tints ? slots.size() * sizeof(int32_t) : 0u)));
     Emitter *d_ems = (Emitter *)ws;
     float *d_rad = (float *)(ws + ems_b);
+    int32_t *d_slots = (int32_t *)(ws + ems_b + rad_b);
     hipError_t e = hipSuccess;
-    if (n_e) e = hipMemcpy(d_ems, ems.data(), n_e * sizeof(Emitter), hipMemcpyHostToDevice);
+    if (tan_tints) e = hipMemcpy(d_slots, slots.data(), slots.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (n_e && e == hipSuccess) e = hipMemcpy(d_ems, ems.data(), n_e * sizeof(Emitter), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_rad, rad.data(), rad.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const RenderConst rc = make_render_const(*p, f, n_e);
         FwdConst fc;
         fc.em_radiance = d_rad; fc.tan_mats = tan_materials; fc.tan_ems = n_e ? tan_emitters : d_rad;
         fc.tan_texels = (s->n_texels && s->dev.texels) ? tan_texels : nullptr;
+        if (tan_tints)
+            e = launch_fwd_tint(s->dev, d_ems, s->cam, f, rc, fc, p->pixel_begin, p->pixel_end, p->spp_total, pl, d_slots, tan_tints,
+                                steady_hw3, transient_hwt3, c->stream);
+        else
         e = launch_fwd(s->dev, d_ems, s->cam, f, rc, fc, p->pixel_begin, p->pixel_end, p->spp_total, pl, steady_hw3, transient_hwt3, c->stream);
     }
     const hipError_t e_sync = hipStreamSynchronize(c->stream);
@@ -1021,6 +1112,18 @@ int mtr_render_fwd(mtr_scene *s, const mtr_render_params *p, const float *tan_ma
     HIP_TRY(c, e);
     HIP_TRY(c, e_sync);
     return MTR_OK;
+}
+
+int mtr_render_fwd(mtr_scene *s, const mtr_render_params *p, const float *tan_materials, const float *tan_emitters,
+                   const float *tan_texels, float *steady_hw3, float *transient_hwt3)
+{
+    return render_fwd(s, p, tan_materials, tan_emitters, tan_texels, nullptr, steady_hw3, transient_hwt3);
+}
+
+int mtr_render_fwd_tint(mtr_scene *s, const mtr_render_params *p, const float *tan_materials, const float *tan_emitters,
+                        const float *tan_texels, const float *tan_tints, float *steady_hw3, float *transient_hwt3)
+{
+    return render_fwd(s, p, tan_materials, tan_emitters, tan_texels, tan_tints, steady_hw3, transient_hwt3);
 }
 
 int mtr_counters_reset(mtr_ctx *c)

@@ -29,22 +29,43 @@ struct FwdConst {
     const float *tan_texels;   // [n_texels * 3]: dt, all textures in scene order (mtr_scene_texture_layout); null: no texel tangents
 };
 
+// The tint hook of fwd_walk (ABI 19, mtr_render_fwd_tint; the transpose of mtr_grad.h's): tint(m, which) answers the tangent ds of
+// `specular_reflectance` (which 0) or `specular_transmittance` (which 1) of material m, three floats, or null.  At a vertex on a
+// conductor or a dielectric interface the emitter-sampling term uses  D + ds_nee / s_nee  (the lobe evaluated for the shadow
+// direction) and the continued path  D + ds_sampled / s_sampled  (the lobe that was sampled); zero rule as for albedos.  The default
+// answers nothing and compiles the tint code out (kOn).
+struct NoTintTan {
+    static constexpr bool kOn = false;
+    MTR_HD const float *operator()(uint32_t, uint32_t) const { return nullptr; }
+};
+MTR_HD d3 plus_tint(d3 D, const mtr_material &m, uint32_t which, const float *ds)
+{
+    const float *s = which ? m.c2 : m.c;
+    if (ds) {
+        if (s[0] != 0.0f) D.x += (double)ds[0] / (double)s[0];
+        if (s[1] != 0.0f) D.y += (double)ds[1] / (double)s[1];
+        if (s[2] != 0.0f) D.z += (double)ds[2] / (double)s[2];
+    }
+    return D;
+}
+
 // Sink: splat(fx, fy, opl, dc) receives every non-zero term's tangent (before the sample scale), steady(fx, fy, sum) the lane's f32
 // sum of them at the end of its path.
-template <bool ROUGH, class Stack, class Sink>
-MTR_HD void fwd_walk(Path p, const SceneView &sc, const Film &film, const RenderConst &rc, const FwdConst &fc, Stack &st, Sink &sink)
+template <bool ROUGH, class Stack, class Sink, class Tint = NoTintTan>
+MTR_HD void fwd_walk(Path p, const SceneView &sc, const Film &film, const RenderConst &rc, const FwdConst &fc, Stack &st, Sink &sink,
+                     Tint tint = Tint())
 {
     NullGradSink ns;
     const bool unwarp = (rc.flags & MTR_FLAG_CAMERA_UNWARP) != 0u;
     const uint32_t fx = p.px - film.crop_x, fy = p.py - film.crop_y;
     d3 D = { 0.0, 0.0, 0.0 };
     f3 sum = mk(0, 0, 0);
-    // dc of the term c_unit lit by emitter e, at optical path length opl
-    auto term = [&](f3 cu, uint32_t e, float opl) {
+    // dc of the term c_unit lit by emitter e, at optical path length opl, with the log-derivative Dv
+    auto term = [&](f3 cu, uint32_t e, float opl, const d3 &Dv) {
         const float *L = fc.em_radiance + 3u * e, *dL = fc.tan_ems + 3u * e;
-        const f3 dc = mk((float)((double)cu.x * ((double)L[0] * D.x + (double)dL[0])),
-                         (float)((double)cu.y * ((double)L[1] * D.y + (double)dL[1])),
-                         (float)((double)cu.z * ((double)L[2] * D.z + (double)dL[2])));
+        const f3 dc = mk((float)((double)cu.x * ((double)L[0] * Dv.x + (double)dL[0])),
+                         (float)((double)cu.y * ((double)L[1] * Dv.y + (double)dL[1])),
+                         (float)((double)cu.z * ((double)L[2] * Dv.z + (double)dL[2])));
         if (dc.x != 0.0f || dc.y != 0.0f || dc.z != 0.0f) {
             sum = mk(sum.x + dc.x, sum.y + dc.y, sum.z + dc.z);
             sink.splat(fx, fy, opl, dc);
@@ -61,7 +82,7 @@ MTR_HD void fwd_walk(Path p, const SceneView &sc, const Film &film, const Render
         shade_hit<ROUGH>(p, h, sc, film, rc, ns, pd, shadow, &hc, EmitterPickTo{ &e_sampled });
         const bool valid = h.prim >= 0;
         // emission (transientpath.py:166-180), at the distance of this vertex, with D before this vertex
-        if (valid && hc.em_plus1 != 0u) term(pd.Le, hc.em_plus1 - 1u, p.dist);
+        if (valid && hc.em_plus1 != 0u) term(pd.Le, hc.em_plus1 - 1u, p.dist, D);
         // the BSDF factor of this vertex is part of its emitter-sampling term and of every later term
         if (valid && pd.active_next) {
             const mtr_material &m = sc.mats[hc.mat];
@@ -88,20 +109,35 @@ MTR_HD void fwd_walk(Path p, const SceneView &sc, const Film &film, const Render
         bool occluded = false;
         if (pd.has_shadow) occluded = traverse<true>(sc, shadow.o, shadow.d, shadow.tmax, st).prim >= 0;
         // emitter sampling (:188-218), at distance + ds.dist * eta, with D after this vertex
-        if (pd.has_shadow && !occluded) term(pd.Lr, e_sampled, pd.opl);
+        bool tinted = false;
+        if constexpr (Tint::kOn) tinted = valid && pd.active_next && bsdf_has_tints(sc.mats[hc.mat].type);
+        if (pd.has_shadow && !occluded) {
+            if (tinted) {
+                if constexpr (Tint::kOn) {
+                    const mtr_material &m = sc.mats[hc.mat];
+                    const uint32_t lobe = tint_of_lobe(m.type, hc.wi.z, shadow_cos(shadow, hc.sp, hc.sn));
+                    term(pd.Lr, e_sampled, pd.opl, plus_tint(D, m, lobe, tint(hc.mat, lobe)));
+                }
+            } else term(pd.Lr, e_sampled, pd.opl, D);
+        }
         alive = shade_finish<ROUGH>(p, h, occluded, pd, sc, film, rc, ns);
+        if constexpr (Tint::kOn) if (tinted) {
+            const mtr_material &m = sc.mats[hc.mat];
+            const uint32_t lobe = tint_of_lobe(m.type, hc.wi.z, dot(p.ray.d, hc.sn));
+            D = plus_tint(D, m, lobe, tint(hc.mat, lobe));
+        }
     }
     if (sum.x != 0.0f || sum.y != 0.0f || sum.z != 0.0f) sink.steady(fx, fy, sum);
 }
 
 // lane (pixel, s) of the render: identity = RNG identity (lane = pixel * spp_total + s), as every primal organisation
-template <bool ROUGH, class Stack, class Sink>
+template <bool ROUGH, class Stack, class Sink, class Tint = NoTintTan>
 MTR_HD void fwd_lane(const SceneView &sc, const Camera &cam, const Film &film, const RenderConst &rc, const FwdConst &fc,
-                     uint32_t pixel, uint32_t s, Stack &st, Sink &sink)
+                     uint32_t pixel, uint32_t s, Stack &st, Sink &sink, Tint tint = Tint())
 {
     Path p;
     path_begin(p, cam, film, rc, pixel, s);
-    fwd_walk<ROUGH>(p, sc, film, rc, fc, st, sink);
+    fwd_walk<ROUGH>(p, sc, film, rc, fc, st, sink, tint);
 }
 
 } // namespace mtr

@@ -24,43 +24,6 @@ namespace mtr {
 
 namespace {
 
-__device__ __forceinline__ void add3(float *p, f3 v)
-{
-    if (v.x != 0.0f) atomicAdd(p, v.x);
-    if (v.y != 0.0f) atomicAdd(p + 1, v.y);
-    if (v.z != 0.0f) atomicAdd(p + 2, v.z);
-}
-
-// rows tier: the lane's pixel row in LDS — [bins][3], then the three steady words
-struct RowSink {
-    float *row; const Film *film; float scale;
-    __device__ __forceinline__ void splat(uint32_t, uint32_t, float opl, f3 dc) const
-    {
-        const int32_t bin = film_bin(*film, opl);
-        if (bin >= 0) add3(row + 3u * (uint32_t)bin, mk(dc.x * scale, dc.y * scale, dc.z * scale));
-    }
-    __device__ __forceinline__ void steady(uint32_t, uint32_t, f3 sum) const
-    {
-        add3(row + 3u * film->bins, mk(sum.x * scale, sum.y * scale, sum.z * scale));
-    }
-};
-
-// global tier: atomics onto the zeroed outputs
-struct GlobalSink {
-    float *transient, *steady_out; const Film *film; float scale;
-    __device__ __forceinline__ void splat(uint32_t fx, uint32_t fy, float opl, f3 dc) const
-    {
-        if (!((fx < film->width) & (fy < film->height))) return;
-        const int32_t bin = film_bin(*film, opl);
-        if (bin >= 0) add3(transient + 3u * (((size_t)fy * film->width + fx) * film->bins + (uint32_t)bin), mk(dc.x * scale, dc.y * scale, dc.z * scale));
-    }
-    __device__ __forceinline__ void steady(uint32_t fx, uint32_t fy, f3 sum) const
-    {
-        if (!((fx < film->width) & (fy < film->height))) return;
-        add3(steady_out + 3u * ((size_t)fy * film->width + fx), mk(sum.x * scale, sum.y * scale, sum.z * scale));
-    }
-};
-
 template <bool SCENE_LDS, bool EXT, bool ROWS>
 __global__ void __launch_bounds__(kBlock) k_fwd_paths(const FwdArgs a)
 {
@@ -166,6 +129,13 @@ constexpr uint32_t kLdsCu = 160u * 1024u;
 
 } // namespace
 
+hipError_t launch_fwd_zero(const FwdArgs &a, hipStream_t stream)
+{
+    const uint32_t n_pixels = a.pixel_end - a.pixel_begin;
+    hipLaunchKernelGGL(k_fwd_zero, dim3(n_pixels < 65535u ? n_pixels : 65535u), dim3(kBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
 uint32_t fwd_tier(const SceneDev &sc, const Film &film)
 {
     const uint32_t scene_b = lds_scene_bytes(sc);
@@ -230,9 +200,7 @@ hipError_t launch_fwd(const SceneDev &sc, const Emitter *ems_unit, const Camera 
     if (pl.tier == MTR_FWD_ROWS)
         return sl ? (ext ? launch_paths<true, true, true>(a, grid, pl.lds, stream) : launch_paths<true, false, true>(a, grid, pl.lds, stream))
                   : (ext ? launch_paths<false, true, true>(a, grid, pl.lds, stream) : launch_paths<false, false, true>(a, grid, pl.lds, stream));
-    const uint32_t n_pixels = pixel_end - pixel_begin;
-    hipLaunchKernelGGL(k_fwd_zero, dim3(n_pixels < 65535u ? n_pixels : 65535u), dim3(kBlock), 0, stream, a);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_fwd_zero(a, stream);
     if (e != hipSuccess) return e;
     return sl ? (ext ? launch_paths<true, true, false>(a, grid, pl.lds, stream) : launch_paths<true, false, false>(a, grid, pl.lds, stream))
               : (ext ? launch_paths<false, true, false>(a, grid, pl.lds, stream) : launch_paths<false, false, false>(a, grid, pl.lds, stream));

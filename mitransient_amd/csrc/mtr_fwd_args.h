@@ -20,6 +20,44 @@ struct FwdArgs {
     float *transient;             // (H, W, T, 3)
 };
 
+// the film sinks of fwd_walk in the kernels (mtr_fwd.hip, mtr_tint.hip)
+__device__ __forceinline__ void add3(float *p, f3 v)
+{
+    if (v.x != 0.0f) atomicAdd(p, v.x);
+    if (v.y != 0.0f) atomicAdd(p + 1, v.y);
+    if (v.z != 0.0f) atomicAdd(p + 2, v.z);
+}
+
+// rows tier: the lane's pixel row in LDS — [bins][3], then the three steady words
+struct RowSink {
+    float *row; const Film *film; float scale;
+    __device__ __forceinline__ void splat(uint32_t, uint32_t, float opl, f3 dc) const
+    {
+        const int32_t bin = film_bin(*film, opl);
+        if (bin >= 0) add3(row + 3u * (uint32_t)bin, mk(dc.x * scale, dc.y * scale, dc.z * scale));
+    }
+    __device__ __forceinline__ void steady(uint32_t, uint32_t, f3 sum) const
+    {
+        add3(row + 3u * film->bins, mk(sum.x * scale, sum.y * scale, sum.z * scale));
+    }
+};
+
+// global tier: atomics onto the zeroed outputs
+struct GlobalSink {
+    float *transient, *steady_out; const Film *film; float scale;
+    __device__ __forceinline__ void splat(uint32_t fx, uint32_t fy, float opl, f3 dc) const
+    {
+        if (!((fx < film->width) & (fy < film->height))) return;
+        const int32_t bin = film_bin(*film, opl);
+        if (bin >= 0) add3(transient + 3u * (((size_t)fy * film->width + fx) * film->bins + (uint32_t)bin), mk(dc.x * scale, dc.y * scale, dc.z * scale));
+    }
+    __device__ __forceinline__ void steady(uint32_t fx, uint32_t fy, f3 sum) const
+    {
+        if (!((fx < film->width) & (fy < film->height))) return;
+        add3(steady_out + 3u * ((size_t)fy * film->width + fx), mk(sum.x * scale, sum.y * scale, sum.z * scale));
+    }
+};
+
 // most workgroups of k_fwd_paths that a compute unit is asked to hold: what its registers allow (132 - 163 VGPRs: three waves per
 // SIMD, a workgroup being one wave on each)
 constexpr int kFwdPerCu = 3;
@@ -40,5 +78,8 @@ bool fwd_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t 
 hipError_t launch_fwd(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
                       const FwdConst &fc, uint32_t pixel_begin, uint32_t pixel_end, uint32_t spp, const FwdPlan &pl,
                       float *steady, float *transient, hipStream_t stream);
+
+// global tier: k_fwd_zero over the launch's pixels (clears their rows and steady words)
+hipError_t launch_fwd_zero(const FwdArgs &a, hipStream_t stream);
 
 } // namespace mtr

@@ -62,6 +62,48 @@ struct NoTexelGrad {
     MTR_HD void operator()(uint32_t, f3) const {}
 };
 
+// The tint hook of grad_walk (ABI 19, mtr_render_grad_tint): the constant RGB `specular_reflectance` (which 0, mtr_material::c) and
+// `specular_transmittance` (which 1, ::c2) of conductor, roughconductor, dielectric, thindielectric and roughdielectric.  The tint
+// multiplies the BSDF weight or value linearly and no sampling decision reads it (lobe choice is by Fresnel, the visible normal by
+// alpha, the pdfs carry no tint), so a term stays multilinear in the tints:  d loss / d s = sum_c w_c (.) c (.) k_s(c) / s,  k_s(c) the
+// vertices at which the factor s is part of c.  WHICH tint a vertex contributes depends on the lobe: the vertex's emitter-sampling
+// term (rough lobes only) carries the tint of the lobe bsdf_eval_cos evaluates for the shadow direction, every later term the tint
+// of the lobe that was sampled — known after shade_finish, from the side of the new ray (the shading code's own test, ci * co > 0:
+// reflection).  tint(m, which, g) receives the term over its tint, then the remaining sum over the sampled lobe's tint; a channel
+// whose tint is exactly 0 receives 0.  lobes(m, nee, sampled): the two lobes of the vertex for the records of a host build (nee -1:
+// no emitter-sampling term).  The default does nothing and compiles the tint code out (kOn).
+struct NoTintGrad {
+    static constexpr bool kOn = false;
+    MTR_HD void operator()(uint32_t, uint32_t, f3) const {}
+    MTR_HD void lobes(uint32_t, int, int) const {}
+};
+MTR_HD bool bsdf_has_tints(uint32_t type)
+{
+    return type == MTR_BSDF_CONDUCTOR || type == MTR_BSDF_ROUGHCONDUCTOR || type == MTR_BSDF_DIELECTRIC ||
+           type == MTR_BSDF_THINDIELECTRIC || type == MTR_BSDF_ROUGHDIELECTRIC;
+}
+// the tint of the lobe that takes wi (local, cosine ci) to a direction with cosine co about the same normal: conductors reflect;
+// a dielectric interface transmits unless both are on one side (rough_dielectric_eval_pdf's `reflect`)
+MTR_HD uint32_t tint_of_lobe(uint32_t type, float ci, float co)
+{
+    const bool dielectric = type == MTR_BSDF_DIELECTRIC || type == MTR_BSDF_THINDIELECTRIC || type == MTR_BSDF_ROUGHDIELECTRIC;
+    return (dielectric && !(ci * co > 0.0f)) ? 1u : 0u;
+}
+// cosine about the shading normal sn of the direction from the vertex sp to the sampled emitter point, rebuilt from the shadow ray
+// shade_hit emitted (origin offset along the geometric normal, tmax = distance (1 - kShadowEps)): the point to rounding
+MTR_HD float shadow_cos(const Ray &shadow, f3 sp, f3 sn)
+{
+    const float t = shadow.tmax / (1.0f - kShadowEps);
+    const f3 ep = mk(fmaf(shadow.d.x, t, shadow.o.x), fmaf(shadow.d.y, t, shadow.o.y), fmaf(shadow.d.z, t, shadow.o.z));
+    return dot(ep - sp, sn);
+}
+MTR_HD f3 over_tint(const mtr_material &m, uint32_t which, double rx, double ry, double rz)
+{
+    const float *s = which ? m.c2 : m.c;
+    return mk(s[0] != 0.0f ? (float)(rx / (double)s[0]) : 0.0f, s[1] != 0.0f ? (float)(ry / (double)s[1]) : 0.0f,
+              s[2] != 0.0f ? (float)(rz / (double)s[2]) : 0.0f);
+}
+
 // w_c of a contribution of film pixel (fx, fy) at optical path length opl; the bin is the splat's own (film_bin)
 MTR_HD f3 grad_weight(const GradConst &gc, const Film &film, uint32_t fx, uint32_t fy, float opl)
 {
@@ -82,9 +124,10 @@ MTR_HD f3 grad_weight(const GradConst &gc, const Film &film, uint32_t fx, uint32
 // gradients go to acc.add_em(e, w_c (.) c_unit), material gradients to acc.add_mat(m, R / a_m) at each diffuse vertex whose
 // BSDF factor enters the remaining terms.  unwarp: camera_unwarp from bounce 0's own closest hit (as path_bounce).
 // tex: the texel hook (bitmap-textured `diffuse` vertices; extended shading code only: a bitmap implies it).
-template <bool ROUGH, bool REPLAY, class Stack, class Acc, class Tex = NoTexelGrad>
+// tint: the tint hook (vertices on conductors and dielectric interfaces).
+template <bool ROUGH, bool REPLAY, class Stack, class Acc, class Tex = NoTexelGrad, class Tint = NoTintGrad>
 MTR_HD d3 grad_walk(Path p, const SceneView &sc, const Film &film, const RenderConst &rc, const GradConst &gc, Stack &st,
-                    Acc &acc, d3 R, Tex tex = Tex())
+                    Acc &acc, d3 R, Tex tex = Tex(), Tint tint = Tint())
 {
     NullGradSink ns;
     const bool unwarp = (rc.flags & MTR_FLAG_CAMERA_UNWARP) != 0u;
@@ -135,6 +178,8 @@ MTR_HD d3 grad_walk(Path p, const SceneView &sc, const Film &film, const RenderC
                 tex(k.first + (uint32_t)k.i01, g * (k.w0x * k.w1y)); tex(k.first + (uint32_t)k.i11, g * (k.w1x * k.w1y));
             }
         }
+        bool tinted = false; int nee_lobe = -1;
+        if constexpr (Tint::kOn) tinted = REPLAY && valid && pd.active_next && bsdf_has_tints(sc.mats[hc.mat].type);
         bool occluded = false;
         if (pd.has_shadow) occluded = traverse<true>(sc, shadow.o, shadow.d, shadow.tmax, st).prim >= 0;
         // emitter sampling (:188-218), at distance + ds.dist * eta
@@ -150,22 +195,35 @@ MTR_HD d3 grad_walk(Path p, const SceneView &sc, const Film &film, const RenderC
                 acc.add_em(e, mk(w.x * cu.x, w.y * cu.y, w.z * cu.z));
                 acc.term(1u, e, pd.opl, cu);
             } else { R.x += cx; R.y += cy; R.z += cz; }
+            if constexpr (Tint::kOn) if (tinted) {
+                // the term carries the tint of the lobe evaluated for the shadow direction
+                const mtr_material &m = sc.mats[hc.mat];
+                nee_lobe = (int)tint_of_lobe(m.type, hc.wi.z, shadow_cos(shadow, hc.sp, hc.sn));
+                tint(hc.mat, (uint32_t)nee_lobe, over_tint(m, (uint32_t)nee_lobe, cx, cy, cz));
+            }
         }
         alive = shade_finish<ROUGH>(p, h, occluded, pd, sc, film, rc, ns);
+        if constexpr (Tint::kOn) if (tinted) {
+            // ... and every later term the tint of the lobe that was sampled: the side of the new ray
+            const mtr_material &m = sc.mats[hc.mat];
+            const uint32_t lobe = tint_of_lobe(m.type, hc.wi.z, dot(p.ray.d, hc.sn));
+            tint(hc.mat, lobe, over_tint(m, lobe, R.x, R.y, R.z));
+            tint.lobes(hc.mat, nee_lobe, (int)lobe);
+        }
     }
     return R;
 }
 
 // lane (pixel, s) of the render: identity = RNG identity (lane = pixel * spp_total + s), as every primal organisation
-template <bool ROUGH, class Stack, class Acc, class Tex = NoTexelGrad>
+template <bool ROUGH, class Stack, class Acc, class Tex = NoTexelGrad, class Tint = NoTintGrad>
 MTR_HD void grad_lane(const SceneView &sc, const Camera &cam, const Film &film, const RenderConst &rc, const GradConst &gc,
-                      uint32_t pixel, uint32_t s, Stack &st, Acc &acc, Tex tex = Tex())
+                      uint32_t pixel, uint32_t s, Stack &st, Acc &acc, Tex tex = Tex(), Tint tint = Tint())
 {
     Path p;
     path_begin(p, cam, film, rc, pixel, s);
     const d3 zero = { 0.0, 0.0, 0.0 };
     const d3 A = grad_walk<ROUGH, false>(p, sc, film, rc, gc, st, acc, zero);
-    grad_walk<ROUGH, true>(p, sc, film, rc, gc, st, acc, A, tex);
+    grad_walk<ROUGH, true>(p, sc, film, rc, gc, st, acc, A, tex, tint);
 }
 
 // d loss / d a of a `diffuse` material with a constant reflectance from the sum r its factor is part of: r / a per channel, 0 for

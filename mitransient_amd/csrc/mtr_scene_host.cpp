@@ -351,6 +351,19 @@ bool colours_are_grey(const mtr_material *mats, uint32_t n_mats, const Emitter *
     return grey;
 }
 
+uint32_t tint_slot_table(const mtr_material *mats, uint32_t n_mats, int32_t *slots)
+{
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < n_mats; ++i) {
+        const uint32_t t = mats[i].type;
+        const bool transmits = t == MTR_BSDF_DIELECTRIC || t == MTR_BSDF_THINDIELECTRIC || t == MTR_BSDF_ROUGHDIELECTRIC;
+        const bool reflects = transmits || t == MTR_BSDF_CONDUCTOR || t == MTR_BSDF_ROUGHCONDUCTOR;
+        const int32_t r = reflects ? (int32_t)n++ : -1, x = transmits ? (int32_t)n++ : -1;
+        if (slots) { slots[2u * i] = r; slots[2u * i + 1u] = x; }
+    }
+    return n;
+}
+
 uint32_t traits_with_laser(uint32_t traits, bool grey_scene, const float laser_irradiance[3])
 {
     return (grey_scene && eq3(laser_irradiance)) ? (traits | kTrGrey) : (traits & ~kTrGrey);

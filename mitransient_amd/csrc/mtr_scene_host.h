@@ -48,6 +48,11 @@ void classify_scene(const mtr_scene_desc &d, HostScene &s);
 // kTrGrey of the NLOS tier: the scene's colours and the laser's irradiance
 uint32_t traits_with_laser(uint32_t traits, bool grey_scene, const float laser_irradiance[3]);
 
+// the tint slots of mtr_scene_tint_layout (ABI 19): materials in table order, `specular_reflectance` of a conductor, roughconductor,
+// dielectric, thindielectric or roughdielectric, then `specular_transmittance` of the three dielectric types.  slots (may be null):
+// two words per material, the slot of its reflectance and of its transmittance or -1.  Returns the number of slots.
+uint32_t tint_slot_table(const mtr_material *mats, uint32_t n_mats, int32_t *slots);
+
 // NLOS tier tables (TransientNLOSPath.prepare, transientnlospath.py:251-292): shape / face distributions,
 // rectangle normals, triangles in ORIGINAL order for Mesh::sample_position, projector constants
 struct HostNlos {

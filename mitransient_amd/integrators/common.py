@@ -378,11 +378,17 @@ class TransientADIntegrator:
         n_m, n_e = max(1, sd.n_materials), max(1, sd.n_emitters)
         tm = np.zeros((n_m, 3), np.float32)
         te = np.zeros((n_e, 3), np.float32)
-        tx = None
+        tx = tt = None
         for k, t in tangents.items():
             kind, i = keys[k]
             t = np.asarray(t.detach().cpu() if hasattr(t, "detach") else t, dtype=np.float32)
-            if kind == "texture":
+            if kind == "tint":
+                if t.size not in (1, 3):
+                    raise NotImplementedError(f"render_forward: {k}: a tangent of 1 or 3 elements, got shape {t.shape}")
+                if tt is None:
+                    tt = np.zeros((max(1, scene.n_tint_slots(sensor)), 3), np.float32)
+                tt[i] += t.reshape(-1)
+            elif kind == "texture":
                 if tx is None:
                     tx = np.zeros((max(1, int(first[-1])), 3), np.float32)
                 tx[int(first[i]):int(first[i + 1])] += t.reshape(-1, 3)
@@ -406,6 +412,12 @@ class TransientADIntegrator:
         steady = torch.zeros((H, W, 3), dtype=torch.float32, device=dev)
         transient = torch.zeros((H, W, T, 3), dtype=torch.float32, device=dev)
         p = self.render_params(film, sampler.seed_value(), spp)
+        if tt is not None:
+            d_tt = torch.from_numpy(tt).to(dev)
+            ctx.check(ctx.lib.mtr_render_fwd_tint(handle, C.byref(p), C.c_void_p(d_tm.data_ptr()), C.c_void_p(d_te.data_ptr()),
+                                                  C.c_void_p(d_tx.data_ptr()) if d_tx is not None else None, C.c_void_p(d_tt.data_ptr()),
+                                                  C.c_void_p(steady.data_ptr()), C.c_void_p(transient.data_ptr())), "mtr_render_fwd_tint")
+            return TensorXf(steady[:ch, :cw].contiguous()), TensorXf(transient)
         ctx.check(ctx.lib.mtr_render_fwd(handle, C.byref(p), C.c_void_p(d_tm.data_ptr()), C.c_void_p(d_te.data_ptr()),
                                          C.c_void_p(d_tx.data_ptr()) if d_tx is not None else None,
                                          C.c_void_p(steady.data_ptr()), C.c_void_p(transient.data_ptr())), "mtr_render_fwd")
@@ -414,6 +426,7 @@ class TransientADIntegrator:
     # -- common.py:325-409 -----------------------------------------------------
     def check_grad_(self, scene, sensor, params):
         """the refusals of the reverse mode (ValueError), all of them before any GPU work"""
+        import numpy as np
         from ..films.phasor_hdr_film import PhasorHDRFilm
         from .transientnlospath import TransientNLOSPath
         v = variant.get() or ""
@@ -441,9 +454,11 @@ class TransientADIntegrator:
         if film.exhaustive_scan:
             raise ValueError("transient_hdr_film with exhaustive_scan: differentiable rendering is not available")
         wanted = [k for k, val in (params or {}).items() if _wants_grad(val)]
-        scene.ensure_own_records([k for k in wanted if k in scene.param_keys()], sensor)
+        scene.ensure_own_records([k for k in wanted if k in scene.param_keys()], sensor)     # (albedo and tint keys)
         keys = dict(scene.grad_keys(sensor))
         keys.update({k: ("texture", i) for k, i in scene.texture_keys(sensor).items()})
+        if not nlos:       # the specular tints (mtr_render_grad_tint): transient_path only
+            keys.update({k: ("tint", i) for k, i in scene.tint_keys(sensor).items()})
         seen = {}
         for k, val in (params or {}).items():
             if not _wants_grad(val):
@@ -451,7 +466,10 @@ class TransientADIntegrator:
             if k not in keys:
                 raise ValueError(f"{k}: not a differentiable parameter (the constant reflectance of a diffuse BSDF, the texels of a "
                                  f"bitmap that only diffuse reflectances use, the constant radiance of an area / angulararea "
-                                 f"emitter and the constant irradiance of a NLOS scene's projector are: {sorted(keys)})")
+                                 f"emitter, the constant irradiance of a NLOS scene's projector and, with transient_path, the "
+                                 f"constant specular tints of conductors and dielectrics are: {sorted(keys)})")
+            if keys[k][0] == "tint" and int(np.prod(tuple(val.shape))) not in (1, 3):
+                raise ValueError(f"{k}: a tint of 1 or 3 elements, got shape {tuple(val.shape)}")
             if keys[k][0] == "texture":
                 if tuple(val.shape) != tuple(scene.data(sensor).textures[keys[k][1]].shape):
                     raise ValueError(f"{k}: expected texels of shape {tuple(scene.data(sensor).textures[keys[k][1]].shape)}, "
@@ -517,11 +535,24 @@ class TransientADIntegrator:
             first = np.cumsum([0] + [int(t.shape[0] * t.shape[1]) for t in sd.textures])
             gx = torch.zeros((int(first[-1]), 3), dtype=torch.float32, device=dev)
             px = torch.empty_like(gx)
+        # tint gradients only when a tint key asks: mtr_render_grad_tint, every slot of mtr_scene_tint_layout
+        tinted = any(keys[k][0] == "tint" for k in wanted)
+        if tinted:
+            gtint = torch.zeros((max(1, scene.n_tint_slots(sensor)), 3), dtype=torch.float32, device=dev)
+            ptint = torch.empty_like(gtint)
         multi = len(samplers_spps) > 1
         for sampler_i, spp_i in samplers_spps:
             p = self.render_params(film, sampler_i.seed_value(), spp_i if multi else total_spp, 0, spp_i, 0, None,
                                    spp_scale=total_spp if multi else 0)
-            if textured:
+            if tinted:
+                ctx.check(ctx.lib.mtr_render_grad_tint(handle, C.byref(p), C.c_void_p(gs_full.data_ptr()), C.c_void_p(g_t.data_ptr()),
+                                                       C.c_void_p(pm.data_ptr()), C.c_void_p(pe.data_ptr()),
+                                                       C.c_void_p(px.data_ptr()) if textured else None, C.c_void_p(ptint.data_ptr())),
+                          "mtr_render_grad_tint")
+                gtint += ptint
+                if textured:
+                    gx += px
+            elif textured:
                 ctx.check(ctx.lib.mtr_render_grad_tex(handle, C.byref(p), C.c_void_p(gs_full.data_ptr()), C.c_void_p(g_t.data_ptr()),
                                                       C.c_void_p(pm.data_ptr()), C.c_void_p(pe.data_ptr()), C.c_void_p(px.data_ptr())),
                           "mtr_render_grad_tex")
@@ -536,6 +567,8 @@ class TransientADIntegrator:
             kind, i = keys[k]
             if kind == "texture":
                 out[k] = gx[int(first[i]):int(first[i + 1])].reshape(tuple(sd.textures[i].shape)).clone()
+            elif kind == "tint":
+                out[k] = gtint[i].clone()
             else:
                 out[k] = (gm if kind == "material" else ge)[i].clone()
         return out

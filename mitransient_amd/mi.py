@@ -254,10 +254,13 @@ class Scene:
     # -- differentiable parameters (mi.traverse keys of mtr_render_grad) ------------------------------------------
     def param_keys(self):
         """{key: 3 floats}: the differentiable parameters and their values, from the dictionary (nothing is flattened)"""
-        from .scene import param_locations, rgb3
+        from .scene import param_locations, tint_locations, rgb3
         if self.geometry_ is not None:
             return {}
         out = {k: list(self.param_values_.get(k, rgb3(v))) for k, (_, _, v) in param_locations(self.dict_).items()}
+        # ... and the specular tints the dictionary sets (<bsdf>.specular_reflectance.value / .specular_transmittance.value)
+        if self.approximate_materials in (False, None, "textures"):
+            out.update({k: list(self.param_values_.get(k, rgb3(v))) for k, (_, _, v) in tint_locations(self.dict_).items()})
         k = self.laser_key()
         if k is not None:
             out[k] = [float(x) for x in self.emitters_[0].irradiance]
@@ -278,6 +281,22 @@ class Scene:
         if k is None or sd.nlos is None:
             return sd.grad_keys
         return {**sd.grad_keys, k: ("emitter", 0)}
+
+    def tint_keys(self, sensor=0):
+        """{key: slot}: the constant specular tints mtr_render_grad_tint / mtr_render_fwd_tint differentiate, resolved to the slots
+        of mtr_scene_tint_layout: ``specular_reflectance.value`` / ``specular_transmittance.value`` of a conductor,
+        roughconductor, dielectric, thindielectric or roughdielectric whose dictionary sets the property.  Empty on a NLOS scene."""
+        from .scene import tint_slot_table
+        sd = self.data(sensor)
+        if sd.nlos is not None:
+            return {}
+        slots = tint_slot_table(sd.materials, sd.n_materials)
+        return {k: slots[mw] for k, mw in sd.tint_params.items()}
+
+    def n_tint_slots(self, sensor=0):
+        from .scene import tint_slot_table
+        sd = self.data(sensor)
+        return len(tint_slot_table(sd.materials, sd.n_materials))
 
     def texture_locations_(self):
         from .scene import texture_locations
@@ -346,9 +365,12 @@ class Scene:
         shape from then on (only when one of its keys is set or differentiated: other scenes keep their tables as they are)"""
         if self.own_materials_:
             return
-        gk = self.data(sensor).grad_keys
-        recs = list(gk.values())
-        if any(k in gk and recs.count(gk[k]) > 1 for k in keys):
+        sd = self.data(sensor)
+        gk = {**{k: i for k, (kind, i) in sd.grad_keys.items() if kind == "material"},
+              **{k: m for k, (m, _) in sd.tint_params.items()}}
+        # (records are counted per parameter: the two tints of one dielectric share their record and need no copy)
+        recs = [(m, k.rsplit(".", 2)[-2]) for k, m in gk.items()]
+        if any(k in gk and recs.count((gk[k], k.rsplit(".", 2)[-2])) > 1 for k in keys):
             self.own_materials_ = True
             for key in list(self._data):
                 del self._data[key]
@@ -374,6 +396,12 @@ class Scene:
             arr = sd.materials[i].a if kind == "material" else sd.emitters[i].radiance
             for c in range(3):
                 arr[c] = v[c]
+        for k, v in self.param_values_.items():
+            if k in sd.tint_params:
+                m, which = sd.tint_params[k]
+                arr = sd.materials[m].c2 if which else sd.materials[m].c
+                for c in range(3):
+                    arr[c] = v[c]
 
     def set_param(self, key, value):
         """a differentiable parameter's new value (3 floats): the flattened tables take it, and the device scenes re-upload their
@@ -402,7 +430,13 @@ class Scene:
             a = np.array([[sd.materials[i].a[c] for c in range(3)] for i in range(max(1, sd.n_materials))], np.float32)
             r = np.array([[sd.emitters[i].radiance[c] for c in range(3)] for i in range(max(1, sd.n_emitters))], np.float32)
             for hkey in [h for h in self._handles if h[0] == skey]:
-                if lib.mtr_scene_set_colors(self._handles[hkey], C.c_void_p(a.ctypes.data), C.c_void_p(r.ctypes.data)) != 0:
+                ok = lib.mtr_scene_set_colors(self._handles[hkey], C.c_void_p(a.ctypes.data), C.c_void_p(r.ctypes.data)) == 0
+                if ok and sd.tint_params and sd.nlos is None:          # ... and the tints (mtr_scene_set_tints; no tint keys on the NLOS tier)
+                    t = np.array([[[m.c[c] for c in range(3)], [m.c2[c] for c in range(3)]]
+                                  for m in sd.materials[:max(1, sd.n_materials)]], np.float32)
+                    t0, t1 = np.ascontiguousarray(t[:, 0]), np.ascontiguousarray(t[:, 1])
+                    ok = lib.mtr_scene_set_tints(self._handles[hkey], C.c_void_p(t0.ctypes.data), C.c_void_p(t1.ctypes.data)) == 0
+                if not ok:
                     lib.mtr_scene_destroy(self._handles.pop(hkey))     # (the NLOS tier: the next render creates the scene again)
                     self._nlos_fp.pop(hkey, None)
 

@@ -1011,6 +1011,8 @@ def flatten_scene(d: Dict[str, Any], film, sensor_dict: Dict[str, Any], base_dir
     # bitmaps by file (what params.update() of a `.data` key replaces) and the `.data` keys of the differentiable ones
     sd.texture_ids = dict(b.texture_cache)
     sd.texture_keys = differentiable_textures(d, b, base_dir) if geometry is None else {}
+    # the constant specular tints by mitsuba key: {key: (material, 0 reflectance | 1 transmittance)}
+    sd.tint_params = differentiable_tints(d, b) if geometry is None else {}
     return sd
 
 
@@ -1072,6 +1074,72 @@ def param_locations(d) -> Dict[str, tuple]:
         if k is not None:
             out[k] = ("material", ("ref", rid), _bsdf_value(v))
     return out
+
+
+_TINT_BSDFS = {"conductor": ("specular_reflectance",), "roughconductor": ("specular_reflectance",),
+               "dielectric": ("specular_reflectance", "specular_transmittance"),
+               "thindielectric": ("specular_reflectance", "specular_transmittance"),
+               "roughdielectric": ("specular_reflectance", "specular_transmittance")}
+
+
+def _bsdf_tint_keys(bd, prefix):
+    """mitsuba's keys of the differentiable tints of a BSDF dictionary: [(key, which, value)] with which 0 for
+    ``specular_reflectance.value``, 1 for ``specular_transmittance.value`` — of a conductor, roughconductor, dielectric,
+    thindielectric or roughdielectric whose dictionary SETS the property to a constant (an unset tint is no parameter, as in
+    mitsuba), ``brdf_0.`` through `twosided`.  `plastic` / `roughplastic` have none: their tint enters lobe sampling."""
+    t = bd.get("type") if isinstance(bd, dict) else None
+    if t in _TINT_BSDFS:
+        return [(prefix + name + ".value", which, _constant_rgb(bd[name])) for which, name in enumerate(_TINT_BSDFS[t])
+                if name in bd and _constant_rgb(bd[name]) is not None]
+    if t == "twosided":
+        inner = [v for k, v in bd.items() if isinstance(v, dict) and k != "type"]
+        if len(inner) == 1 and inner[0].get("type") != "ref":
+            return _bsdf_tint_keys(inner[0], prefix + "brdf_0.")
+    return []
+
+
+def tint_locations(d) -> Dict[str, tuple]:
+    """the tints mtr_render_grad_tint differentiates, from the scene dictionary alone, by mitsuba key: (where, which, value) with
+    where as in param_locations"""
+    shapes = {k: v for k, v in d.items() if isinstance(v, dict) and v.get("type") in _GRAD_SHAPE_TYPES}
+    refs, out = set(), {}
+    for name, sd in shapes.items():
+        b = _shape_bsdf(sd)
+        if b is not None and b.get("type") == "ref":
+            refs.add(b["id"])
+        elif b is not None:
+            for k, which, v in _bsdf_tint_keys(b, f"{name}.bsdf."):
+                out[k] = (("shape", name), which, v)
+    for rid in refs:
+        v = d.get(rid)
+        for k, which, val in (_bsdf_tint_keys(v, f"{rid}.") if isinstance(v, dict) else []):
+            out[k] = (("ref", rid), which, val)
+    return out
+
+
+def tint_slot_table(materials, n_materials):
+    """the slots of mtr_scene_tint_layout (mtr_scene_host.cpp: tint_slot_table): {(material, which): slot}"""
+    refl = (_cabi.MTR_BSDF_CONDUCTOR, _cabi.MTR_BSDF_ROUGHCONDUCTOR, _cabi.MTR_BSDF_DIELECTRIC, _cabi.MTR_BSDF_THINDIELECTRIC,
+            _cabi.MTR_BSDF_ROUGHDIELECTRIC)
+    trans = (_cabi.MTR_BSDF_DIELECTRIC, _cabi.MTR_BSDF_THINDIELECTRIC, _cabi.MTR_BSDF_ROUGHDIELECTRIC)
+    slots = {}
+    for m in range(n_materials):
+        for which, types in enumerate((refl, trans)):
+            if materials[m].type in types:
+                slots[(m, which)] = len(slots)
+    return slots
+
+
+def differentiable_tints(d, b) -> Dict[str, tuple]:
+    """tint_locations resolved to the flattened tables: {key: (material index, which)}"""
+    if b.approx not in (False, None, "textures"):
+        return {}
+    keys = {}
+    for k, ((how, name), which, _) in tint_locations(d).items():
+        m = b.mat_cache.get(("ref", name)) if how == "ref" else b.shape_mat.get(name)
+        if m is not None and (m, which) in tint_slot_table(b.materials, len(b.materials)):
+            keys[k] = (m, which)
+    return keys
 
 
 def _bitmap_id(v, base_dir):
