@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 19
+#define MTR_ABI_VERSION 20
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -475,7 +475,12 @@ int  mtr_render_grad(mtr_scene *, const mtr_render_params *params,
  * The sums are f64 in one of two tiers (mtr_render_grad_tex_tier): in the workgroups' LDS slabs when all texel words fit beside
  * the material / emitter words (bitwise reproducible), by f64 global atomics otherwise (the f32 result can differ in its last
  * bit from run to run: arrival order).
- * (ABI 17) On a NLOS scene a non-NULL grad_texels is MTR_ERR_UNSUPPORTED: texel gradients are for transient_path. */
+ * (ABI 20) A NLOS scene (Single or Confocal capture, as mtr_render_grad) has texel gradients as well, in the same two tiers:
+ * the bitmap-textured `diffuse` vertices of a term — those whose sampling weight is in its throughput, the vertex the term is
+ * emitted at and, under laser sampling, the laser spot — receive as above, the laser spot the term itself over its interpolated
+ * colour.  Hidden geometry and relay wall alike; grad_emitters is (1, 3) as for mtr_render_grad.  (Up to ABI 19 a non-NULL
+ * grad_texels on a NLOS scene was MTR_ERR_UNSUPPORTED.)  mtr_scene_set_texture stays refused on a NLOS scene: create the scene
+ * again (a bitmap enters the scene's classification). */
 int  mtr_render_grad_tex(mtr_scene *, const mtr_render_params *params,
                          const float *grad_steady_hw3, const float *grad_transient_hwt3,
                          float *grad_materials, float *grad_emitters, float *grad_texels);

@@ -441,7 +441,7 @@ int mtr_scene_texture_layout(const mtr_scene *s, uint32_t index, uint32_t *first
 int mtr_render_grad_tex_tier(const mtr_scene *s, uint32_t *tier)
 {
     if (!s || !tier) return MTR_ERR_INVALID;
-    *tier = grad_tex_tier(s->dev, s->n_texels);
+    *tier = grad_tex_tier(s->dev, s->n_texels, s->nlos.on);
     return MTR_OK;
 }
 
@@ -924,7 +924,6 @@ static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_
     if (nlos) {
         if (s->nlos.k.capture_type == MTR_CAPTURE_EXHAUSTIVE)
             return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad: the NLOS tier with a Single or Confocal capture only (no Exhaustive capture)");
-        if (grad_texels) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad_tex: texel gradients are for transient_path only (not the NLOS tier)");
         if (grad_tints) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_grad_tint: tint gradients are for transient_path only (not the NLOS tier)");
         if (s->nlos.k.film_w != f.width || s->nlos.k.film_h != f.height)
             return fail(c, MTR_ERR_INVALID, "mtr_render_grad: film size changed after mtr_scene_set_nlos; call it again");
@@ -951,7 +950,7 @@ static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_
         if (int r = render_grad(s, p, g_s, g_t, grad_materials, grad_emitters, grad_texels)) return r;
         grad_texels = nullptr;
     }
-    const uint32_t tier = grad_texels ? grad_tex_tier(s->dev, n_tx) : MTR_GRAD_TEX_NONE;
+    const uint32_t tier = grad_texels ? grad_tex_tier(s->dev, n_tx, nlos) : MTR_GRAD_TEX_NONE;
     const uint32_t slab_tx = grad_tints ? n_tints : (tier == MTR_GRAD_TEX_SLAB ? n_tx : 0u);     // slab entries behind the emitters'
     const uint32_t grid = n_lanes ? grad_grid(s->dev, n_lanes, c->n_cu, &lds, &scene_lds, slab_tx, nlos) : 0u;
     if (n_lanes && grid == 0u)

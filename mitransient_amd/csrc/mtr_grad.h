@@ -24,7 +24,8 @@
 // factors are the vertices whose weight is in beta, c itself and — with laser sampling — the laser spot c2; its irradiance factor
 // is the projector's `irradiance` (the walk runs with UNIT irradiance, the true one goes alongside as the one "emitter").  Every
 // diffuse vertex receives R / a as above; c2's material receives its own term over its albedo.  Detached as well: the laser-target
-// and hidden-geometry sampling, the method coin and the dr.epsilon cut-offs (:539-540).
+// and hidden-geometry sampling, the method coin and the dr.epsilon cut-offs (:539-540).  Texels (ABI 20): grad_nlos_walk with a
+// texel hook — the bitmap-textured vertices in beta and at c give R / a(v) to their taps, a textured laser spot its term over a(c2).
 #pragma once
 #include "mtr_core.h"
 #include "mtr_nlos.h"
@@ -242,6 +243,7 @@ MTR_HD bool grad_over_albedo(const mtr_material &m, double rx, double ry, double
 template <class Acc>
 struct NlosGradHook {
     static constexpr bool kOn = true;
+    static constexpr bool kTex = false;
     const SceneView *sc; const Film *film; const GradConst *gc; Acc *acc; d3 *R;
     uint32_t fx, fy; bool replay;
     MTR_HD void vertex(uint32_t m, bool active_next) const
@@ -266,29 +268,90 @@ struct NlosGradHook {
     }
 };
 
+// NlosGradHook with the texel hook of grad_walk (ABI 20; extended shading code only: a bitmap implies it).  A bounce vertex on a
+// bitmap-textured `diffuse` gives R / a to its four taps, a(v) the albedo nlos_bounce shaded with; a textured laser spot c2 gives
+// the term over a(c2) to c2's taps (spot() keeps c2's lookup until the term arrives: *spot_h, *spot_a).  Materials and the laser
+// receive what NlosGradHook gives them (a textured material: nothing).
+template <class Acc, class Tex>
+struct NlosGradTexHook {
+    static constexpr bool kOn = true;
+    static constexpr bool kTex = true;
+    const SceneView *sc; const Film *film; const GradConst *gc; Acc *acc; d3 *R;
+    uint32_t fx, fy; bool replay;
+    Tex tex; Hit *spot_h; f3 *spot_a;
+    // r / a per channel (0 where a is 0) to the four taps of the lookup at h, times texture_taps' own weights
+    MTR_HD void taps(const mtr_material &m, const Hit &h, f3 a, double rx, double ry, double rz) const
+    {
+        if (m.type != MTR_BSDF_DIFFUSE || m.albedo_texture == 0u || !sc->texels) return;
+        float u, v;
+        hit_uv(*sc, h, u, v);
+        const TexTaps k = texture_taps(sc->tex_info[m.albedo_texture - 1u], u, v);
+        const f3 g = mk(a.x != 0.0f ? (float)(rx / (double)a.x) : 0.0f, a.y != 0.0f ? (float)(ry / (double)a.y) : 0.0f,
+                        a.z != 0.0f ? (float)(rz / (double)a.z) : 0.0f);
+        tex(k.first + (uint32_t)k.i00, g * (k.w0x * k.w0y)); tex(k.first + (uint32_t)k.i10, g * (k.w1x * k.w0y));
+        tex(k.first + (uint32_t)k.i01, g * (k.w0x * k.w1y)); tex(k.first + (uint32_t)k.i11, g * (k.w1x * k.w1y));
+    }
+    MTR_HD void vertex(uint32_t m, bool active_next) const
+    {
+        if (!replay) return;
+        acc->vertex(m, 0.0f, active_next);
+        f3 g;
+        if (active_next && grad_over_albedo(sc->mats[m], R->x, R->y, R->z, g)) acc->add_mat(m, g);
+    }
+    MTR_HD void vertex_tex(Hit h, f3 albedo, uint32_t m, bool active_next) const
+    {
+        if (replay && active_next) taps(sc->mats[m], h, albedo, R->x, R->y, R->z);
+    }
+    MTR_HD void spot(Hit h2, f3 albedo2) const { *spot_h = h2; *spot_a = albedo2; }
+    MTR_HD void term(f3 cu, float opl, uint32_t m, bool at_laser_spot) const
+    {
+        const float *L = gc->em_radiance;
+        const f3 w = grad_weight(*gc, *film, fx, fy, opl);
+        const double cx = (double)w.x * (double)(cu.x * L[0]), cy = (double)w.y * (double)(cu.y * L[1]),
+                     cz = (double)w.z * (double)(cu.z * L[2]);
+        if (!replay) { R->x += cx; R->y += cy; R->z += cz; return; }
+        f3 g;
+        if (at_laser_spot && grad_over_albedo(sc->mats[m], cx, cy, cz, g)) acc->add_mat(m, g);
+        if (at_laser_spot) taps(sc->mats[m], *spot_h, *spot_a, cx, cy, cz);
+        R->x -= cx; R->y -= cy; R->z -= cz;
+        acc->add_em(0u, mk(w.x * cu.x, w.y * cu.y, w.z * cu.z));
+        acc->term(1u, m, opl, cu);
+    }
+};
+
 // One walk of a lane's NLOS path (TransientNLOSPath.sample, :740-918, through nlos_bounce): `replay` as REPLAY of grad_walk.
 // nc carries unit irradiance; reload: nlos_bounce's (a kernel re-reads nc / film / rc after every traversal).
-template <bool EXT, class Stack, class Acc, class Reload = NoReload>
+// tex: the texel hook of grad_walk; the default compiles the texel code out (NlosGradHook, as before ABI 20).
+template <bool EXT, class Stack, class Acc, class Reload = NoReload, class Tex = NoTexelGrad>
 MTR_HD d3 grad_nlos_walk(Path p, bool replay, const SceneView &sc, const NlosConst &nc, const Film &film, const RenderConst &rc,
-                         const GradConst &gc, Stack &st, Acc &acc, d3 R, const Reload &reload = Reload())
+                         const GradConst &gc, Stack &st, Acc &acc, d3 R, const Reload &reload = Reload(), Tex tex = Tex())
 {
     NullGradSink ns;
     BounceStats bs{ 0u, 0u };
-    const NlosGradHook<Acc> hook{ &sc, &film, &gc, &acc, &R, p.px - film.crop_x, p.py - film.crop_y, replay };
-    bool alive = true;
-    while (alive) alive = nlos_bounce<EXT, 0u>(p, sc, nc, film, rc, st, ns, bs, reload, hook);
-    return R;
+    if constexpr (Tex::kOn && EXT) {
+        Hit spot_h; f3 spot_a = mk(0, 0, 0);
+        spot_h.t = 0.0f; spot_h.u = 0.0f; spot_h.v = 0.0f; spot_h.prim = 0;
+        const NlosGradTexHook<Acc, Tex> hook{ &sc, &film, &gc, &acc, &R, p.px - film.crop_x, p.py - film.crop_y, replay, tex, &spot_h, &spot_a };
+        bool alive = true;
+        while (alive) alive = nlos_bounce<EXT, 0u>(p, sc, nc, film, rc, st, ns, bs, reload, hook);
+        return R;
+    } else {
+        const NlosGradHook<Acc> hook{ &sc, &film, &gc, &acc, &R, p.px - film.crop_x, p.py - film.crop_y, replay };
+        bool alive = true;
+        while (alive) alive = nlos_bounce<EXT, 0u>(p, sc, nc, film, rc, st, ns, bs, reload, hook);
+        return R;
+    }
 }
 
 // lane (pixel, s) of a NLOS render: both walks through ONE copy of the loop (four traversals per bounce are inlined in it)
-template <bool EXT, class Stack, class Acc, class Reload = NoReload>
+template <bool EXT, class Stack, class Acc, class Reload = NoReload, class Tex = NoTexelGrad>
 MTR_HD void grad_nlos_lane(const SceneView &sc, const NlosConst &nc, const Film &film, const RenderConst &rc, const GradConst &gc,
-                           uint32_t pixel, uint32_t s, Stack &st, Acc &acc, const Reload &reload = Reload())
+                           uint32_t pixel, uint32_t s, Stack &st, Acc &acc, const Reload &reload = Reload(), Tex tex = Tex())
 {
     Path p;
     nlos_begin(p, nc, film, rc, pixel, s);
     d3 R = { 0.0, 0.0, 0.0 };
-    for (int pass = 0; pass < 2; ++pass) R = grad_nlos_walk<EXT>(p, pass != 0, sc, nc, film, rc, gc, st, acc, R, reload);
+    for (int pass = 0; pass < 2; ++pass) R = grad_nlos_walk<EXT>(p, pass != 0, sc, nc, film, rc, gc, st, acc, R, reload, tex);
 }
 
 } // namespace mtr

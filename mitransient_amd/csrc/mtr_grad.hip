@@ -16,8 +16,9 @@
 // A launch without texel gradients runs the kernels it ran before (TEX = kTexNone: no texel code in them).
 // The NLOS tier (ABI 17; mtr_grad_nlos.hip, a translation unit of its own so that the kernels here keep their instructions):
 // k_grad_paths_nlos<EXT> walks grad_nlos_lane over the scene staged in LDS (every NLOS scene
-// the project runs fits; one that does not is refused).  The laser is the slab's one "emitter": its three words sit behind the
-// materials', and k_grad_reduce stores them to grad_emitters[0].  The ~110 dwords of NlosConst are re-read from the kernarg segment
+// the project runs fits; one that does not is refused); with texel gradients (ABI 20) k_grad_paths_nlos_tex<TEX> of
+// mtr_grad_nlos_tex.hip, in the two tiers above, followed by the same reductions.  The laser is the slab's one "emitter": its
+// three words sit behind the materials', and k_grad_reduce stores them to grad_emitters[0].  The ~110 dwords of NlosConst are re-read from the kernarg segment
 // after every traversal (kernarg_copy, as k_fused<NLOS> does) instead of living in scalar registers through four walks per bounce.
 #include "mtr_kernels.h"
 #include "mtr_grad.h"
@@ -28,31 +29,6 @@
 namespace mtr {
 
 namespace {
-
-// the texel hooks of grad_walk (mtr_grad.h)
-struct TexelSlab {                  // slab tier: LDS atomics into the workgroup's slab
-    static constexpr bool kOn = true;
-    double *t;
-    __device__ __forceinline__ void operator()(uint32_t i, f3 g) const
-    {
-        double *p = t + 3u * i;
-        if (g.x != 0.0f) atomicAdd(p, (double)g.x);
-        if (g.y != 0.0f) atomicAdd(p + 1, (double)g.y);
-        if (g.z != 0.0f) atomicAdd(p + 2, (double)g.z);
-    }
-};
-struct TexelGlobal {                // global tier: one no-return global_atomic_add_f64 per non-zero word
-    static constexpr bool kOn = true;
-    double *t;
-    __device__ __forceinline__ void operator()(uint32_t i, f3 g) const
-    {
-        double *p = t + 3u * (size_t)i;
-        if (g.x != 0.0f) atomicAdd(p, (double)g.x);
-        if (g.y != 0.0f) atomicAdd(p + 1, (double)g.y);
-        if (g.z != 0.0f) atomicAdd(p + 2, (double)g.z);
-    }
-};
-enum : int { kTexNone = 0, kTexSlab = 1, kTexGlobal = 2 };
 
 template <bool SCENE_LDS, bool EXT, int TEX = kTexNone>
 __global__ void __launch_bounds__(kBlock) k_grad_paths(const GradArgs a)
@@ -149,14 +125,14 @@ hipError_t launch_paths(const GradArgs &a, int grid, size_t lds, hipStream_t str
 
 } // namespace
 
-uint32_t grad_tex_tier(const SceneDev &sc, uint32_t n_texels)
+uint32_t grad_tex_tier(const SceneDev &sc, uint32_t n_texels, bool nlos)
 {
     if (n_texels == 0u || !sc.has_rough || !sc.texels) return MTR_GRAD_TEX_NONE;
     if ((uint64_t)n_texels * 24u > kGradTexSlabBytes) return MTR_GRAD_TEX_GLOBAL;
     // ... and the whole carve-up must still fit (grad_grid's own bound)
     const uint32_t scene_b = lds_scene_bytes(sc);
     const bool scene_lds = sc.wnodes != nullptr && scene_b <= 64u * 1024u;
-    const size_t lds = al16((3u * (sc.n_mats + sc.n_ems) + 3u * n_texels) * 8u) + (size_t)wf_stack_rows(sc, scene_lds) * kBlock * 4u +
+    const size_t lds = al16((3u * (sc.n_mats + (nlos ? 1u : sc.n_ems)) + 3u * n_texels) * 8u) + (size_t)wf_stack_rows(sc, scene_lds) * kBlock * 4u +
                        (scene_lds ? scene_b : 0u);
     return lds <= 160u * 1024u ? MTR_GRAD_TEX_SLAB : MTR_GRAD_TEX_GLOBAL;
 }
@@ -193,8 +169,21 @@ hipError_t launch_grad(const SceneDev &sc, const Emitter *ems_unit, const Camera
     a.n_texels = n_texels; a.tex_acc = tex_acc; a.grad_texels = grad_texels;
     const bool ext = sc.has_rough != 0u;
     if (nlos_unit) {
-        if (tex_tier != MTR_GRAD_TEX_NONE || !scene_lds) return hipErrorInvalidValue;
+        if (!scene_lds) return hipErrorInvalidValue;
         a.n_ems = 1u;                                   // the laser
+        if (tex_tier != MTR_GRAD_TEX_NONE) {            // k_grad_paths_nlos_tex (mtr_grad_nlos_tex.hip), then the reductions of the tier
+            if (!ext || !grad_texels || (tex_tier == MTR_GRAD_TEX_GLOBAL && !tex_acc)) return hipErrorInvalidValue;
+            hipError_t e = launch_grad_paths_nlos_tex(a, *nlos_unit, tex_tier, (int)grid, lds, stream);
+            if (e != hipSuccess) return e;
+            const uint32_t n_me = 3u * (sc.n_mats + 1u);
+            if (tex_tier == MTR_GRAD_TEX_SLAB) {
+                hipLaunchKernelGGL(k_grad_reduce_tex, dim3((n_me + 3u * n_texels + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+                return hipGetLastError();
+            }
+            hipLaunchKernelGGL(k_grad_reduce, dim3((n_me + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, a);
+            hipLaunchKernelGGL(k_grad_tex_store, dim3((uint32_t)((3u * (size_t)n_texels + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, a);
+            return hipGetLastError();
+        }
         hipError_t e = launch_grad_paths_nlos(a, *nlos_unit, ext, (int)grid, lds, stream);
         if (e != hipSuccess) return e;
         const uint32_t slab_n = 3u * (sc.n_mats + 1u);

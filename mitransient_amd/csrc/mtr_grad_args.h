@@ -1,4 +1,4 @@
-// mtr_grad_args.h — the argument block and the LDS slab of the gradient kernels (mtr_grad.hip, mtr_grad_nlos.hip)
+// mtr_grad_args.h — the argument block and the LDS slab of the gradient kernels (mtr_grad.hip, mtr_grad_nlos.hip, mtr_grad_nlos_tex.hip)
 #pragma once
 #include "mtr_kernels.h"
 #include "mtr_grad.h"
@@ -45,7 +45,35 @@ struct SlabAcc {
     __device__ __forceinline__ void term(uint32_t, uint32_t, float, f3) {}
 };
 
+// the texel hooks of grad_walk / grad_nlos_walk (mtr_grad.h)
+struct TexelSlab {                  // slab tier: LDS atomics into the workgroup's slab
+    static constexpr bool kOn = true;
+    double *t;
+    __device__ __forceinline__ void operator()(uint32_t i, f3 g) const
+    {
+        double *p = t + 3u * i;
+        if (g.x != 0.0f) atomicAdd(p, (double)g.x);
+        if (g.y != 0.0f) atomicAdd(p + 1, (double)g.y);
+        if (g.z != 0.0f) atomicAdd(p + 2, (double)g.z);
+    }
+};
+struct TexelGlobal {                // global tier: one no-return global_atomic_add_f64 per non-zero word
+    static constexpr bool kOn = true;
+    double *t;
+    __device__ __forceinline__ void operator()(uint32_t i, f3 g) const
+    {
+        double *p = t + 3u * (size_t)i;
+        if (g.x != 0.0f) atomicAdd(p, (double)g.x);
+        if (g.y != 0.0f) atomicAdd(p + 1, (double)g.y);
+        if (g.z != 0.0f) atomicAdd(p + 2, (double)g.z);
+    }
+};
+enum : int { kTexNone = 0, kTexSlab = 1, kTexGlobal = 2 };
+
 // k_grad_paths_nlos<EXT> (mtr_grad_nlos.hip) over the lanes of `a`; launch_grad runs k_grad_reduce behind it
 hipError_t launch_grad_paths_nlos(const GradArgs &a, const NlosConst &nlos_unit, bool ext, int grid, size_t lds, hipStream_t stream);
+// k_grad_paths_nlos_tex<TEX> (mtr_grad_nlos_tex.hip; extended shading code) in tier MTR_GRAD_TEX_SLAB / _GLOBAL; launch_grad runs
+// k_grad_reduce_tex, or k_grad_reduce and k_grad_tex_store, behind it
+hipError_t launch_grad_paths_nlos_tex(const GradArgs &a, const NlosConst &nlos_unit, uint32_t tier, int grid, size_t lds, hipStream_t stream);
 
 } // namespace mtr

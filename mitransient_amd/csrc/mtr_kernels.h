@@ -196,7 +196,7 @@ hipError_t launch_develop(const Film &film, const float *t4, float *t3, const fl
 // workgroups on every scene staged in LDS; the rows of `partial` and k_grad_reduce_tex's pass grow with it as well.
 struct GradConst;
 constexpr uint32_t kGradTexSlabBytes = 8u * 1024u;
-uint32_t grad_tex_tier(const SceneDev &sc, uint32_t n_texels);
+uint32_t grad_tex_tier(const SceneDev &sc, uint32_t n_texels, bool nlos = false);     // nlos: the laser's words in the slab
 // nlos (grad_grid) / nlos_unit (launch_grad: the scene's NlosConst with unit irradiance, gc.em_radiance = the true one): the NLOS
 // tier — the laser takes the slab's three emitter words (grad_ems is (1, 3)), the scene must fit LDS, and at most kGradNlosPerCu
 // workgroups per compute unit are asked for (the kernel's launch bound)

@@ -173,8 +173,12 @@ struct NoReload { MTR_HD void operator()() const {} };
 // its terms; term(Lr, opl, material, at_laser_spot) sees every emitter_nee_sample term BEFORE the sample scale, with its optical
 // path length and the material of the vertex that was connected to the laser (at_laser_spot: that vertex is the laser spot c2 of
 // emitter_laser_targets_sample, not the bounce's own).  The default does nothing: callers that pass no hook are what they were.
+// A hook with kTex (texel gradients, ABI 20) also sees the texture lookups: vertex_tex(hit, albedo, material, active_next) right
+// after vertex() at every valid bounce vertex, and spot(hit, albedo) at the laser spot c2 before the term that is connected
+// through it — the Hit (for the texture coordinate and the four taps) and the albedo the primal shades with (material_albedo).
 struct NoNlosHook {
     static constexpr bool kOn = false;       // compiles the calls out
+    static constexpr bool kTex = false;      // ... and the texture calls
     MTR_HD void vertex(uint32_t, bool) const {}
     MTR_HD void term(f3, float, uint32_t, bool) const {}
 };
@@ -243,6 +247,7 @@ MTR_HD f3 nlos_laser_targets(Path &p, const HitCtx &c, const mtr_material &mat, 
     if (!(wlz > 0.0f)) return mk(0, 0, 0);                                                     // :543
     const float pdf_ls = (dl * dl) / wlz;                                                      // :546-551
     const f3 b2 = mk(p.beta.x * (bs.x / pdf_ls), p.beta.y * (bs.y / pdf_ls), p.beta.z * (bs.z / pdf_ls));
+    if constexpr (Hook::kTex) hook.spot(h2, material_albedo<EXT>(sc, sc.mats[c2.mat], h2));
     return nlos_emitter_nee<EXT, TR>(p, c2, sc.mats[c2.mat], material_albedo<EXT>(sc, sc.mats[c2.mat], h2), b2, p.dist + dl * p.eta, depth + 1, true,
                                  laser, sc, nc, film, rc, st, sink, stats, reload, hook);
 }
@@ -305,6 +310,7 @@ MTR_HD bool nlos_bounce(Path &p, const SceneView &sc, const NlosConst &nc, const
     const mtr_material &mat = sc.mats[c.mat];
     const f3 albedo = valid ? material_albedo<EXT>(sc, mat, h) : mk(0, 0, 0);
     if constexpr (Hook::kOn) hook.vertex(c.mat, active_next);
+    if constexpr (Hook::kTex) { if (valid) hook.vertex_tex(h, albedo, c.mat, active_next); }
     // the only emitter is the projector (not a surface): Le = 0 (:757-777)
     if (active_next && nlos_bsdf_smooth<EXT, TR>(mat)) {                                 // active_em :785-786
         if ((nc.flags & MTR_NLOS_LASER_SAMPLING) && nc.capture_type == MTR_CAPTURE_EXHAUSTIVE) {

@@ -441,9 +441,6 @@ class TransientADIntegrator:
             if int(self.capture_type) == 3:
                 raise ValueError("transient_nlos_path: differentiable rendering is not available for an Exhaustive capture "
                                  "(Single and Confocal are)")
-            for k, val in (params or {}).items():
-                if _wants_grad(val) and k.endswith(".data"):
-                    raise ValueError(f"{k}: texel gradients are available with transient_path only (not transient_nlos_path)")
         if isinstance(sensor, int):
             sensor = scene.sensors()[sensor]
         film = sensor.film()
@@ -466,8 +463,8 @@ class TransientADIntegrator:
             if k not in keys:
                 raise ValueError(f"{k}: not a differentiable parameter (the constant reflectance of a diffuse BSDF, the texels of a "
                                  f"bitmap that only diffuse reflectances use, the constant radiance of an area / angulararea "
-                                 f"emitter, the constant irradiance of a NLOS scene's projector and, with transient_path, the "
-                                 f"constant specular tints of conductors and dielectrics are: {sorted(keys)})")
+                                 f"emitter and the constant irradiance of a NLOS scene's projector are; the constant specular "
+                                 f"tints of conductors and dielectrics with transient_path only: {sorted(keys)})")
             if keys[k][0] == "tint" and int(np.prod(tuple(val.shape))) not in (1, 3):
                 raise ValueError(f"{k}: a tint of 1 or 3 elements, got shape {tuple(val.shape)}")
             if keys[k][0] == "texture":
