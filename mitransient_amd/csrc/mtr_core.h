@@ -1032,13 +1032,21 @@ __device__ __forceinline__ void wide_walk_device(Trav &tr, const SceneView &sc, 
 // A field of the kernel's (single, by-value) argument read from the kernarg segment with scalar loads AT THE POINT OF USE: the
 // empty asm makes the address opaque, so the loads can neither be hoisted out of a persistent loop nor merged with the
 // compiler's own copy of the argument.  (Taking the address of the argument itself sends the whole struct through scratch.)
-template <class T>
+// ONE_BASE: the SEGMENT's address is made opaque instead of the field's.  The field's address (segment + offset) is loop-invariant: the
+// compiler computes one per call site in front of a persistent loop and holds them all across it, i.e. in spill lanes — three pairs
+// in k_fused's flat-walk kernels, re-read with v_readlane at every use.  From one opaque base the offsets are immediates of the
+// loads and the only value held is the segment's own address (config 2's kernel: 76 -> 50 spilled SGPRs, 139 -> 59 lane copies in
+// the persistent loop).  Chosen per kernel: the allocator of kernels that spill vector registers is not indifferent to it.
+template <class T, bool ONE_BASE = false>
 __device__ __forceinline__ T kernarg_copy(size_t offset)
 {
     static_assert(sizeof(T) % 4 == 0, "dword-sized fields");
     typedef const uint32_t __attribute__((address_space(4))) *WordPtr;
-    WordPtr w = (WordPtr)((const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr() + offset);
-    asm volatile("" : "+s"(w));
+    typedef const char __attribute__((address_space(4))) *BytePtr;
+    BytePtr base = (BytePtr)__builtin_amdgcn_kernarg_segment_ptr();
+    if (ONE_BASE) asm volatile("" : "+s"(base));
+    WordPtr w = (WordPtr)(base + offset);
+    if (!ONE_BASE) asm volatile("" : "+s"(w));
     T out;
     uint32_t *o = (uint32_t *)&out;
 #pragma unroll
@@ -1046,6 +1054,10 @@ __device__ __forceinline__ T kernarg_copy(size_t offset)
     return out;
 }
 #endif
+
+// (a traversal stack type may name the form of kernarg_copy its kernel reads the flat top level with: Stack::kOneKernargBase)
+template <class S, class = void> struct stack_one_kernarg_base { static constexpr bool value = false; };
+template <class S> struct stack_one_kernarg_base<S, decltype((void)S::kOneKernargBase)> { static constexpr bool value = S::kOneKernargBase; };
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // The "walk" of a scene with a FLAT TOP LEVEL (FlatTop).  Nothing here decides a hit: rectangles are intersected by
@@ -1066,14 +1078,15 @@ __device__ __forceinline__ void flat_walk_device(Trav &tr, const SceneView &sc, 
 {
     typedef WNode N;
     const char *root = (const char *)sc.wnodes;
-    const FlatHdr fh = kernarg_copy<FlatHdr>(sc.flat_off);
+    constexpr bool kOneBase = stack_one_kernarg_base<Stack>::value;
+    const FlatHdr fh = kernarg_copy<FlatHdr, kOneBase>(sc.flat_off);
     bool live = true;
     // ---- boxes: face selection per box, uniform over the wave
     uint32_t fm = 0u;
     const float omax = fmaxf(fmaxf(fabsf(tr.o.x), fabsf(tr.o.y)), fabsf(tr.o.z));
     for (uint32_t b = 0; b < fh.n_boxes; ++b) {
         // (requesting the next box's rows before this one's arithmetic costs 45 scalar moves per iteration: measured, not kept)
-        const FlatXf X = kernarg_copy<FlatXf>(sc.flat_off + sizeof(FlatHdr) + sizeof(FlatXf) * b);
+        const FlatXf X = kernarg_copy<FlatXf, kOneBase>(sc.flat_off + sizeof(FlatHdr) + sizeof(FlatXf) * b);
         const q4 A = X.A, B = X.B, C = X.C, S = X.S;
         const f3 o = tr.o, d = tr.d;
         const f3 ol = mk(fmaf(A.z, o.z, fmaf(A.y, o.y, fmaf(A.x, o.x, A.w))), fmaf(B.z, o.z, fmaf(B.y, o.y, fmaf(B.x, o.x, B.w))),

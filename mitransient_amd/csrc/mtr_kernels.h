@@ -118,6 +118,21 @@ struct FusedArgs {
 
 struct FusedConfig { int stack; bool scene_lds; bool hist_lds; bool fixed; bool rough; size_t lds_bytes; int grid; int per_cu; uint32_t traits; };
 
+// k_fused's lean kernels count paths, bounces, shadow rays and contributions of a work ticket in 32-bit wave counters, drained
+// between tickets.  What guarantees that none wraps is the kernel's own drain of a wave that has counted 2^30 bounces; this cap is no
+// bound by itself (kChunkContribs is an AVERAGE a render is expected to stay under) — it cuts a ticket to pixels x spp_chunk x
+// kChunkContribs < 2^32, never below one pixel, so that the drain inside the loop stays a branch ordinary renders do not take.
+constexpr uint64_t kChunkContribs = 16u;
+inline uint32_t fused_chunk_cap(uint32_t chunk, uint32_t spp_chunk)
+{
+    const uint64_t per_px = (uint64_t)(spp_chunk ? spp_chunk : 1u) * kChunkContribs;
+    const uint64_t cap = ((1ull << 32) - 1ull) / per_px;          // chunk * per_px < 2^32
+    if ((uint64_t)chunk > cap) chunk = (uint32_t)cap;
+    return chunk < 1u ? 1u : chunk;
+}
+
+// pixels per work ticket of a launch of `grid` workgroups (fused_plan): about 32768 samples, at least two tickets per workgroup, capped as above
+uint32_t fused_chunk(uint32_t n_pixels, uint32_t spp_chunk, uint32_t grid);
 // chooses G, LDS carve-up and grid for a render; returns false if nothing fits
 bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t spp_chunk, int n_cu,
                 FusedArgs &args, FusedConfig &cfg);
@@ -210,3 +225,7 @@ hipError_t launch_grad(const SceneDev &sc, const Emitter *ems_unit, const Camera
                        const NlosConst *nlos_unit = nullptr);
 
 } // namespace mtr
+
+// test hooks of the library, outside the C ABI of include/mitransient_amd.h: fused_chunk / fused_chunk_cap as the tests call them
+extern "C" uint32_t mtr_test_fused_chunk(uint32_t n_pixels, uint32_t spp_chunk, uint32_t grid);
+extern "C" uint32_t mtr_test_fused_chunk_cap(uint32_t chunk, uint32_t spp_chunk);

@@ -15,12 +15,15 @@
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <type_traits>
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 namespace mtr {
 
 // ------------------------------------------------------------------ helpers
-struct LdsStack {
+template <bool ONE_BASE = false>      // ONE_BASE: the kernel reads its argument through kernarg_copy<T, true> (mtr_core.h), the flat walk included
+struct LdsStackT {
+    static constexpr bool kOneKernargBase = ONE_BASE;
     int32_t *base;     // &stack[tid]; entry k lives at base[k * kBlock]  (one bank column per lane)
     int sp;            // the column has FusedArgs::stack_rows rows: one per stacked group + the row push_if writes before it counts
     __device__ __forceinline__ void reset() { sp = 0; }
@@ -83,6 +86,7 @@ struct LdsStack {
     __device__ __forceinline__ void count(int) {}
 #endif
 };
+typedef LdsStackT<> LdsStack;
 
 __device__ __forceinline__ void lds_add(float *p, float v)
 {
@@ -98,6 +102,18 @@ __device__ __forceinline__ void log_splat(const SplatLog &lg, uint32_t lane, uin
         R[0] = lane; R[1] = depth | (kind << 16); R[2] = pixel; R[3] = bin;
         R[4] = __float_as_uint(r); R[5] = __float_as_uint(g); R[6] = __float_as_uint(b); R[7] = __float_as_uint(opl);
     }
+}
+
+// SPLAT LOG IN k_fused's lean kernels.  A timed render keeps no log (FusedArgs::log.rec == nullptr), yet as a member of the sink the
+// log's six words were held across both walks of a bounce — in spill lanes — and restored at either contribution site: 24 v_readlane
+// per wave iteration of config 2 for a branch never taken.  The sink's copy is used for the null test alone (its other words are
+// dead); the log is read from the kernarg segment inside the branch.  (The base pointer re-read after either walk as well: two
+// spilled SGPRs fewer and no faster — HISTORY.md's index, round 7.)
+__device__ __forceinline__ void log_splat_fused(uint32_t lane, uint32_t depth, uint32_t kind,
+                                                uint32_t pixel, uint32_t bin, float r, float g, float b, float opl)
+{
+    const SplatLog lg = kernarg_copy<SplatLog, true>(offsetof(FusedArgs, log));
+    log_splat(lg, lane, depth, kind, pixel, bin, r, g, b, opl);
 }
 
 // signed 2^-42 fixed point for order-independent LDS sums (ds_add_u64): resolution 2.3e-13, range +-2^21; a non-zero
@@ -123,7 +139,8 @@ __device__ __forceinline__ bool splat_fixed_unsafe(float r, float g, float b, fl
 #endif
 
 // the workgroup's ring of row histograms in LDS: planes [3][G*T]
-template <bool GREY = false>          // GREY (scene trait kTrGrey): r == g == b in every contribution, the row holds ONE plane
+// LEAN (k_fused's flat-walk kernels): SPLAT LOG, above
+template <bool GREY = false, bool LEAN = false>          // GREY (scene trait kTrGrey): r == g == b in every contribution, the row holds ONE plane
 struct LdsHistSink {
     float *hist; uint32_t plane;       // plane = G * T
     uint32_t row;                      // (local pixel) * T, set per path
@@ -138,7 +155,8 @@ struct LdsHistSink {
         if (GREY) lds_add(p, r);
         else { lds_add(p, r); lds_add(p + plane, g); lds_add(p + 2 * plane, b); }
         ++n_splats;
-        if (log.rec) log_splat(log, lane, depth, kind, fy * film_w + fx, bin, r, g, b, opl);
+        if (LEAN) { if (log.rec) log_splat_fused(lane, depth, kind, fy * film_w + fx, bin, r, g, b, opl); }
+        else if (log.rec) log_splat(log, lane, depth, kind, fy * film_w + fx, bin, r, g, b, opl);
     }
 };
 
@@ -229,6 +247,12 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
+    // LEAN UNIFORM STATE (the kernels of the flat walk, f32 rows: config 2's): what the persistent loop holds in scalar registers across
+    // its walks is cut three ways — one opaque base for every kernarg_copy (mtr_core.h), 32-bit wave counters drained per chunk, and
+    // the splat log re-read where a contribution is made (below).  Config 2's kernel: 76 -> 26 spilled SGPRs, 139 -> 57 v_readlane /
+    // v_writelane in the loop, no spilled VGPR.  The other instantiations keep the former code: they spill vector registers, and the
+    // same changes moved their allocation the wrong way (more spilled VGPRs, more scratch) in most of them.
+    constexpr bool kLean = SCENE_LDS && HIST_LDS && !NLOS && !PHASOR && !FIXED && !ROUGH && flat_kind(TR) != 0;
 #ifdef MTR_PROFILE_TAIL
     const unsigned long long t0_wall = wall_clock64();
 #endif
@@ -290,7 +314,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     if (HIST_LDS) for (uint32_t k = tid; k < (kGrey ? K * T : (PHASOR ? 1u : (FIXED ? 9u : 3u)) * plane); k += kBlock) s_hist[k] = 0.0f;
     if (FIXED) for (uint32_t k = tid; k < K * 4; k += kBlock) s_steady_ovf[k] = 0.0f;
 
-    LdsStack st; st.base = s_stack + tid; st.sp = 0;
+    LdsStackT<kLean> st; st.base = s_stack + tid; st.sp = 0;
 #ifndef MTR_NO_PARK
     st.park_row = (int)a.stack_rows;
 #endif
@@ -304,7 +328,23 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     // Counters are kept per WAVE, summed from ballots (scalar registers, scalar adds): five per-lane counters would be
     // five vector registers live across every traversal of a kernel that already spills.  The NLOS loop can trace many
     // shadow rays per bounce (one per illuminated point), so that variant counts per lane.
-    unsigned long long w_closest = 0, w_shadow = 0, w_bounce = 0, w_paths = 0, w_splats = 0;
+    // 32 BITS PER CHUNK (kLean).  The counters are live across everything in the loop; as five 64-bit sums they are ten scalar registers,
+    // two of them spilled and restored in every wave iteration.  Four 32-bit ones instead — closest-hit rays are bounces, plus one per
+    // path under camera_unwarp — drained into the workgroup's 64-bit sums at the end of every chunk (drain_counters).  No wrap: a wave
+    // iteration adds at most 64 paths, 64 bounces, 64 shadow rays and 128 contributions — paths and shadow rays never outnumber the
+    // bounces, contributions are at most twice as many — and a wave that has counted 2^30 bounces since its last drain drains at
+    // once: THAT is what rules a wrap out.  fused_chunk_cap only keeps that branch cold for any path length a render is likely to have.
+    typedef typename std::conditional<kLean, uint32_t, unsigned long long>::type WaveCount;
+    WaveCount w_closest = 0, w_shadow = 0, w_bounce = 0, w_paths = 0, w_splats = 0;       // (w_closest: not kLean)
+    auto drain_counters = [&]() {
+        if ((tid & 63) == 0) {
+            atomicAdd(&s_cnt[0], (unsigned long long)w_paths);
+            atomicAdd(&s_cnt[2], (unsigned long long)w_shadow);
+            atomicAdd(&s_cnt[3], (unsigned long long)w_splats);
+            atomicAdd(&s_cnt[4], (unsigned long long)w_bounce);
+        }
+        w_paths = 0; w_shadow = 0; w_splats = 0; w_bounce = 0;
+    };
 #ifdef MTR_PROFILE_OCC
     unsigned long long occ_iter = 0, occ_alive = 0, occ_wait = 0;
 #endif
@@ -376,7 +416,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
         if (__ballot(waiting) != 0ull) {
             bool started = false;
             // (the arguments a path start needs: read from the kernarg segment here, see kernarg_copy)
-            const LoopArgs la = kernarg_copy<LoopArgs>(offsetof(FusedArgs, spp_begin));
+            const LoopArgs la = kernarg_copy<LoopArgs, kLean>(offsetof(FusedArgs, spp_begin));
             if (waiting) {
                 q = fastdiv(i, la.div_spp);
                 slot = q - fastdiv(q, la.div_G) * la.G;
@@ -395,9 +435,9 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                         // argument it lived in scalar registers across the whole persistent loop, i.e. in v_readlane'd spill slots
                         // (the loop holds more than 100 uniform values).  Scalar loads from the kernarg segment where a path starts
                         // instead: 111 -> 82 spilled SGPRs, config 2 61.1 -> 60.4 ms (same box)
-                        const Camera cam_l = kernarg_copy<Camera>(offsetof(FusedArgs, cam));
-                        const Film film_s = kernarg_copy<Film>(offsetof(FusedArgs, film));
-                        const RenderConst rc_s = kernarg_copy<RenderConst>(offsetof(FusedArgs, rc));
+                        const Camera cam_l = kernarg_copy<Camera, kLean>(offsetof(FusedArgs, cam));
+                        const Film film_s = kernarg_copy<Film, kLean>(offsetof(FusedArgs, film));
+                        const RenderConst rc_s = kernarg_copy<RenderConst, kLean>(offsetof(FusedArgs, rc));
                         path_begin(p, cam_l, film_s, rc_s, pixel, s);
                         if (LdsStack::kPark) { st.park_inc(p.rng.inc); st.park_prev_p(p.prev_p); st.park_prev_pdf(p.prev_pdf); }
                     }
@@ -408,7 +448,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
             }
             const uint32_t n_started = (uint32_t)__popcll(__ballot(started));
             w_paths += n_started;
-            if (!NLOS && (a.rc.flags & MTR_FLAG_CAMERA_UNWARP)) w_closest += n_started;
+            if (!kLean && !NLOS && (a.rc.flags & MTR_FLAG_CAMERA_UNWARP)) w_closest += n_started;
         }
         st.prof_mark(2);
         if (__ballot(alive) == 0ull) {
@@ -451,7 +491,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
             auto refresh = [&](Path &pp, auto &) {
                 uint32_t w = xy; asm volatile("" : "+v"(w));
                 pp.px = w & 0xffffu; pp.py = w >> 16;
-                if (!NLOS) { film_l = kernarg_copy<Film>(offsetof(FusedArgs, film)); rc_l = kernarg_copy<RenderConst>(offsetof(FusedArgs, rc)); }
+                if (!NLOS) { film_l = kernarg_copy<Film, kLean>(offsetof(FusedArgs, film)); rc_l = kernarg_copy<RenderConst, kLean>(offsetof(FusedArgs, rc)); }
             };
             if (PHASOR) {
                 LdsPhasorSink sink; sink.row = s_hist + slot * T; sink.freq = a.film.freq; sink.n_freq = a.film.n_freq;
@@ -466,7 +506,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                              : path_bounce<ROUGH, TR>(p, sv, film_l, rc_l, st, sink, bstat, refresh, unwarp);
                 if (NLOS) n_splats += sink.n_splats; else did_splats = sink.n_splats;
             } else if (HIST_LDS) {
-                LdsHistSink<(TR & kTrGrey) != 0u> sink; sink.hist = s_hist; sink.plane = plane; sink.row = slot * T;
+                LdsHistSink<(TR & kTrGrey) != 0u, kLean> sink; sink.hist = s_hist; sink.plane = plane; sink.row = slot * T;
                 sink.film_w = a.film.width; sink.lane = p.lane; sink.n_splats = 0; sink.log = a.log;
                 alive = NLOS ? nlos_bounce<ROUGH, TR>(p, sv, nc_l, film_l, rc_l, st, sink, bstat, reload_nlos)
                              : path_bounce<ROUGH, TR>(p, sv, film_l, rc_l, st, sink, bstat, refresh, unwarp);
@@ -623,7 +663,9 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                 __hip_atomic_store(s_owner + fs, fq + K, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
+        if (kLean && __builtin_expect(w_bounce >= 0x40000000u, 0)) drain_counters();
     }
+    if (kLean) drain_counters();          // (32 BITS PER CHUNK, above: the next chunk's first barrier, or the one below, orders the sums)
     }       // chunks
     __syncthreads();
 
@@ -632,8 +674,8 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
         atomicAdd(&s_cnt[1], (unsigned long long)n_closest);
         atomicAdd(&s_cnt[2], (unsigned long long)n_shadow);
         atomicAdd(&s_cnt[3], (unsigned long long)n_splats);
-    } else w_closest += w_bounce;
-    if ((tid & 63) == 0) {
+    } else if (!kLean) w_closest += w_bounce;
+    if (!kLean && (tid & 63) == 0) {
         atomicAdd(&s_cnt[0], w_paths);
         atomicAdd(&s_cnt[1], w_closest);
         atomicAdd(&s_cnt[2], w_shadow);
@@ -641,6 +683,9 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
         atomicAdd(&s_cnt[4], w_bounce);
     }
     __syncthreads();
+    // (kLean) closest-hit rays: one per bounce, and camera_unwarp's ray of every path (counted, not traced: see `unwarp`)
+    if (kLean && tid == 0) s_cnt[1] = s_cnt[4] + ((a.rc.flags & MTR_FLAG_CAMERA_UNWARP) ? s_cnt[0] : 0ull);
+    if (kLean) __syncthreads();
     if (tid < 5 && a.counters) atomicAdd(&a.counters->paths + tid, s_cnt[tid]);
 #ifdef MTR_PROFILE_OCC
     if ((tid & 63) == 0 && a.counters) {
@@ -679,6 +724,15 @@ static uint32_t scene_lds_bytes(const SceneDev &sc)
     return align16(sc.n_wnodes * sizeof(WNode)) + align16(sc.n_slots / 2 * sizeof(TriPair)) +
            align16(sc.n_slots * sizeof(TriShade)) + align16(sc.n_mats * sizeof(mtr_material)) +
            align16(sc.n_ems * sizeof(Emitter));
+}
+
+uint32_t fused_chunk(uint32_t n_pixels, uint32_t spp_chunk, uint32_t grid)
+{
+    uint32_t chunk = (32768u + spp_chunk - 1u) / (spp_chunk ? spp_chunk : 1u);
+    const uint32_t c_bal = (uint32_t)((unsigned long long)n_pixels / (2ull * (unsigned long long)(grid ? grid : 1u)));
+    if (chunk > c_bal) chunk = c_bal;
+    if (chunk < 1u) chunk = 1u;
+    return fused_chunk_cap(chunk, spp_chunk);       // (k_fused's per-chunk counters are 32 bits wide)
 }
 
 bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t spp_chunk, int n_cu,
@@ -765,11 +819,8 @@ bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_
     // of the kernel — fewer pixels as the launch runs out — level the workgroups out; rounds 1 - 5 asked for 8 chunks per workgroup, which cut
     // the tickets of a 64-row band of config 2 to 4 pixels: eight band launches 55.9 ms, with 16-pixel tickets 54.9; config 4's share
     // 5.955 -> 5.92 ms with 42 instead of 10 pixels per ticket)
-    uint32_t chunk = (32768u + spp_chunk - 1u) / (spp_chunk ? spp_chunk : 1u);
-    const uint32_t c_bal = (uint32_t)((unsigned long long)n_pixels / (2ull * (unsigned long long)grid));
-    if (chunk > c_bal) chunk = c_bal;
-    if (chunk < 1u) chunk = 1u;
-    if (const char *e = mtr::knob("MTR_FUSED_CHUNK")) { const int v = atoi(e); if (v >= 1) chunk = (uint32_t)v; }     // experiments
+    uint32_t chunk = fused_chunk(n_pixels, spp_chunk, (uint32_t)grid);
+    if (const char *e = mtr::knob("MTR_FUSED_CHUNK")) { const int v = atoi(e); if (v >= 1) chunk = fused_chunk_cap((uint32_t)v, spp_chunk); }     // experiments
     if ((unsigned long long)chunk * spp_chunk > 0xffff0000ull) return false;     // the per-chunk sample counter is 32 bits wide
     args.chunk = chunk;
     args.n_chunks = (n_pixels + chunk - 1u) / chunk;
@@ -1156,3 +1207,7 @@ hipError_t launch_develop(const Film &film, const float *t4, float *t3, const fl
 }
 
 } // namespace mtr
+
+// test hooks (declared in mtr_kernels.h): the plan's host arithmetic without a device or a context
+extern "C" uint32_t mtr_test_fused_chunk(uint32_t n_pixels, uint32_t spp_chunk, uint32_t grid) { return mtr::fused_chunk(n_pixels, spp_chunk, grid); }
+extern "C" uint32_t mtr_test_fused_chunk_cap(uint32_t chunk, uint32_t spp_chunk) { return mtr::fused_chunk_cap(chunk, spp_chunk); }
