@@ -584,21 +584,38 @@ MTR_HD void trav_node_step(Trav &tr, const SceneView &sc, Stack &st)
 // translation first, then one fmadd per column), t = -o.z / d.z, local = fmadd(d, t, o), hit iff 0 <= t <= maxt and
 // |local.x|, |local.y| <= 1; (u, v) of the hit = (local.x, local.y)
 MTR_HD bool is_quad_leaf(int32_t cur) { return cur < 0 && cur != kTravDone && ((~(uint32_t)cur) & kLeafQuadBit) != 0u; }
-template <class Stack>
-MTR_HD bool trav_quad_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hit)
+// Where a primitive test takes its ray from.  RayOfTrav (every tree walker, the default): o, d and tmax of the Trav.  RayByValue: the
+// ray is the argument itself and the Trav's is never written — flat_walk_device.  A callee that reads o and d through `Trav &` is
+// optimised on its own before it is inlined; its scalar loads next to a splat are widened there to overlapping two-float loads, and a
+// Trav with such loads on it can no longer be taken apart into registers: the ray then lives in private memory and is read back at
+// every stage.  The source is a TYPE, so a by-value caller cannot leave the ray out; the tree walkers compile to what they were.
+struct RayOfTrav {
+    MTR_HD f3 o(const Trav &tr) const { return tr.o; }
+    MTR_HD f3 d(const Trav &tr) const { return tr.d; }
+    MTR_HD float tmax(const Trav &tr) const { return tr.tmax; }
+};
+struct RayByValue {
+    f3 ro, rd;
+    float rtmax;
+    MTR_HD f3 o(const Trav &) const { return ro; }
+    MTR_HD f3 d(const Trav &) const { return rd; }
+    MTR_HD float tmax(const Trav &) const { return rtmax; }
+};
+template <class RaySrc = RayOfTrav, class Stack>
+MTR_HD bool trav_quad_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hit, const RaySrc ray = RaySrc())
 {
     st.count(1);
     const uint32_t first = ((~(uint32_t)tr.cur) & ~kLeafQuadBit) >> 2;
     const TriPair &tp = sc.tpairs[first >> 1];
     const q4 Z = tp.g[0], X = tp.g[1], Y = tp.g[2];
     const uint32_t orig = fbits(tp.g[4].z);
-    const f3 o = tr.o, d = tr.d;
+    const f3 o = ray.o(tr), d = ray.d(tr);
     const float oz = fmaf(Z.z, o.z, fmaf(Z.y, o.y, fmaf(Z.x, o.x, Z.w))), dz = fmaf(Z.z, d.z, fmaf(Z.y, d.y, Z.x * d.x));
     const float t = -oz / dz;
     const float ox = fmaf(X.z, o.z, fmaf(X.y, o.y, fmaf(X.x, o.x, X.w))), dx = fmaf(X.z, d.z, fmaf(X.y, d.y, X.x * d.x));
     const float oy = fmaf(Y.z, o.z, fmaf(Y.y, o.y, fmaf(Y.x, o.x, Y.w))), dy = fmaf(Y.z, d.z, fmaf(Y.y, d.y, Y.x * d.x));
     const float lx = fmaf(dx, t, ox), ly = fmaf(dy, t, oy);
-    const bool hit = (t >= 0.0f) && (t <= tr.tmax) && (fabsf(lx) <= 1.0f) && (fabsf(ly) <= 1.0f);
+    const bool hit = (t >= 0.0f) && (t <= ray.tmax(tr)) && (fabsf(lx) <= 1.0f) && (fabsf(ly) <= 1.0f);
     const bool closer = (t < tr.h.t) | ((t == tr.h.t) & (orig < tr.best_orig));
     const bool better = hit && (any_hit || closer);
     tr.h.t = better ? t : tr.h.t; tr.h.u = better ? lx : tr.h.u; tr.h.v = better ? ly : tr.h.v;
@@ -608,11 +625,11 @@ MTR_HD bool trav_quad_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hi
 
 // ONE_PAIR: the caller knows that no triangle leaf of the tree holds more than two triangles (scene trait kTrLeafPair): one
 // pass, no loop around it
-template <bool ONE_PAIR = false, class Stack>
-MTR_HD bool trav_leaf_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hit)
+template <bool ONE_PAIR = false, class RaySrc = RayOfTrav, class Stack>
+MTR_HD bool trav_leaf_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hit, const RaySrc ray = RaySrc())
 {
     const uint32_t code = ~(uint32_t)tr.cur;
-    if (code & kLeafQuadBit) return trav_quad_test(tr, sc, st, any_hit);
+    if (code & kLeafQuadBit) return trav_quad_test(tr, sc, st, any_hit, ray);
     const uint32_t first = code >> 2, cnt = ONE_PAIR ? (code & 1u) + 1u : (code & 3u) + 1u;
     bool found = false;
     // Moller-Trumbore [mitsuba3: Mesh::ray_intersect_triangle]: pvec = cross(d, e2); inv_det = 1 / dot(e1, pvec);
@@ -636,7 +653,7 @@ MTR_HD bool trav_leaf_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hi
         const f2 e1x{ g1.z, g1.w }, e1y{ g2.x, g2.y }, e1z{ g2.z, g2.w };
         const f2 e2x{ g3.x, g3.y }, e2y{ g3.z, g3.w }, e2z{ g4.x, g4.y };
         const uint32_t orig_a = fbits(g4.z), orig_b = fbits(g4.w);
-        const f3 o = tr.o, d = tr.d;
+        const f3 o = ray.o(tr), d = ray.d(tr);
         // pvec = cross(d, e2)
         const f2 pvx = fma2(e2z, d.y, neg2(mul2(e2y, d.z))), pvy = fma2(e2x, d.z, neg2(mul2(e2z, d.x))), pvz = fma2(e2y, d.x, neg2(mul2(e2x, d.y)));
         const f2 det = fma2(e1x, pvx, fma2(e1y, pvy, mul2(e1z, pvz)));                 // dot(e1, pvec)
@@ -652,7 +669,7 @@ MTR_HD bool trav_leaf_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hi
         // v_readlane in the persistent loop, 65.3 -> 67.9 ms on config 2; this form has the instruction count of the plain test.
         const f2 w = rsub2(1.0f, add2(u, v));
         {
-            const bool hit = (u.x >= -kEdgeEps) && (v.x >= -kEdgeEps) && (w.x >= -kEdgeEps) && (t.x >= 0.0f) && (t.x <= tr.tmax);
+            const bool hit = (u.x >= -kEdgeEps) && (v.x >= -kEdgeEps) && (w.x >= -kEdgeEps) && (t.x >= 0.0f) && (t.x <= ray.tmax(tr));
             const bool closer = (t.x < tr.h.t) | ((t.x == tr.h.t) & (orig_a < tr.best_orig));      // bitwise: no branches for three compares
             const bool better = hit && (any_hit ? !found : closer);
             found = found || hit;
@@ -660,7 +677,7 @@ MTR_HD bool trav_leaf_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hi
             tr.h.prim = better ? pa : tr.h.prim; tr.best_orig = better ? orig_a : tr.best_orig;
         }
         {
-            const bool hit = two && (u.y >= -kEdgeEps) && (v.y >= -kEdgeEps) && (w.y >= -kEdgeEps) && (t.y >= 0.0f) && (t.y <= tr.tmax);
+            const bool hit = two && (u.y >= -kEdgeEps) && (v.y >= -kEdgeEps) && (w.y >= -kEdgeEps) && (t.y >= 0.0f) && (t.y <= ray.tmax(tr));
             const bool closer = (t.y < tr.h.t) | ((t.y == tr.h.t) & (orig_b < tr.best_orig));
             const bool better = hit && (any_hit ? !found : closer);
             found = found || hit;
@@ -1060,6 +1077,31 @@ template <class S, class = void> struct stack_one_kernarg_base { static constexp
 template <class S> struct stack_one_kernarg_base<S, decltype((void)S::kOneKernargBase)> { static constexpr bool value = S::kOneKernargBase; };
 
 #if defined(__HIP_DEVICE_COMPILE__)
+// One pair of children of the root against a ray: the slab tests of flat_walk_device's rectangle stage.  `p0`, `p1`: the children exist.
+// (A function of values, not a lambda over the walk's locals: a closure is memory, and see trav_quad_test for what becomes of a ray
+// that is read from memory next to a splat.)
+template <bool ANY_HIT, uint32_t J>
+__device__ __forceinline__ void flat_slab_pair(const f3 id, const f3 noid, const float tb, const uint32_t sel0, const uint32_t sel1, const uint32_t sel2,
+                                               const char *root, const bool p0, const bool p1, uint32_t &qm, uint32_t &key1, uint32_t &key2)
+{
+    const char *pb = root + 48u * J;
+    const f2 nx = fma2(*(const f2 *)(pb + sel0), id.x, noid.x), fx = fma2(*(const f2 *)(pb + (sel0 ^ 8u)), id.x, noid.x);
+    const f2 ny = fma2(*(const f2 *)(pb + sel1), id.y, noid.y), fy = fma2(*(const f2 *)(pb + (sel1 ^ 8u)), id.y, noid.y);
+    const f2 nz = fma2(*(const f2 *)(pb + sel2), id.z, noid.z), fz = fma2(*(const f2 *)(pb + (sel2 ^ 8u)), id.z, noid.z);
+    const float tn0 = fmaxf(fmaxf(nx.x, ny.x), fmaxf(nz.x, 0.0f));
+    const float tf0 = fminf(fminf(fx.x, fy.x), fminf(fz.x, tb));
+    const float tn1 = fmaxf(fmaxf(nx.y, ny.y), fmaxf(nz.y, 0.0f));
+    const float tf1 = fminf(fminf(fx.y, fy.y), fminf(fz.y, tb));
+    const bool h0 = (tn0 <= tf0) && p0;
+    const bool h1 = (tn1 <= tf1) && p1;
+    qm |= (h0 ? 1u : 0u) << (2u * J);
+    qm |= (h1 ? 2u : 0u) << (2u * J);
+    if (!ANY_HIT) {
+        const uint32_t ka = h0 ? ((fbits(tn0) & ~7u) | (2u * J)) : 0xffffffffu, kb = h1 ? ((fbits(tn1) & ~7u) | (2u * J + 1u)) : 0xffffffffu;
+        key2 = min(key2, max(key1, ka)); key1 = min(key1, ka);
+        key2 = min(key2, max(key1, kb)); key1 = min(key1, kb);
+    }
+}
 // The "walk" of a scene with a FLAT TOP LEVEL (FlatTop).  Nothing here decides a hit: rectangles are intersected by
 // trav_quad_test, cube faces by trav_leaf_test, ties go to the original index — the arithmetic of every other walker; what
 // is different is only WHICH primitives a ray is spared, and every rule that spares one is one the tree walk applies too:
@@ -1073,28 +1115,36 @@ template <class S> struct stack_one_kernarg_base<S, decltype((void)S::kOneKernar
 // Shadow rays leave at their first hit; the rectangle tests of a wave whose rays all ended on a box are skipped.
 // TOP_LEAVES: the top level may hold triangle leaves beside rectangles and boxes (kTrFlatLeaves).  A compile-time fact, not a test of
 // FlatTop::prim_mask at run time: with the general form in the Cornell box's kernel config 2 took 54.1 instead of 52.8 ms (round 6).
+// (The ray comes BY VALUE and is never stored in the Trav, which carries the hit alone: o, d and what trav_init derives from them
+// are plain values from the first box to the last rectangle.  Round 8: they were a 32-byte object in private memory before, written
+// once and read back four times per walk — see trav_quad_test for the cause.)
 template <bool ANY_HIT, bool ONE_PAIR, bool TOP_LEAVES, class Stack>
-__device__ __forceinline__ void flat_walk_device(Trav &tr, const SceneView &sc, Stack &st)
+__device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o, const f3 d, const float tmax, Stack &st)
 {
     typedef WNode N;
+    Trav tr;                  // the hit so far, its tie-breaking index and the leaf under test; never the ray
+    const RayByValue ray{ o, d, tmax };
+    tr.h.t = kInf; tr.h.u = 0.0f; tr.h.v = 0.0f; tr.h.prim = -1;
+    tr.best_orig = 0xffffffffu;
+    st.reset();
+    if (!sc.n_slots) return tr.h;
     const char *root = (const char *)sc.wnodes;
     constexpr bool kOneBase = stack_one_kernarg_base<Stack>::value;
     const FlatHdr fh = kernarg_copy<FlatHdr, kOneBase>(sc.flat_off);
     bool live = true;
     // ---- boxes: face selection per box, uniform over the wave
     uint32_t fm = 0u;
-    const float omax = fmaxf(fmaxf(fabsf(tr.o.x), fabsf(tr.o.y)), fabsf(tr.o.z));
+    const float omax = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
     for (uint32_t b = 0; b < fh.n_boxes; ++b) {
         // (requesting the next box's rows before this one's arithmetic costs 45 scalar moves per iteration: measured, not kept)
         const FlatXf X = kernarg_copy<FlatXf, kOneBase>(sc.flat_off + sizeof(FlatHdr) + sizeof(FlatXf) * b);
         const q4 A = X.A, B = X.B, C = X.C, S = X.S;
-        const f3 o = tr.o, d = tr.d;
         const f3 ol = mk(fmaf(A.z, o.z, fmaf(A.y, o.y, fmaf(A.x, o.x, A.w))), fmaf(B.z, o.z, fmaf(B.y, o.y, fmaf(B.x, o.x, B.w))),
                          fmaf(C.z, o.z, fmaf(C.y, o.y, fmaf(C.x, o.x, C.w))));
         const f3 dl = mk(fmaf(A.z, d.z, fmaf(A.y, d.y, A.x * d.x)), fmaf(B.z, d.z, fmaf(B.y, d.y, B.x * d.x)),
                          fmaf(C.z, d.z, fmaf(C.y, d.y, C.x * d.x)));
         const f3 id = mk(safe_rcp(dl.x), safe_rcp(dl.y), safe_rcp(dl.z));
-        fm |= box_select(box_mag_bound(A, B, C, S, omax), ol, dl, id, tr.tmax) << (6u * b);
+        fm |= box_select(box_mag_bound(A, B, C, S, omax), ol, dl, id, tmax) << (6u * b);
     }
     st.prof_flat(0);
     // ---- the selected faces, in lock step (box = k / 6, face = k % 6; the face's leaf = child `face` of the box node)
@@ -1104,7 +1154,7 @@ __device__ __forceinline__ void flat_walk_device(Trav &tr, const SceneView &sc, 
             fm &= fm - 1u;
             const uint32_t box = (k * 43u) >> 8, face = k - 6u * box;
             tr.cur = *(const int32_t *)(root + (size_t)(fh.node0 + box) * N::kBytes + N::kRefOff + 4u * face);
-            const bool found = trav_leaf_test<true>(tr, sc, st, ANY_HIT);
+            const bool found = trav_leaf_test<true>(tr, sc, st, ANY_HIT, ray);
             if (ANY_HIT && found) live = false;
         }
     }
@@ -1113,9 +1163,12 @@ __device__ __forceinline__ void flat_walk_device(Trav &tr, const SceneView &sc, 
     // (a segment-box pre-test for shadow rays — the box of [o, o + d tmax] against the rectangles' boxes, 12 comparisons per pair
     // instead of the slab tests — was measured in round 6: 53.4 -> 53.9 ms; some lane of nearly every wave grazes the light's box)
     if (__ballot(live) != 0ull) {
-        const f3 id = tr.id, noid = tr.noid;
-        const float tb = fminf(tr.tmax, tr.h.t);          // (no kCullSlack: rectangles and cube faces are no slivers — and the two multiplies cost config 2 1.6 %)
-        const uint32_t sel0 = tr.sel[0], sel1 = tr.sel[1], sel2 = tr.sel[2];
+        // reciprocal direction and entry-plane offsets as trav_init derives them, here where they are first needed: nothing of
+        // them is held across the box stage
+        const f3 id = mk(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
+        const f3 noid = mk(-(o.x * id.x), -(o.y * id.y), -(o.z * id.z));
+        const uint32_t sel0 = id.x < 0.0f ? 8u : 0u, sel1 = 16u + (id.y < 0.0f ? 8u : 0u), sel2 = 32u + (id.z < 0.0f ? 8u : 0u);
+        const float tb = fminf(tmax, tr.h.t);          // (no kCullSlack: rectangles and cube faces are no slivers — and the two multiplies cost config 2 1.6 %)
         uint32_t qm = 0u;
         // nearest / second nearest entry distance as ORDERED KEYS: the bits of a non-negative float order like the float, so
         // key = (bits(tn) & ~7) | child orders the candidates by entry distance with the child index along for the ride — one
@@ -1124,34 +1177,19 @@ __device__ __forceinline__ void flat_walk_device(Trav &tr, const SceneView &sc, 
         uint32_t key1 = 0xffffffffu, key2 = 0xffffffffu;
         // one pair of children of the root per step; the offsets are compile-time constants (the loop is unrolled: a pair whose
         // children are absent has inverted boxes and fails by itself), a shadow ray keeps no entry distances
-        auto slab_pair = [&](uint32_t j) {
-            const char *pb = root + 48u * j;
-            const f2 nx = fma2(*(const f2 *)(pb + sel0), id.x, noid.x), fx = fma2(*(const f2 *)(pb + (sel0 ^ 8u)), id.x, noid.x);
-            const f2 ny = fma2(*(const f2 *)(pb + sel1), id.y, noid.y), fy = fma2(*(const f2 *)(pb + (sel1 ^ 8u)), id.y, noid.y);
-            const f2 nz = fma2(*(const f2 *)(pb + sel2), id.z, noid.z), fz = fma2(*(const f2 *)(pb + (sel2 ^ 8u)), id.z, noid.z);
-            const float tn0 = fmaxf(fmaxf(nx.x, ny.x), fmaxf(nz.x, 0.0f));
-            const float tf0 = fminf(fminf(fx.x, fy.x), fminf(fz.x, tb));
-            const float tn1 = fmaxf(fmaxf(nx.y, ny.y), fmaxf(nz.y, 0.0f));
-            const float tf1 = fminf(fminf(fx.y, fy.y), fminf(fz.y, tb));
-            const bool h0 = (tn0 <= tf0) && (TOP_LEAVES ? ((fh.prim_mask >> (2u * j)) & 1u) != 0u : 2u * j < fh.n_quads);
-            const bool h1 = (tn1 <= tf1) && (TOP_LEAVES ? ((fh.prim_mask >> (2u * j + 1u)) & 1u) != 0u : 2u * j + 1u < fh.n_quads);
-            qm |= (h0 ? 1u : 0u) << (2u * j);
-            qm |= (h1 ? 2u : 0u) << (2u * j);
-            if (!ANY_HIT) {
-                const uint32_t ka = h0 ? ((fbits(tn0) & ~7u) | (2u * j)) : 0xffffffffu, kb = h1 ? ((fbits(tn1) & ~7u) | (2u * j + 1u)) : 0xffffffffu;
-                key2 = min(key2, max(key1, ka)); key1 = min(key1, ka);
-                key2 = min(key2, max(key1, kb)); key1 = min(key1, kb);
-            }
-        };
+#define MTR_FLAT_SLAB_PAIR(J) flat_slab_pair<ANY_HIT, J>(id, noid, tb, sel0, sel1, sel2, root, \
+            TOP_LEAVES ? ((fh.prim_mask >> (2u * J)) & 1u) != 0u : 2u * J < fh.n_quads, \
+            TOP_LEAVES ? ((fh.prim_mask >> (2u * J + 1u)) & 1u) != 0u : 2u * J + 1u < fh.n_quads, qm, key1, key2)
         if (TOP_LEAVES) {
-            slab_pair(0u);
-            if (fh.prim_mask > 3u) slab_pair(1u);
-            if (fh.prim_mask > 15u) slab_pair(2u);
-            if (kWide > 6u && fh.prim_mask > 63u) slab_pair(3u);
+            MTR_FLAT_SLAB_PAIR(0u);
+            if (fh.prim_mask > 3u) MTR_FLAT_SLAB_PAIR(1u);
+            if (fh.prim_mask > 15u) MTR_FLAT_SLAB_PAIR(2u);
+            if (kWide > 6u && fh.prim_mask > 63u) MTR_FLAT_SLAB_PAIR(3u);
         } else {
-            slab_pair(0u); slab_pair(1u); slab_pair(2u);
-            if (kWide > 6u && fh.n_quads > 6u) slab_pair(3u);
+            MTR_FLAT_SLAB_PAIR(0u); MTR_FLAT_SLAB_PAIR(1u); MTR_FLAT_SLAB_PAIR(2u);
+            if (kWide > 6u && fh.n_quads > 6u) MTR_FLAT_SLAB_PAIR(3u);
         }
+#undef MTR_FLAT_SLAB_PAIR
         if (!live) qm = 0u;
         st.prof_flat(2);
         for (uint32_t it = 0; __ballot(qm != 0u) != 0ull; ++it) {
@@ -1160,13 +1198,14 @@ __device__ __forceinline__ void flat_walk_device(Trav &tr, const SceneView &sc, 
                 qm &= ~(1u << k);
                 tr.cur = *(const int32_t *)(root + N::kRefOff + 4u * k);
                 // (a rectangle or — only where the top level holds triangle leaves — a leaf of one or two pairs)
-                const bool found = (!TOP_LEAVES || is_quad_leaf(tr.cur)) ? trav_quad_test(tr, sc, st, ANY_HIT) : trav_leaf_test<ONE_PAIR>(tr, sc, st, ANY_HIT);
+                const bool found = (!TOP_LEAVES || is_quad_leaf(tr.cur)) ? trav_quad_test(tr, sc, st, ANY_HIT, ray)
+                                                                         : trav_leaf_test<ONE_PAIR>(tr, sc, st, ANY_HIT, ray);
                 if (ANY_HIT ? found : (it == 0u && tr.h.t < bitsf(key2 & ~7u))) qm = 0u;
             }
         }
     }
     st.prof_flat(4);
-    tr.cur = kTravDone;
+    return tr.h;
 }
 #endif
 
@@ -1177,16 +1216,13 @@ __device__ __forceinline__ void flat_walk_device(Trav &tr, const SceneView &sc, 
 template <bool ANY_HIT, bool ONE_PAIR = false, int FLAT = 0, class Stack>
 MTR_HD Hit traverse(const SceneView &sc, f3 o, f3 d, float tmax, Stack &st)
 {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (FLAT) return flat_walk_device<ANY_HIT, ONE_PAIR, FLAT == 2>(sc, o, d, tmax, st);
+#endif
     Trav tr;
     trav_init(tr, sc, o, d, tmax, st);
 #ifdef MTR_PROFILE_SIMT
     uint32_t my_nodes = 0;
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (FLAT) {
-        if (tr.cur != kTravDone) flat_walk_device<ANY_HIT, ONE_PAIR, FLAT == 2>(tr, sc, st);
-        return tr.h;
-    }
 #endif
     if (sc.wnodes) {
         // three kinds of steps, each run by the whole wave at once: inner nodes until no lane holds one, then one

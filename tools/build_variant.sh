@@ -14,17 +14,25 @@ if [ "$ref" != "-" ]; then
 fi
 cd "$src/mitransient_amd/csrc"
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -munsafe-fp-atomics -Wno-unused-function"
+KFLAGS=$(sed -n 's/^KFLAGS *= *//p' Makefile)      # the flags THAT tree's Makefile gives mtr_kernels.hip alone (none before round 8)
 if [[ " $* " == *" -DMTR_ONLY_C2 "* ]]; then
   h=$(cat mtr_api.hip mtr_wavefront.hip mtr_splat.hip mtr_bvh.cpp mtr_scene_host.cpp *.h ../../include/mitransient_amd.h | sha256sum | cut -c1-16)
   od="$root/ab/obj/$h"; mkdir -p "$od"
   for f in mtr_api.hip mtr_wavefront.hip mtr_splat.hip mtr_bvh.cpp mtr_scene_host.cpp; do
     [ -f "$od/$f.o" ] || /opt/rocm/bin/hipcc $FL -c $f -o "$od/$f.o" &
   done
-  /opt/rocm/bin/hipcc $FL "$@" -c mtr_kernels.hip -o "$od/kernels_$name.o" &
+  /opt/rocm/bin/hipcc $FL $KFLAGS "$@" -c mtr_kernels.hip -o "$od/kernels_$name.o" &
   wait
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o "$root/ab/libs/lib_$name.so" "$od"/mtr_api.hip.o "$od"/mtr_wavefront.hip.o "$od"/mtr_splat.hip.o "$od"/mtr_bvh.cpp.o "$od"/mtr_scene_host.cpp.o "$od/kernels_$name.o"
 else
-  /opt/rocm/bin/hipcc $FL "$@" -shared -o "$root/ab/libs/lib_$name.so" mtr_api.hip mtr_kernels.hip mtr_wavefront.hip mtr_splat.hip mtr_bvh.cpp mtr_scene_host.cpp
+  # every source, by that tree's own Makefile (its per-file flags included), with the extra flags on all of them — in a copy,
+  # so that the working tree keeps its own library and objects
+  if [ "$ref" = "-" ]; then
+    src=$(mktemp -d); mkdir -p "$src/mitransient_amd" && cp -r "$root/mitransient_amd/csrc" "$src/mitransient_amd/" && cp -r "$root/include" "$src/"
+    cd "$src/mitransient_amd/csrc" && rm -f libmitransient_amd.so *.o
+  fi
+  make CXXFLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -munsafe-fp-atomics -Wno-unused-function $*" libmitransient_amd.so
+  cp libmitransient_amd.so "$root/ab/libs/lib_$name.so"
 fi
-[ "$ref" != "-" ] && rm -rf "$src"
+[ "$src" != "$root" ] && rm -rf "$src"
 echo "built ab/libs/lib_$name.so"

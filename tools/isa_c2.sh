@@ -1,10 +1,11 @@
 #!/bin/bash
-# tools/isa_c2.sh <tag> [extra flags] — static ISA statistics of the ONE k_fused instantiation config 2 runs (cross-compiles, ~1 min):
+# tools/isa_c2.sh <tag> [extra flags] — static ISA statistics of the ONE k_fused instantiation config 2 runs (cross-compiles, ~1 min; the Makefile's flags for mtr_kernels.hip — pass -fslp-vectorize for the packed form):
 # registers / spills, instruction mix of the persistent loop and of its two inlined tree walks.  Output under /tmp/isa_<tag>/.
 tag=$1; shift
-src="$(cd "$(dirname "$0")/../mitransient_amd/csrc" && pwd)/mtr_kernels.hip"
+csrc="$(cd "$(dirname "$0")/../mitransient_amd/csrc" && pwd)"; src="$csrc/mtr_kernels.hip"
+KFLAGS=$(sed -n 's/^KFLAGS *= *//p' "$csrc/Makefile")      # what the Makefile gives mtr_kernels.hip alone
 d=/tmp/isa_$tag; mkdir -p $d; cd $d
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -munsafe-fp-atomics -Wno-unused-function -DMTR_ONLY_C2 "$@" \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -munsafe-fp-atomics -Wno-unused-function $KFLAGS -DMTR_ONLY_C2 "$@" \
   -Rpass-analysis=kernel-resource-usage --save-temps -c "$src" -o k.o 2> log.txt
 grep -A12 "k_fusedILb1ELb1ELb0ELi4ELb0ELb0ELb0ELj15E" log.txt | grep -E "VGPRs:|Spill|Scratch" | sed 's/.*remark: *//' | tr '\n' ' '; echo
 python3 - <<'PY'

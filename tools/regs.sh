@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/regs.sh [file.hip] [pattern] — VGPRs / spills / occupancy per kernel (cross-compiles, no GPU needed)
 f=${1:-mtr_kernels.hip}; pat=${2:-.}
-cd "$(dirname "$0")/../mitransient_amd/csrc" && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -munsafe-fp-atomics -Wno-unused-function $EXTRA \
+cd "$(dirname "$0")/../mitransient_amd/csrc" && KFLAGS=$([ "$f" = mtr_kernels.hip ] && sed -n 's/^KFLAGS *= *//p' Makefile; true) && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -munsafe-fp-atomics -Wno-unused-function $KFLAGS $EXTRA \
   -Rpass-analysis=kernel-resource-usage -c $f -o /dev/null 2>&1 | python3 -c "
 import sys, re
 cur = None; rows = {}
