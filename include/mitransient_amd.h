@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 20
+#define MTR_ABI_VERSION 21
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -136,7 +136,9 @@ typedef struct mtr_film_desc {
      * makes the tensor H x W x (2F + 1) — per frequency the real and imaginary part of sum(value * exp(i * phase)),
      * phase = fmod(-2 pi f (opl - start_opl), 2 pi), then the weight channel — instead of time bins; every finite optical
      * path length counts (temporal_bins / bin_width_opl only choose the frequencies, on the host).  Monochromatic: the
-     * value is channel 0 of the contribution.  frequencies: host pointer, read during the call that takes the desc. */
+     * value is channel 0 of the contribution.  frequencies: host pointer, read during the call that takes the desc.
+     * (ABI 21) Both integrators render into it: transient_path, and the NLOS tier with a Single or Confocal capture (an
+     * Exhaustive capture needs the exhaustive_scan rows a phasor film does not have: MTR_ERR_UNSUPPORTED). */
     uint32_t n_frequencies;
     const float *frequencies;
 } mtr_film_desc;
@@ -428,7 +430,14 @@ int  mtr_film_clear(mtr_ctx *, const mtr_film_desc *, float *transient_hwt4 /*de
  *   transient_hwt4 : device f32 (H, W, T, 4)  channels R,G,B,W (W stays 0)
  *   steady_hw4     : device f32 (H, W, 4)     sum of L over samples, and the sample count in .w
  * counters/times may be NULL.  Asynchronous on the context stream unless
- * counters or times are requested (then it synchronises the stream). */
+ * counters or times are requested (then it synchronises the stream).
+ * A phasor film (mtr_film_desc.n_frequencies > 0): transient_hwt4 is device f32 (H, W, 2F + 1) instead.
+ * (ABI 21) ... also for a scene with the NLOS tier, Single or Confocal capture (up to ABI 20: MTR_ERR_UNSUPPORTED).  Under
+ * MTR_MODE_AUTO such a render runs the fused kernel — (Re, Im) rows in LDS — when the scene has plain shading, the 2F floats
+ * of a row fit LDS beside the staged scene and F <= 16 (measured: DESIGN.md section 6), and the wavefront organisation ((opl,
+ * value) records) otherwise; MTR_MODE_FUSED runs any F whose rows fit and is MTR_ERR_UNSUPPORTED with extended shading or
+ * rows that do not fit.  MTR_ERR_UNSUPPORTED, before any launch and with both tensors
+ * untouched: an Exhaustive capture with a phasor film, and MTR_FLAG_POLARIZED on the NLOS tier or with a phasor film. */
 int  mtr_render(mtr_scene *, const mtr_render_params *,
                 float *transient_hwt4, float *steady_hw4,
                 mtr_counters *counters_out /*host*/, mtr_kernel_times *times_out /*host*/);

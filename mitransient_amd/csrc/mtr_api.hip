@@ -252,6 +252,8 @@ int mtr_scene_set_nlos(mtr_scene *s, const mtr_nlos_desc *n)
     memcpy(d.camera.to_world, s->cam.tw, sizeof s->cam.tw);
     d.camera.near_clip = s->cam.near_clip; d.camera.far_clip = s->cam.far_clip;
     d.nlos = n;
+    if (d.film.n_frequencies && n->capture_type == MTR_CAPTURE_EXHAUSTIVE)
+        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_scene_set_nlos: an Exhaustive capture (MTR_CAPTURE_EXHAUSTIVE) is not available with a phasor_hdr_film");
     HostNlos hn;
     if (const char *msg = derive_nlos(d, hn)) return fail(c, MTR_ERR_INVALID, std::string("mtr_scene_set_nlos: ") + msg);
     NlosDev &D = s->nlos;
@@ -743,10 +745,27 @@ static int resolve_mode(mtr_scene *s, const mtr_render_params *p, uint32_t n_pix
         if (developed_ok) *developed_ok = 0u;
         return MTR_OK;
     }
+    // a phasor film has one (Re, Im) row per pixel: no [laser_x][laser_y] rows for the illuminated points of an Exhaustive capture
+    if (s->nlos.on && f.n_freq && s->nlos.k.capture_type == MTR_CAPTURE_EXHAUSTIVE)
+        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: an Exhaustive capture (MTR_CAPTURE_EXHAUSTIVE) is not available with a phasor_hdr_film");
+    if (s->nlos.on && f.n_freq && mode != MTR_MODE_WAVEFRONT) {
+        // NLOS tier with a phasor film.  The fused kernel (k_fused<NLOS, PHASOR>) needs plain shading and (Re, Im) rows that fit LDS beside
+        // the scene — it has LDS rows or none: fused_plan — and pays 2F LDS float atomics per contribution, where the wavefront
+        // organisation appends one 16-byte record and k_wf_phasor_scatter folds the records per frequency in registers.  Config 4's share
+        // with the film swapped (confocal 256 x 256, 512 spp, flat-shaded 'Z', tools/nlos_phasor_bench.py), fused / wavefront: F = 16
+        // 7.00 / 7.38 ms, F = 27 8.91 / 7.65, F = 43 11.9 / 8.2, F = 412 91.3 / 16.0 (run-to-run spread 0.1 - 0.3 ms): AUTO takes the
+        // tier's default, the fused kernel, up to 16 frequencies and the wavefront organisation beyond
+        constexpr uint32_t kNlosPhasorFusedMaxF = 16u;
+        const bool fused_ok = !s->dev.has_rough && fused_probe(s, p, n_pixels, spp_chunk).hist_lds;
+        if (mode == MTR_MODE_FUSED && !fused_ok)
+            return fail(c, MTR_ERR_UNSUPPORTED, s->dev.has_rough
+                ? "mtr_render: rough BSDFs / smooth-shaded triangles with a phasor film or deterministic rows need the wavefront mode"
+                : "mtr_render: the (Re, Im) rows of this phasor_hdr_film do not fit LDS: the NLOS tier renders it in the wavefront mode");
+        if (mode == MTR_MODE_AUTO) mode = (fused_ok && f.n_freq <= kNlosPhasorFusedMaxF) ? MTR_MODE_FUSED : MTR_MODE_WAVEFRONT;
+    }
     if (s->nlos.on && mode == MTR_MODE_AUTO)                             // (wavefront = the second organisation: on request, and for
         mode = (s->dev.has_rough && (p->flags & MTR_FLAG_DETERMINISTIC)) ? MTR_MODE_WAVEFRONT : MTR_MODE_FUSED;      // deterministic rows with the extended shading)
     if (f.n_freq) {                      // phasor film: (opl, value) records -> wavefront pipeline by default; LDS (Re, Im) rows in the fused kernel on request
-        if (s->nlos.on) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: phasor_hdr_film is not available for the NLOS tier");
         if (mode == MTR_MODE_AUTO) mode = MTR_MODE_WAVEFRONT;
     }
     if (s->dev.has_rough) {              // GGX lobes / smooth normals / bitmaps: f32 rows only (fused), or the wavefront pipeline

@@ -204,6 +204,27 @@ struct LdsPhasorSink {
     }
 };
 
+// ... under the NLOS loop, whose four walks per bounce leave no scalar register to spare (reload_nlos): only the row's address
+// rides through the walks; the frequency table, its length and start_opl are read from the kernarg segment where a contribution is made
+struct LdsPhasorSinkNlos {
+    float *row;                        // the pixel's slot: 2F floats
+    uint32_t film_w, lane, n_splats;
+    SplatLog log;
+    __device__ __forceinline__ void splat(uint32_t fx, uint32_t fy, uint32_t bin, float r, float g, float b,
+                                          float opl, uint32_t depth, uint32_t kind)
+    {
+        const Film fl = kernarg_copy<Film>(offsetof(FusedArgs, film));
+        const float rel = opl - fl.start_opl;                                // phasor_hdr_film.py:249
+        for (uint32_t f = 0; f < fl.n_freq; ++f) {
+            float c, sn;
+            phasor_term(fl.freq[f], rel, c, sn);
+            lds_add(row + 2u * f, r * c); lds_add(row + 2u * f + 1u, r * sn);
+        }
+        ++n_splats;
+        if (log.rec) log_splat(log, lane, depth, kind, fy * film_w + fx, bin, r, g, b, opl);
+    }
+};
+
 // contract form: f32 atomics straight into the (H,W,T,4) tensor in HBM
 struct GlobalAtomicSink {
     float *film; uint32_t film_w, bins;
@@ -493,7 +514,12 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                 pp.px = w & 0xffffu; pp.py = w >> 16;
                 if (!NLOS) { film_l = kernarg_copy<Film, kLean>(offsetof(FusedArgs, film)); rc_l = kernarg_copy<RenderConst, kLean>(offsetof(FusedArgs, rc)); }
             };
-            if (PHASOR) {
+            if (PHASOR && NLOS) {
+                LdsPhasorSinkNlos sink; sink.row = s_hist + slot * T;
+                sink.film_w = a.film.width; sink.lane = p.lane; sink.n_splats = 0; sink.log = a.log;
+                alive = nlos_bounce<ROUGH, TR>(p, sv, nc_l, film_l, rc_l, st, sink, bstat, reload_nlos);
+                n_splats += sink.n_splats;
+            } else if (PHASOR) {
                 LdsPhasorSink sink; sink.row = s_hist + slot * T; sink.freq = a.film.freq; sink.n_freq = a.film.n_freq;
                 sink.start_opl = a.film.start_opl; sink.film_w = a.film.width; sink.lane = p.lane; sink.n_splats = 0; sink.log = a.log;
                 alive = path_bounce<ROUGH, TR>(p, sv, film_l, rc_l, st, sink, bstat, refresh, unwarp);
@@ -771,6 +797,9 @@ bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_
     if (g_fit >= 1) G = g_want < g_fit ? g_want : g_fit;
     else if (fixed_b + row_bytes + 64 <= kLdsMax) G = 1;                  // one long row still fits the CU
     else { G = g_want; cfg.hist_lds = false; }                          // row > LDS: f32 atomics to HBM
+    // phasor_hdr_film: the (Re, Im) rows are LDS rows or nothing (k_fused<PHASOR> has no global-atomic form) — a frequency table too long
+    // for LDS beside the staged scene is the wavefront organisation's (resolve_mode)
+    if (film.n_freq && !cfg.hist_lds) return false;
     cfg.fixed = det && cfg.hist_lds;
     cfg.traits = (cfg.rough ? (sc.traits & kTrNoLobes) : (sc.traits & ~kTrNoLobes)) & ~kTrGrey;
     if (grey) cfg.traits |= kTrGrey;                 // (g_fit >= 1 by the bound on the bins above: hist_lds holds)
@@ -841,9 +870,10 @@ static hipError_t launch_fused_s(const FusedArgs &args, const FusedConfig &cfg, 
     if (NLOS || args.film.n_freq || cfg.rough || cfg.fixed || !cfg.scene_lds || !cfg.hist_lds || cfg.traits != MTR_C2_TRAITS || cfg.per_cu <= 3) return hipErrorInvalidValue;
     k = k_fused<true, true, false, MTR_FUSED_MIN_WAVES, false, false, false, MTR_C2_TRAITS>;
 #else
-    if (!NLOS && args.film.n_freq) {
-        if (!cfg.hist_lds || cfg.rough) return hipErrorInvalidValue;       // (2F floats per row always fit: fused_plan)
-        k = cfg.scene_lds ? k_fused<true, true, false, MTR_FUSED_MIN_WAVES, true> : k_fused<false, true, false, MTR_FUSED_MIN_WAVES, true>;
+    if (args.film.n_freq) {
+        if (!cfg.hist_lds || cfg.rough) return hipErrorInvalidValue;       // ((Re, Im) rows live in LDS or nowhere: fused_plan refuses the others)
+        if constexpr (NLOS) k = cfg.scene_lds ? k_fused<true, true, true, 3, true> : k_fused<false, true, true, 3, true>;      // (the NLOS loop: the 168-register form, below)
+        else k = cfg.scene_lds ? k_fused<true, true, false, MTR_FUSED_MIN_WAVES, true> : k_fused<false, true, false, MTR_FUSED_MIN_WAVES, true>;
     }
     else if (cfg.rough) {                  // scenes with GGX lobes / smooth normals / bitmaps: the f32 organisations only, 168 registers for the larger shading
         if (cfg.fixed) return hipErrorInvalidValue;

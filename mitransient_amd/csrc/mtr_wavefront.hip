@@ -832,7 +832,7 @@ __global__ void __launch_bounds__(kBlock, 2) k_wf_nlos_bounce(const WfArgs a)
                 RecordSink sink;
                 sink.rec = a.rec; sink.s_rec_count = s_rec; sink.rec_cap = a.rec_cap;
                 sink.film = a.film_out; sink.film_w = a.film.width; sink.bins = a.film.bins;
-                sink.n_freq = 0u; sink.freq = nullptr; sink.start_opl = a.film.start_opl;
+                sink.n_freq = a.film.n_freq; sink.freq = a.film.freq; sink.start_opl = a.film.start_opl;      // (phasor film: records keep the optical path length)
                 sink.p_local = pl; sink.p_seg = pl - pl0; sink.lane = p.lane;
                 sink.n_splats = 0; sink.n_overflow = 0; sink.log = a.log;
                 BounceStats bs; bs.closest = 0; bs.shadow = 0;

@@ -17,6 +17,16 @@ class CaptureType(enum.IntEnum):                  # transientnlospath.py:12-13
     Exhaustive = 3
 
 
+def check_exhaustive_film(capture_type, film):
+    """An Exhaustive capture stores one histogram per illuminated point (the ``exhaustive_scan`` rows of a
+    transient_hdr_film); a phasor_hdr_film has none.  The reference fails in ``prepare`` on ``film.laser_scan_width``
+    (transientnlospath.py:340-381); here the combination is named, before any GPU work."""
+    from ..films.phasor_hdr_film import PhasorHDRFilm
+    if int(capture_type) == CaptureType.Exhaustive and isinstance(film, PhasorHDRFilm):
+        raise ValueError("transient_nlos_path: capture_type 'exhaustive' is not available with a phasor_hdr_film "
+                         "(it needs a transient_hdr_film with exhaustive_scan=True; use capture_type 'single' or 'confocal')")
+
+
 class TransientNLOSPath(TransientADIntegrator):
     def __init__(self, props):
         super().__init__(props)
@@ -65,6 +75,7 @@ class TransientNLOSPath(TransientADIntegrator):
         if not isinstance(sensor, (NLOSCaptureMeter, PerspectiveSensor)):
             raise AssertionError("transient_nlos_path needs a nlos_capture_meter or a perspective sensor")
         film = sensor.film()
+        check_exhaustive_film(self.capture_type, film)
         if self.capture_type == 3:
             if not getattr(film, "exhaustive_scan", False):
                 raise AssertionError("capture_type 'exhaustive' needs a film with exhaustive_scan=True and "

@@ -830,6 +830,8 @@ def film_desc_from(film) -> _cabi.mtr_film_desc:
 
 def nlos_desc_from(integrator, sensor, emitter, relay_shape: int) -> _cabi.mtr_nlos_desc:
     """mtr_nlos_desc from the live plugin objects (so that nlos.focus_emitter_* edits are picked up)."""
+    from .integrators.transientnlospath import check_exhaustive_film
+    check_exhaustive_film(integrator.capture_type, sensor.film())
     n = _cabi.mtr_nlos_desc()
     origin = getattr(sensor, "sensor_origin", (0.0, 0.0, 0.0))       # perspective sensor: unused
     for k in range(3):
