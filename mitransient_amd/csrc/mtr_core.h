@@ -194,35 +194,54 @@ MTR_HD f3 cosine_hemisphere(float u1, float u2)
 // 16-byte quads: every record below is read as whole quads (ds_read_b128 from LDS,
 // global_load_dwordx4 from HBM/L2).
 struct alignas(16) q4 { float x, y, z, w; };
-// two independent f32 lanes of one register pair: v_pk_fma_f32 on the device (same roundings as two fmaf)
+// two independent f32 values that one site evaluates side by side (two triangles of a leaf, two children of a node).
+// The pair is STRUCTURE; what it is lowered to is the template argument of the helpers: PK = one packed instruction on a register pair
+// (v_pk_fma_f32, v_pk_mul_f32, ...), !PK = two plain f32 instructions.  Either form rounds the same (-ffp-contract=off: an fma only
+// where the source says fmaf), so results do not depend on it.  The host has the plain form only.
+// MTR_PAIR_SCALAR, given to a translation unit on its command line, chooses the plain form per family of sites (a mask; 0 when absent:
+// every site packed).  A file built with the SLP vectoriser gets plain pairs packed again by the compiler, so there the mask
+// means something only together with -fno-slp-vectorize (Makefile: KFLAGS, mtr_kernels.hip alone).
+#define MTR_PAIR_LEAF  1      // the pair Moller-Trumbore of trav_leaf_test
+#define MTR_PAIR_SLABS 2      // the slab pairs of flat_slab_pair (the flat walk's rectangle stage)
+#define MTR_PAIR_NODES 4      // the node steps of the tree walks: trav_node_step, wide_node_test, qwide_node_step, q8_node_step
+#define MTR_PAIR_ALL   7
+#ifndef MTR_PAIR_SCALAR
+#define MTR_PAIR_SCALAR 0
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+constexpr bool kPkLeaf = !(MTR_PAIR_SCALAR & MTR_PAIR_LEAF), kPkSlabs = !(MTR_PAIR_SCALAR & MTR_PAIR_SLABS), kPkNodes = !(MTR_PAIR_SCALAR & MTR_PAIR_NODES);
+#else
+constexpr bool kPkLeaf = false, kPkSlabs = false, kPkNodes = false;
+#endif
 struct f2 { float x, y; };
+// plain: the only form the host has
+MTR_HD f2 mul2_plain(f2 a, f2 b) { return f2{ a.x * b.x, a.y * b.y }; }
+MTR_HD f2 sub2_plain(f2 a, f2 b) { return f2{ a.x - b.x, a.y - b.y }; }
+MTR_HD f2 add2_plain(f2 a, f2 b) { return f2{ a.x + b.x, a.y + b.y }; }
+MTR_HD f2 fma2_plain(f2 a, f2 b, f2 c) { return f2{ fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y) }; }
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef float v2f_ __attribute__((ext_vector_type(2)));
-MTR_HD f2 mul2(f2 a, f2 b) { const v2f_ r = v2f_{ a.x, a.y } * v2f_{ b.x, b.y }; return f2{ r.x, r.y }; }
-MTR_HD f2 mul2(f2 a, float b) { const v2f_ r = v2f_{ a.x, a.y } * v2f_{ b, b }; return f2{ r.x, r.y }; }
-MTR_HD f2 rsub2(float a, f2 b) { const v2f_ r = v2f_{ a, a } - v2f_{ b.x, b.y }; return f2{ r.x, r.y }; }          // a - b
-MTR_HD f2 add2(f2 a, f2 b) { const v2f_ r = v2f_{ a.x, a.y } + v2f_{ b.x, b.y }; return f2{ r.x, r.y }; }
-MTR_HD f2 fma2(f2 a, f2 b, f2 c) { const v2f_ r = __builtin_elementwise_fma(v2f_{ a.x, a.y }, v2f_{ b.x, b.y }, v2f_{ c.x, c.y }); return f2{ r.x, r.y }; }
-MTR_HD f2 fma2(f2 a, float b, f2 c) { const v2f_ r = __builtin_elementwise_fma(v2f_{ a.x, a.y }, v2f_{ b, b }, v2f_{ c.x, c.y }); return f2{ r.x, r.y }; }
-#else
-MTR_HD f2 mul2(f2 a, f2 b) { return f2{ a.x * b.x, a.y * b.y }; }
-MTR_HD f2 mul2(f2 a, float b) { return f2{ a.x * b, a.y * b }; }
-MTR_HD f2 rsub2(float a, f2 b) { return f2{ a - b.x, a - b.y }; }
-MTR_HD f2 add2(f2 a, f2 b) { return f2{ a.x + b.x, a.y + b.y }; }
-MTR_HD f2 fma2(f2 a, f2 b, f2 c) { return f2{ fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y) }; }
-MTR_HD f2 fma2(f2 a, float b, f2 c) { return f2{ fmaf(a.x, b, c.x), fmaf(a.y, b, c.y) }; }
-#endif
-MTR_HD f2 neg2(f2 a) { return f2{ -a.x, -a.y }; }
-MTR_HD f2 fma2(f2 a, float b, float c)
+__device__ __forceinline__ f2 pk2_(v2f_ r) { return f2{ r.x, r.y }; }
+template <bool PK> MTR_HD f2 mul2(f2 a, f2 b) { if constexpr (PK) return pk2_(v2f_{ a.x, a.y } * v2f_{ b.x, b.y }); else return mul2_plain(a, b); }
+template <bool PK> MTR_HD f2 sub2(f2 a, f2 b) { if constexpr (PK) return pk2_(v2f_{ a.x, a.y } - v2f_{ b.x, b.y }); else return sub2_plain(a, b); }
+template <bool PK> MTR_HD f2 add2(f2 a, f2 b) { if constexpr (PK) return pk2_(v2f_{ a.x, a.y } + v2f_{ b.x, b.y }); else return add2_plain(a, b); }
+template <bool PK> MTR_HD f2 fma2(f2 a, f2 b, f2 c)
 {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    const v2f r = __builtin_elementwise_fma(v2f{ a.x, a.y }, v2f{ b, b }, v2f{ c, c });
-    return f2{ r.x, r.y };
-#else
-    return f2{ fmaf(a.x, b, c), fmaf(a.y, b, c) };
-#endif
+    if constexpr (PK) return pk2_(__builtin_elementwise_fma(v2f_{ a.x, a.y }, v2f_{ b.x, b.y }, v2f_{ c.x, c.y }));
+    else return fma2_plain(a, b, c);
 }
+#else
+template <bool PK> MTR_HD f2 mul2(f2 a, f2 b) { return mul2_plain(a, b); }
+template <bool PK> MTR_HD f2 sub2(f2 a, f2 b) { return sub2_plain(a, b); }
+template <bool PK> MTR_HD f2 add2(f2 a, f2 b) { return add2_plain(a, b); }
+template <bool PK> MTR_HD f2 fma2(f2 a, f2 b, f2 c) { return fma2_plain(a, b, c); }
+#endif
+// a float beside a pair stands in both of its halves
+template <bool PK> MTR_HD f2 mul2(f2 a, float b) { return mul2<PK>(a, f2{ b, b }); }
+template <bool PK> MTR_HD f2 rsub2(float a, f2 b) { return sub2<PK>(f2{ a, a }, b); }          // a - b
+template <bool PK> MTR_HD f2 fma2(f2 a, float b, f2 c) { return fma2<PK>(a, f2{ b, b }, c); }
+template <bool PK> MTR_HD f2 fma2(f2 a, float b, float c) { return fma2<PK>(a, f2{ b, b }, f2{ c, c }); }
+MTR_HD f2 neg2(f2 a) { return f2{ -a.x, -a.y }; }
 MTR_HD uint32_t fbits(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
 MTR_HD float bitsf(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
 
@@ -551,18 +570,18 @@ MTR_HD void trav_node_step(Trav &tr, const SceneView &sc, Stack &st)
     int32_t c0, c1;
     if (sc.node_pairs) {      // LDS: six 8-byte reads at per-ray offsets (one address computation each) instead of selects
         const char *nb = (const char *)sc.nodes + ((size_t)(uint32_t)tr.cur << 6);
-        nx = fma2(*(const f2 *)(nb + tr.sel[0]), id.x, noid.x); fx = fma2(*(const f2 *)(nb + (tr.sel[0] ^ 8u)), id.x, noid.x);
-        ny = fma2(*(const f2 *)(nb + tr.sel[1]), id.y, noid.y); fy = fma2(*(const f2 *)(nb + (tr.sel[1] ^ 8u)), id.y, noid.y);
-        nz = fma2(*(const f2 *)(nb + tr.sel[2]), id.z, noid.z); fz = fma2(*(const f2 *)(nb + (tr.sel[2] ^ 8u)), id.z, noid.z);
+        nx = fma2<kPkNodes>(*(const f2 *)(nb + tr.sel[0]), id.x, noid.x); fx = fma2<kPkNodes>(*(const f2 *)(nb + (tr.sel[0] ^ 8u)), id.x, noid.x);
+        ny = fma2<kPkNodes>(*(const f2 *)(nb + tr.sel[1]), id.y, noid.y); fy = fma2<kPkNodes>(*(const f2 *)(nb + (tr.sel[1] ^ 8u)), id.y, noid.y);
+        nz = fma2<kPkNodes>(*(const f2 *)(nb + tr.sel[2]), id.z, noid.z); fz = fma2<kPkNodes>(*(const f2 *)(nb + (tr.sel[2] ^ 8u)), id.z, noid.z);
         const f2 cc = *(const f2 *)(nb + 48);
         c0 = (int32_t)fbits(cc.x); c1 = (int32_t)fbits(cc.y);
     } else {
         const Node &n = sc.nodes[tr.cur];
         const q4 X = n.q[0], Y = n.q[1], Z = n.q[2], C = n.q[3];
         const bool sx = id.x < 0.0f, sy = id.y < 0.0f, sz = id.z < 0.0f;
-        nx = fma2(sx ? f2{ X.z, X.w } : f2{ X.x, X.y }, id.x, noid.x); fx = fma2(sx ? f2{ X.x, X.y } : f2{ X.z, X.w }, id.x, noid.x);
-        ny = fma2(sy ? f2{ Y.z, Y.w } : f2{ Y.x, Y.y }, id.y, noid.y); fy = fma2(sy ? f2{ Y.x, Y.y } : f2{ Y.z, Y.w }, id.y, noid.y);
-        nz = fma2(sz ? f2{ Z.z, Z.w } : f2{ Z.x, Z.y }, id.z, noid.z); fz = fma2(sz ? f2{ Z.x, Z.y } : f2{ Z.z, Z.w }, id.z, noid.z);
+        nx = fma2<kPkNodes>(sx ? f2{ X.z, X.w } : f2{ X.x, X.y }, id.x, noid.x); fx = fma2<kPkNodes>(sx ? f2{ X.x, X.y } : f2{ X.z, X.w }, id.x, noid.x);
+        ny = fma2<kPkNodes>(sy ? f2{ Y.z, Y.w } : f2{ Y.x, Y.y }, id.y, noid.y); fy = fma2<kPkNodes>(sy ? f2{ Y.x, Y.y } : f2{ Y.z, Y.w }, id.y, noid.y);
+        nz = fma2<kPkNodes>(sz ? f2{ Z.z, Z.w } : f2{ Z.x, Z.y }, id.z, noid.z); fz = fma2<kPkNodes>(sz ? f2{ Z.x, Z.y } : f2{ Z.z, Z.w }, id.z, noid.z);
         c0 = (int32_t)fbits(C.x); c1 = (int32_t)fbits(C.y);
     }
     const float tn0 = fmaxf(fmaxf(nx.x, ny.x), fmaxf(nz.x, 0.0f));
@@ -655,19 +674,19 @@ MTR_HD bool trav_leaf_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hi
         const uint32_t orig_a = fbits(g4.z), orig_b = fbits(g4.w);
         const f3 o = ray.o(tr), d = ray.d(tr);
         // pvec = cross(d, e2)
-        const f2 pvx = fma2(e2z, d.y, neg2(mul2(e2y, d.z))), pvy = fma2(e2x, d.z, neg2(mul2(e2z, d.x))), pvz = fma2(e2y, d.x, neg2(mul2(e2x, d.y)));
-        const f2 det = fma2(e1x, pvx, fma2(e1y, pvy, mul2(e1z, pvz)));                 // dot(e1, pvec)
+        const f2 pvx = fma2<kPkLeaf>(e2z, d.y, neg2(mul2<kPkLeaf>(e2y, d.z))), pvy = fma2<kPkLeaf>(e2x, d.z, neg2(mul2<kPkLeaf>(e2z, d.x))), pvz = fma2<kPkLeaf>(e2y, d.x, neg2(mul2<kPkLeaf>(e2x, d.y)));
+        const f2 det = fma2<kPkLeaf>(e1x, pvx, fma2<kPkLeaf>(e1y, pvy, mul2<kPkLeaf>(e1z, pvz)));                 // dot(e1, pvec)
         const f2 inv_det{ 1.0f / det.x, 1.0f / det.y };
-        const f2 tvx = rsub2(o.x, p0x), tvy = rsub2(o.y, p0y), tvz = rsub2(o.z, p0z);  // tvec = o - p0
-        const f2 u = mul2(fma2(tvx, pvx, fma2(tvy, pvy, mul2(tvz, pvz))), inv_det);    // dot(tvec, pvec) * inv_det
+        const f2 tvx = rsub2<kPkLeaf>(o.x, p0x), tvy = rsub2<kPkLeaf>(o.y, p0y), tvz = rsub2<kPkLeaf>(o.z, p0z);  // tvec = o - p0
+        const f2 u = mul2<kPkLeaf>(fma2<kPkLeaf>(tvx, pvx, fma2<kPkLeaf>(tvy, pvy, mul2<kPkLeaf>(tvz, pvz))), inv_det);    // dot(tvec, pvec) * inv_det
         // qvec = cross(tvec, e1)
-        const f2 qx = fma2(tvy, e1z, neg2(mul2(tvz, e1y))), qy = fma2(tvz, e1x, neg2(mul2(tvx, e1z))), qz = fma2(tvx, e1y, neg2(mul2(tvy, e1x)));
-        const f2 v = mul2(fma2(qx, d.x, fma2(qy, d.y, mul2(qz, d.z))), inv_det);       // dot(d, qvec) * inv_det
-        const f2 t = mul2(fma2(e2x, qx, fma2(e2y, qy, mul2(e2z, qz))), inv_det);       // dot(e2, qvec) * inv_det
+        const f2 qx = fma2<kPkLeaf>(tvy, e1z, neg2(mul2<kPkLeaf>(tvz, e1y))), qy = fma2<kPkLeaf>(tvz, e1x, neg2(mul2<kPkLeaf>(tvx, e1z))), qz = fma2<kPkLeaf>(tvx, e1y, neg2(mul2<kPkLeaf>(tvy, e1x)));
+        const f2 v = mul2<kPkLeaf>(fma2<kPkLeaf>(qx, d.x, fma2<kPkLeaf>(qy, d.y, mul2<kPkLeaf>(qz, d.z))), inv_det);       // dot(d, qvec) * inv_det
+        const f2 t = mul2<kPkLeaf>(fma2<kPkLeaf>(e2x, qx, fma2<kPkLeaf>(e2y, qy, mul2<kPkLeaf>(e2z, qz))), inv_det);       // dot(e2, qvec) * inv_det
         // hit iff u, v, w = 1 - (u + v) >= -kEdgeEps (mitsuba's `u <= 1` follows from the other three) and 0 <= t <= tmax.  ONE
         // constant: with a second one (1 + eps for `u + v <= 1 + eps`) the scalar registers of k_fused overflowed — 177 more
         // v_readlane in the persistent loop, 65.3 -> 67.9 ms on config 2; this form has the instruction count of the plain test.
-        const f2 w = rsub2(1.0f, add2(u, v));
+        const f2 w = rsub2<kPkLeaf>(1.0f, add2<kPkLeaf>(u, v));
         {
             const bool hit = (u.x >= -kEdgeEps) && (v.x >= -kEdgeEps) && (w.x >= -kEdgeEps) && (t.x >= 0.0f) && (t.x <= ray.tmax(tr));
             const bool closer = (t.x < tr.h.t) | ((t.x == tr.h.t) & (orig_a < tr.best_orig));      // bitwise: no branches for three compares
@@ -813,14 +832,14 @@ MTR_HD uint32_t wide_node_test(Trav &tr, const void *nodes, Stack &st)
             const char *pb = nb + 48u * j;
             f2 nx, fx, ny, fy, nz, fz;
             if (OFFS) {
-                nx = fma2(*(const f2 *)(pb + sel0), id.x, noid.x); fx = fma2(*(const f2 *)(pb + (sel0 ^ 8u)), id.x, noid.x);
-                ny = fma2(*(const f2 *)(pb + sel1), id.y, noid.y); fy = fma2(*(const f2 *)(pb + (sel1 ^ 8u)), id.y, noid.y);
-                nz = fma2(*(const f2 *)(pb + sel2), id.z, noid.z); fz = fma2(*(const f2 *)(pb + (sel2 ^ 8u)), id.z, noid.z);
+                nx = fma2<kPkNodes>(*(const f2 *)(pb + sel0), id.x, noid.x); fx = fma2<kPkNodes>(*(const f2 *)(pb + (sel0 ^ 8u)), id.x, noid.x);
+                ny = fma2<kPkNodes>(*(const f2 *)(pb + sel1), id.y, noid.y); fy = fma2<kPkNodes>(*(const f2 *)(pb + (sel1 ^ 8u)), id.y, noid.y);
+                nz = fma2<kPkNodes>(*(const f2 *)(pb + sel2), id.z, noid.z); fz = fma2<kPkNodes>(*(const f2 *)(pb + (sel2 ^ 8u)), id.z, noid.z);
             } else {
                 const q4 X = *(const q4 *)pb, Y = *(const q4 *)(pb + 16), Z = *(const q4 *)(pb + 32);
-                nx = fma2(sx ? f2{ X.z, X.w } : f2{ X.x, X.y }, id.x, noid.x); fx = fma2(sx ? f2{ X.x, X.y } : f2{ X.z, X.w }, id.x, noid.x);
-                ny = fma2(sy ? f2{ Y.z, Y.w } : f2{ Y.x, Y.y }, id.y, noid.y); fy = fma2(sy ? f2{ Y.x, Y.y } : f2{ Y.z, Y.w }, id.y, noid.y);
-                nz = fma2(sz ? f2{ Z.z, Z.w } : f2{ Z.x, Z.y }, id.z, noid.z); fz = fma2(sz ? f2{ Z.x, Z.y } : f2{ Z.z, Z.w }, id.z, noid.z);
+                nx = fma2<kPkNodes>(sx ? f2{ X.z, X.w } : f2{ X.x, X.y }, id.x, noid.x); fx = fma2<kPkNodes>(sx ? f2{ X.x, X.y } : f2{ X.z, X.w }, id.x, noid.x);
+                ny = fma2<kPkNodes>(sy ? f2{ Y.z, Y.w } : f2{ Y.x, Y.y }, id.y, noid.y); fy = fma2<kPkNodes>(sy ? f2{ Y.x, Y.y } : f2{ Y.z, Y.w }, id.y, noid.y);
+                nz = fma2<kPkNodes>(sz ? f2{ Z.z, Z.w } : f2{ Z.x, Z.y }, id.z, noid.z); fz = fma2<kPkNodes>(sz ? f2{ Z.x, Z.y } : f2{ Z.z, Z.w }, id.z, noid.z);
             }
             const float tn0 = fmaxf(fmaxf(nx.x, ny.x), fmaxf(nz.x, 0.0f));
             const float tf0 = fminf(fminf(fx.x, fy.x), fminf(fz.x, tb));
@@ -888,9 +907,9 @@ MTR_HD void qwide_node_step(Trav &tr, const QNode4 *nodes, Stack &st)
 #pragma unroll
 #endif
     for (uint32_t c = 0; c < 4u; c += 2u) {
-        const f2 nx = fma2(f2{ qbyte(nxw, c), qbyte(nxw, c + 1u) }, kx, bx), fx = fma2(f2{ qbyte(fxw, c), qbyte(fxw, c + 1u) }, kx, bx);
-        const f2 ny = fma2(f2{ qbyte(nyw, c), qbyte(nyw, c + 1u) }, ky, by), fy = fma2(f2{ qbyte(fyw, c), qbyte(fyw, c + 1u) }, ky, by);
-        const f2 nz = fma2(f2{ qbyte(nzw, c), qbyte(nzw, c + 1u) }, kz, bz), fz = fma2(f2{ qbyte(fzw, c), qbyte(fzw, c + 1u) }, kz, bz);
+        const f2 nx = fma2<kPkNodes>(f2{ qbyte(nxw, c), qbyte(nxw, c + 1u) }, kx, bx), fx = fma2<kPkNodes>(f2{ qbyte(fxw, c), qbyte(fxw, c + 1u) }, kx, bx);
+        const f2 ny = fma2<kPkNodes>(f2{ qbyte(nyw, c), qbyte(nyw, c + 1u) }, ky, by), fy = fma2<kPkNodes>(f2{ qbyte(fyw, c), qbyte(fyw, c + 1u) }, ky, by);
+        const f2 nz = fma2<kPkNodes>(f2{ qbyte(nzw, c), qbyte(nzw, c + 1u) }, kz, bz), fz = fma2<kPkNodes>(f2{ qbyte(fzw, c), qbyte(fzw, c + 1u) }, kz, bz);
         const float tn0 = fmaxf(fmaxf(nx.x, ny.x), fmaxf(nz.x, 0.0f));
         const float tf0 = fminf(fminf(fx.x, fy.x), fminf(fz.x, tb));
         const float tn1 = fmaxf(fmaxf(nx.y, ny.y), fmaxf(nz.y, 0.0f));
@@ -952,9 +971,9 @@ MTR_HD void q8_node_step(Trav &tr, const QNode8 *nodes, Stack &st)
 #pragma unroll
 #endif
         for (uint32_t c = 0; c < 4u; c += 2u) {
-            const f2 nx = fma2(f2{ qbyte(nxw, c), qbyte(nxw, c + 1u) }, kx, bx), fx = fma2(f2{ qbyte(fxw, c), qbyte(fxw, c + 1u) }, kx, bx);
-            const f2 ny = fma2(f2{ qbyte(nyw, c), qbyte(nyw, c + 1u) }, ky, by), fy = fma2(f2{ qbyte(fyw, c), qbyte(fyw, c + 1u) }, ky, by);
-            const f2 nz = fma2(f2{ qbyte(nzw, c), qbyte(nzw, c + 1u) }, kz, bz), fz = fma2(f2{ qbyte(fzw, c), qbyte(fzw, c + 1u) }, kz, bz);
+            const f2 nx = fma2<kPkNodes>(f2{ qbyte(nxw, c), qbyte(nxw, c + 1u) }, kx, bx), fx = fma2<kPkNodes>(f2{ qbyte(fxw, c), qbyte(fxw, c + 1u) }, kx, bx);
+            const f2 ny = fma2<kPkNodes>(f2{ qbyte(nyw, c), qbyte(nyw, c + 1u) }, ky, by), fy = fma2<kPkNodes>(f2{ qbyte(fyw, c), qbyte(fyw, c + 1u) }, ky, by);
+            const f2 nz = fma2<kPkNodes>(f2{ qbyte(nzw, c), qbyte(nzw, c + 1u) }, kz, bz), fz = fma2<kPkNodes>(f2{ qbyte(fzw, c), qbyte(fzw, c + 1u) }, kz, bz);
             const float tn0 = fmaxf(fmaxf(nx.x, ny.x), fmaxf(nz.x, 0.0f));
             const float tf0 = fminf(fminf(fx.x, fy.x), fminf(fz.x, tb));
             const float tn1 = fmaxf(fmaxf(nx.y, ny.y), fmaxf(nz.y, 0.0f));
@@ -1085,9 +1104,9 @@ __device__ __forceinline__ void flat_slab_pair(const f3 id, const f3 noid, const
                                                const char *root, const bool p0, const bool p1, uint32_t &qm, uint32_t &key1, uint32_t &key2)
 {
     const char *pb = root + 48u * J;
-    const f2 nx = fma2(*(const f2 *)(pb + sel0), id.x, noid.x), fx = fma2(*(const f2 *)(pb + (sel0 ^ 8u)), id.x, noid.x);
-    const f2 ny = fma2(*(const f2 *)(pb + sel1), id.y, noid.y), fy = fma2(*(const f2 *)(pb + (sel1 ^ 8u)), id.y, noid.y);
-    const f2 nz = fma2(*(const f2 *)(pb + sel2), id.z, noid.z), fz = fma2(*(const f2 *)(pb + (sel2 ^ 8u)), id.z, noid.z);
+    const f2 nx = fma2<kPkSlabs>(*(const f2 *)(pb + sel0), id.x, noid.x), fx = fma2<kPkSlabs>(*(const f2 *)(pb + (sel0 ^ 8u)), id.x, noid.x);
+    const f2 ny = fma2<kPkSlabs>(*(const f2 *)(pb + sel1), id.y, noid.y), fy = fma2<kPkSlabs>(*(const f2 *)(pb + (sel1 ^ 8u)), id.y, noid.y);
+    const f2 nz = fma2<kPkSlabs>(*(const f2 *)(pb + sel2), id.z, noid.z), fz = fma2<kPkSlabs>(*(const f2 *)(pb + (sel2 ^ 8u)), id.z, noid.z);
     const float tn0 = fmaxf(fmaxf(nx.x, ny.x), fmaxf(nz.x, 0.0f));
     const float tf0 = fminf(fminf(fx.x, fy.x), fminf(fz.x, tb));
     const float tn1 = fmaxf(fmaxf(nx.y, ny.y), fmaxf(nz.y, 0.0f));

@@ -16,14 +16,15 @@ cd "$src/mitransient_amd/csrc"
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -munsafe-fp-atomics -Wno-unused-function"
 KFLAGS=$(sed -n 's/^KFLAGS *= *//p' Makefile)      # the flags THAT tree's Makefile gives mtr_kernels.hip alone (none before round 8)
 if [[ " $* " == *" -DMTR_ONLY_C2 "* ]]; then
-  h=$(cat mtr_api.hip mtr_wavefront.hip mtr_splat.hip mtr_bvh.cpp mtr_scene_host.cpp *.h ../../include/mitransient_amd.h | sha256sum | cut -c1-16)
+  others=$(sed -n 's/^SRCS *= *//p' Makefile | tr ' ' '\n' | grep -v '^mtr_kernels.hip$')      # every other source of THAT tree's library
+  h=$(cat $others *.h ../../include/mitransient_amd.h | sha256sum | cut -c1-16)
   od="$root/ab/obj/$h"; mkdir -p "$od"
-  for f in mtr_api.hip mtr_wavefront.hip mtr_splat.hip mtr_bvh.cpp mtr_scene_host.cpp; do
+  for f in $others; do
     [ -f "$od/$f.o" ] || /opt/rocm/bin/hipcc $FL -c $f -o "$od/$f.o" &
   done
   /opt/rocm/bin/hipcc $FL $KFLAGS "$@" -c mtr_kernels.hip -o "$od/kernels_$name.o" &
   wait
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o "$root/ab/libs/lib_$name.so" "$od"/mtr_api.hip.o "$od"/mtr_wavefront.hip.o "$od"/mtr_splat.hip.o "$od"/mtr_bvh.cpp.o "$od"/mtr_scene_host.cpp.o "$od/kernels_$name.o"
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o "$root/ab/libs/lib_$name.so" $(for f in $others; do echo "$od/$f.o"; done) "$od/kernels_$name.o"
 else
   # every source, by that tree's own Makefile (its per-file flags included), with the extra flags on all of them — in a copy,
   # so that the working tree keeps its own library and objects

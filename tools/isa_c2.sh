@@ -29,7 +29,7 @@ def st(a, b):
     seg = ins[a:b + 1]
     c = collections.Counter(x.split()[0] for x in seg)
     return dict(n=len(seg), valu=sum(v for k, v in c.items() if k.startswith('v_')), salu=sum(v for k, v in c.items() if k.startswith('s_')),
-                mov=c['v_mov_b32_e32'] + c['v_mov_b64_e32'], lane=c['v_readlane_b32'] + c['v_writelane_b32'], ds=sum(v for k, v in c.items() if k.startswith('ds_')),
+                pk=sum(v for k, v in c.items() if k.startswith('v_pk_') and k.endswith('_f32')), mov=c['v_mov_b32_e32'] + c['v_mov_b64_e32'], lane=c['v_readlane_b32'] + c['v_writelane_b32'], ds=sum(v for k, v in c.items() if k.startswith('ds_')),
                 scratch=sum(v for k, v in c.items() if k.startswith('scratch_')), div=c['v_div_fixup_f32'], nop=c['s_nop'])
 print('kernel', st(0, len(ins) - 1))
 big = sorted(loops, key=lambda ab: ab[0] - ab[1])

@@ -11,5 +11,5 @@ for l in sys.stdin:
     m = re.search(r'remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)', l)
     if m and cur: rows[cur][m.group(1).strip()] = int(m.group(2))
 for k, r in rows.items():
-    if re.search('$pat', k): print('%-70s vgpr %3d spill %3d scratch %4d occ %d' % (k[:70], r.get('VGPRs', -1), r.get('VGPRs Spill', -1), r.get('ScratchSize', -1), r.get('Occupancy', -1)))
+    if re.search('$pat', k): print('%-70s vgpr %3d sspill %3d spill %3d scratch %4d occ %d' % (k[:70], r.get('VGPRs', -1), r.get('SGPRs Spill', -1), r.get('VGPRs Spill', -1), r.get('ScratchSize', -1), r.get('Occupancy', -1)))
 "
