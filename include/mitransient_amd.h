@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 21
+#define MTR_ABI_VERSION 22
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -93,9 +93,16 @@ typedef struct mtr_texture {
     const float *rgb;      /* host, height * width * 3 floats, row 0 first (v = 0), already linear (sRGB decoded by the caller) */
 } mtr_texture;
 
-/* ---- emitters: `area` emitter attached to a `rectangle` (analytic sampling) or to a triangle mesh ---- */
+/* ---- emitters: `area` emitter attached to a `rectangle` (analytic sampling) or to a triangle mesh; (ABI 22) mitsuba's `point`
+ *      and `spot` emitters, which no ray can hit and no triangle references ---- */
+enum { MTR_EMITTER_AREA = 0,   /* `area` / `angulararea` on a shape: every caller up to ABI 21 */
+       MTR_EMITTER_POINT = 1,  /* mitsuba `point`: position = center, intensity = radiance; sample_direction has ds.pdf = 1, ds.delta,
+                                  weight intensity / dist^2 */
+       MTR_EMITTER_SPOT = 2    /* mitsuba `spot`: the same from center along `axis`, times the falloff of the angle to the axis: 1 inside
+                                  beam_width, linear in the angle down to 0 at cutoff_angle (cutoff / cos_cutoff / cos_beam /
+                                  inv_transition below, the curve `angulararea` copied from it) */ };
 typedef struct mtr_emitter {
-    float center[3];      /* rectangle: to_world * (0,0,0)                       */
+    float center[3];      /* rectangle: to_world * (0,0,0); point / spot: the position */
     float du[3];          /* rectangle: to_world * (1,0,0) - center  (half edge) */
     float dv[3];          /* rectangle: to_world * (0,1,0) - center  (half edge) */
     float radiance[3];
@@ -111,6 +118,10 @@ typedef struct mtr_emitter {
     float cos_cutoff;      /* cos(cutoff) (:68)                                                                                     */
     float cos_beam;        /* cos(deg2rad(beam_width)) (:60-61, :69), beam_width defaults to cutoff_angle                          */
     float inv_transition;  /* 1 / (cutoff - beam), +inf when they are equal (:62-66)                                               */
+    /* ABI 22 */
+    uint32_t kind;         /* MTR_EMITTER_*.  Point and spot: du, dv, is_mesh, first_tri, n_tris, flip_normals and angular are ignored,
+                              `radiance` holds the intensity; a spot's four falloff constants are read (finite, cutoff >= beam; inv_transition +inf when equal)     */
+    float axis[3];         /* spot: the unit world-space direction of the beam (to_world's +z axis); to_world is rigid                   */
 } mtr_emitter;
 
 /* ---- sensor: `perspective` (utils.py:92-105 of the reference) ----------- */
@@ -379,7 +390,7 @@ int  mtr_scene_bvh_info(const mtr_scene *, uint32_t *n_nodes, uint32_t *max_dept
 /* Which specialised kernels the scene's tables select (for tests and tools; no counterpart in the reference, whose tracing
  * JIT specialises on the scene implicitly): MTR_TRAIT_* bits. */
 #define MTR_TRAIT_DIFFUSE          1u   /* every material plain one-sided diffuse */
-#define MTR_TRAIT_ONE_RECT_EMITTER 2u   /* exactly one emitter, an analytic rectangle (`area`, not `angulararea`) */
+#define MTR_TRAIT_ONE_RECT_EMITTER 2u   /* exactly one emitter, an analytic rectangle (`area`, not `angulararea`, no point / spot emitter) */
 #define MTR_TRAIT_LEAF_PAIR        4u   /* no leaf of the LDS-staged tree beyond one triangle pair */
 #define MTR_TRAIT_FLAT_TOP         8u   /* top level = rectangles, triangle leaves and box nodes: the fused kernel does not walk a tree */
 #define MTR_TRAIT_FLAT_LEAVES     16u   /* ... and there are triangle leaves among them */
@@ -455,7 +466,8 @@ int  mtr_render_plan(mtr_scene *, const mtr_render_params *, uint32_t *mode_out,
  *   grad_materials : device f32 (n_materials, 3)  d loss / d reflectance of every plain `diffuse` material (constant `a`;
  *                                                  other materials receive 0, and so do bitmap-textured ones: their
  *                                                  gradient is per texel, mtr_render_grad_tex)
- *   grad_emitters  : device f32 (n_emitters, 3)   d loss / d radiance of every `area` / `angulararea` emitter
+ *   grad_emitters  : device f32 (n_emitters, 3)   d loss / d radiance of every `area` / `angulararea` emitter, (ABI 22) d loss /
+ *                                                 d intensity of every `point` / `spot` emitter
  * with the upstream gradients of the DEVELOPED tensors
  *   grad_steady_hw3     : device f32 (H, W, 3)
  *   grad_transient_hwt3 : device f32 (H, W, T, 3)

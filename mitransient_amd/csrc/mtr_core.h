@@ -353,10 +353,14 @@ constexpr uint32_t kLeafQuadBit = 0x40000000u;      // in the leaf code ~ref = (
 struct alignas(16) TriShade { q4 h[MTR_TSHADE_QUADS]; };
 constexpr uint32_t kShadeQuadBit = 0x80000000u;
 constexpr uint32_t kShadeSmoothBit = 0x40000000u;
+// kind of an Emitter.  The delta emitters (mitsuba `point` / `spot`, ABI 22; kind >= kEmPoint) are positions no ray can hit: only
+// shade_hit's emitter sampling meets them, and never in a kTrOneRectEmitter kernel
+constexpr uint32_t kEmRect = 0u, kEmMesh = 1u, kEmPoint = 2u, kEmSpot = 3u;
 struct alignas(16) Emitter {                       // 96 B
-    float center[3], du[3], dv[3], n[3], radiance[3], inv_area;       // rectangle: analytic sampling
-    uint32_t is_mesh, first_tri, n_tris, angular;                      // mesh: triangle range (ORIGINAL indices); angular: `angulararea`
-    float cutoff, cos_cutoff, cos_beam, inv_transition;                // angulararea.py:55-72 (mtr_emitter), read only when `angular`
+    float center[3], du[3], dv[3], n[3], radiance[3], inv_area;       // rectangle: analytic sampling; point / spot: center = position,
+                                                                       // n = the spot's axis, radiance = intensity
+    uint32_t kind, first_tri, n_tris, angular;                         // mesh: triangle range (ORIGINAL indices); angular: `angulararea`
+    float cutoff, cos_cutoff, cos_beam, inv_transition;                // angulararea.py:55-72 (mtr_emitter), read only when `angular` or kEmSpot
 };
 // angulararea.py:74-82 _fallof_curve of a unit direction whose cosine to the emitter's shading normal is c
 MTR_HD float angular_falloff(const Emitter &E, float c)
@@ -2140,8 +2144,12 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
         }
         pick(ei);
         const Emitter &E = sc.ems[ei];
+        // a delta emitter [mitsuba3: point.cpp / spot.cpp sample_direction]: ds.p = the position, ds.pdf = 1, ds.delta, the weight
+        // intensity * falloff / dist^2 — no random number, and mis_em = 1 below (transientpath.py:210)
+        const bool delta = !kOneRect && E.kind >= kEmPoint;
         f3 ep, en;
-        if (!kOneRect && E.is_mesh) {
+        if (delta) { ep = ld3(E.center); en = ld3(E.n); }                    // (en: the spot's axis; a point's is never read)
+        else if (!kOneRect && E.kind == kEmMesh) {
             mesh_sample_position(sc.samp_tris, sc.face_cdf, sc.face_pmf, E.first_tri, E.n_tris, u1, u2, ep, en, ROUGH ? sc.samp_vn : nullptr);
         } else {
             float a = fmaf(u1, 2.0f, -1.0f), b = fmaf(u2, 2.0f, -1.0f);
@@ -2156,13 +2164,15 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
         float dp = dot(dd, en), adp = fabsf(dp);
         float x = dist2 / adp;
         float pdf_dir = E.inv_area * ((fabsf(x) <= 3.402823466e+38f) ? x : 0.0f);
+        if (delta) pdf_dir = dist2 > 0.0f ? 1.0f : 0.0f;
         // angulararea sample_direction (angulararea.py:107-128): falloff of normalize(Frame3f(ds.n).to_local(-ds.d)), the term dropped where it is
         // zero, and radiance * (falloff * inv_dist^2) / ds.pdf — the reference's extra 1 / dist^2 on top of the solid-angle pdf
-        const bool ang = !kOneRect && E.angular != 0u;
+        // spot: the same curve of normalize(to_world^-1 (-ds.d)).z — to_world is rigid, so the frame about its +z axis gives that z
+        const bool ang = !kOneRect && (E.angular != 0u || E.kind == kEmSpot);
         const float fall = ang ? angular_falloff(E, unit_z(to_local_about(en, -dd))) : 1.0f;
-        if ((dp < 0.0f) & (pdf_dir != 0.0f) & (fall > 0.0f)) {
+        if (((dp < 0.0f) | delta) & (pdf_dir != 0.0f) & (fall > 0.0f)) {
             f3 emw;
-            if (ang) { const float inv_dist = 1.0f / dist; emw = (ld3(E.radiance) * (fall * (inv_dist * inv_dist))) / pdf_dir; }
+            if (ang || delta) { const float inv_dist = 1.0f / dist; emw = (ld3(E.radiance) * (fall * (inv_dist * inv_dist))) / pdf_dir; }
             else emw = ld3(E.radiance) / pdf_dir;
             float pdf = pdf_dir;
             if (n_emitters > 1) { pdf = pdf_dir * rc.inv_n_emitters; emw = emw * rc.n_emitters_f; }
@@ -2181,14 +2191,14 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
                     f3 bval; float bpdf;
                     pd.alb = material_albedo<ROUGH>(sc, mat, h); pd.has_alb = 1u;
                     rough_eval_pdf(mat, pd.alb, wi_e, wo, bval, bpdf);
-                    float mis_em = mis_weight(pdf, bpdf);
+                    float mis_em = delta ? 1.0f : mis_weight(pdf, bpdf);
                     pd.Lr = mk(((p.beta.x * mis_em) * bval.x) * emw.x, ((p.beta.y * mis_em) * bval.y) * emw.y,
                                ((p.beta.z * mis_em) * bval.z) * emw.z);
                     pd.opl = p.dist + dist * eta;
                 } else
                 if (wi_e.z > 0.0f && wo.z > 0.0f) {
                     float bpdf = kInvPi * wo.z;
-                    float mis_em = mis_weight(pdf, bpdf);
+                    float mis_em = delta ? 1.0f : mis_weight(pdf, bpdf);
                     const f3 alb = material_albedo<ROUGH>(sc, mat, h);
                     if (ROUGH) { pd.alb = alb; pd.has_alb = 1u; }
                     pd.Lr = mk(((p.beta.x * mis_em) * ((alb.x * kInvPi) * wo.z)) * emw.x,

@@ -434,7 +434,7 @@ MTR_HD bool polar_bounce(PolarPath &pp, const SceneView &sc, const Film &film, c
             }
             const Emitter &E = sc.ems[ei];
             f3 ep, en;
-            if (E.is_mesh) mesh_sample_position(sc.samp_tris, sc.face_cdf, sc.face_pmf, E.first_tri, E.n_tris, u1, u2, ep, en, sc.samp_vn);
+            if (E.kind != kEmRect) mesh_sample_position(sc.samp_tris, sc.face_cdf, sc.face_pmf, E.first_tri, E.n_tris, u1, u2, ep, en, sc.samp_vn);
             else {
                 const float a = fmaf(u1, 2.0f, -1.0f), b = fmaf(u2, 2.0f, -1.0f);
                 ep = mk(fmaf(E.du[0], a, fmaf(E.dv[0], b, E.center[0])), fmaf(E.du[1], a, fmaf(E.dv[1], b, E.center[1])),

@@ -303,9 +303,29 @@ const char *derive_scene(const mtr_scene_desc &d, HostScene &s)
     for (uint32_t i = 0; i < d.n_emitters; ++i) {
         const mtr_emitter &e = d.emitters[i];
         Emitter &E = s.ems[i];
-        E.is_mesh = e.is_mesh; E.first_tri = e.first_tri; E.n_tris = e.n_tris;
+        E.kind = e.is_mesh ? kEmMesh : kEmRect; E.first_tri = e.first_tri; E.n_tris = e.n_tris;
         E.angular = e.angular ? 1u : 0u;
         E.cutoff = E.cos_cutoff = E.cos_beam = E.inv_transition = 0.0f;
+        if (e.kind != MTR_EMITTER_AREA) {      // (ABI 22) a delta emitter: the position, the intensity, and a spot's axis and falloff constants
+            if (e.kind != MTR_EMITTER_POINT && e.kind != MTR_EMITTER_SPOT) return "emitter: unknown kind";
+            if (d.nlos) return "NLOS: point / spot emitters are not supported next to the projector";
+            const bool spot = e.kind == MTR_EMITTER_SPOT;
+            E.kind = spot ? kEmSpot : kEmPoint; E.first_tri = E.n_tris = 0u; E.angular = 0u; E.inv_area = 0.0f;
+            for (int k = 0; k < 3; ++k) {
+                if (!std::isfinite(e.center[k]) || !std::isfinite(e.radiance[k])) return "point / spot emitter: position and intensity must be finite";
+                E.center[k] = e.center[k]; E.du[k] = E.dv[k] = E.n[k] = 0.0f; E.radiance[k] = e.radiance[k];
+            }
+            if (spot) {
+                const float len2 = e.axis[0] * e.axis[0] + e.axis[1] * e.axis[1] + e.axis[2] * e.axis[2];
+                // (cutoff == beam: inv_transition is +inf, as in an angulararea record; every other constant is finite)
+                if (!std::isfinite(e.cutoff) || !std::isfinite(e.cos_cutoff) || !std::isfinite(e.cos_beam) || std::isnan(e.inv_transition) ||
+                    !(e.cutoff > 0.0f) || !(e.cos_beam >= e.cos_cutoff) || !(e.inv_transition > 0.0f) || !(fabsf(len2 - 1.0f) <= 1e-4f))
+                    return "spot emitter: bad axis / cutoff / beam";
+                for (int k = 0; k < 3; ++k) E.n[k] = e.axis[k];
+                E.cutoff = e.cutoff; E.cos_cutoff = e.cos_cutoff; E.cos_beam = e.cos_beam; E.inv_transition = e.inv_transition;
+            }
+            continue;
+        }
         if (e.angular) {      // angulararea.py:55-72: the caller derives the constants; cutoff >= beam (the assert of :71)
             if (!(e.cutoff >= 0.0f) || !(e.cos_beam >= e.cos_cutoff) || !(e.inv_transition > 0.0f)) return "angular emitter: bad cutoff / beam";
             E.cutoff = e.cutoff; E.cos_cutoff = e.cos_cutoff; E.cos_beam = e.cos_beam; E.inv_transition = e.inv_transition;
@@ -377,7 +397,7 @@ void classify_scene(const mtr_scene_desc &d, HostScene &hs)
         if (!polar_bsdf_supported(d.materials[i].type)) hs.polar_ok = false;
         if (bsdf_is_lobe(d.materials[i].type)) lobes = true;
     }
-    for (const Emitter &e : hs.ems) if (e.angular) hs.polar_ok = false;
+    for (const Emitter &e : hs.ems) if (e.angular || e.kind >= kEmPoint) hs.polar_ok = false;
     hs.needs_ext = lobes || !hs.vnormals.empty() || !hs.texels.empty();      // smooth-shaded triangles, bitmap textures: the extended shading code as well
     // scene traits (mtr_core.h): facts about the tables that let the kernels drop shading code no hit can reach
     hs.traits = 0u;
@@ -386,7 +406,7 @@ void classify_scene(const mtr_scene_desc &d, HostScene &hs)
         for (uint32_t i = 0; i < d.n_materials; ++i)
             if (d.materials[i].type != MTR_BSDF_DIFFUSE || (d.materials[i].flags & MTR_MAT_TWOSIDED)) diffuse_only = false;
         if (diffuse_only) hs.traits |= kTrDiffuse;
-        if (d.n_emitters == 1 && !hs.ems[0].is_mesh && !hs.ems[0].angular) hs.traits |= kTrOneRectEmitter;     // (its kernels have no falloff code)
+        if (d.n_emitters == 1 && hs.ems[0].kind == kEmRect && !hs.ems[0].angular) hs.traits |= kTrOneRectEmitter;     // (its kernels have no falloff code, and no delta emitter)
         bool leaf_pairs = hs.has_wide;
         for (const WNode &n : hs.wnodes)
             for (uint32_t k = 0; k < n.count; ++k) {

@@ -463,7 +463,7 @@ class TransientADIntegrator:
             if k not in keys:
                 raise ValueError(f"{k}: not a differentiable parameter (the constant reflectance of a diffuse BSDF, the texels of a "
                                  f"bitmap that only diffuse reflectances use, the constant radiance of an area / angulararea "
-                                 f"emitter and the constant irradiance of a NLOS scene's projector are; the constant specular "
+                                 f"emitter, the constant intensity of a point / spot emitter and the constant irradiance of a NLOS scene's projector are; the constant specular "
                                  f"tints of conductors and dielectrics with transient_path only: {sorted(keys)})")
             if keys[k][0] == "tint" and int(np.prod(tuple(val.shape))) not in (1, 3):
                 raise ValueError(f"{k}: a tint of 1 or 3 elements, got shape {tuple(val.shape)}")

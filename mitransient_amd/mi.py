@@ -146,7 +146,7 @@ class Scene:
         self.texture_values_ = {}              # {(file, raw): (H, W, 3) f32} texels set through a `.data` key
         from . import integrators as _i, films as _f  # noqa: F401  (registers the plugins)
         from .shapes import Shape
-        from .emitters import Projector
+        from .emitters import Projector, _DeltaEmitter, make_delta_emitter
         if d.get("type") != "scene":
             raise ValueError("load_dict(): expected a dictionary with 'type': 'scene'")
         self.base_dir = base_dir
@@ -154,6 +154,7 @@ class Scene:
         # so that mitransient.nlos.focus_emitter_* edits made later are seen by the render
         self.shape_objs_, self.emitters_, self.sensors_ = {}, [], []
         self.emitter_names_ = []               # the projectors' keys in the scene dictionary (<emitter id>.irradiance.value)
+        self.lights_ = {}                      # point / spot emitters by key: the live objects (their records are flattened from them)
         flat = {}
         for k, v in d.items():
             if isinstance(v, Shape):
@@ -167,6 +168,12 @@ class Scene:
                 e.dict_ = v
                 self.emitters_.append(e)
                 self.emitter_names_.append(k)
+            elif isinstance(v, _DeltaEmitter):                                 # loaded on its own: mi.load_dict(point / spot)
+                self.lights_[k] = v
+                flat[k] = v.dict_
+            elif isinstance(v, dict) and v.get("type") in ("point", "spot"):
+                self.lights_[k] = make_delta_emitter(v)
+                flat[k] = v
             elif isinstance(v, dict) and v.get("type") in _SHAPE_TYPES:
                 self.shape_objs_[k] = _load_shape(v)
                 flat[k] = v
@@ -187,6 +194,9 @@ class Scene:
                 for v in flat.values() if isinstance(v, dict) for e in v.values()):
             # transientnlospath.py:256-260: the NLOS integrator takes exactly one emitter, a projector
             raise ValueError("transient_nlos_path: an angulararea emitter cannot light a NLOS scene (one projector is required)")
+        if isinstance(self.integrator_, TransientNLOSPath) and self.lights_:
+            raise ValueError(f"transient_nlos_path: a {next(iter(self.lights_.values())).KIND} emitter cannot light a NLOS scene "
+                             "(one projector is required)")
         for k, v in flat.items():
             if isinstance(v, dict) and v.get("type") == "perspective":
                 self.sensors_.append(_make_sensor(v))
@@ -212,7 +222,7 @@ class Scene:
         return self.sensors_
 
     def emitters(self):
-        return self.emitters_
+        return self.emitters_ + list(self.lights_.values())
 
     def shapes(self):
         return list(self.shape_objs_.values())
@@ -225,15 +235,16 @@ class Scene:
         if isinstance(sensor, int):
             sensor = self.sensors_[sensor]
         key = id(sensor)
-        ver = getattr(sensor, "version_", 0)
-        if key in self._data and self._data_ver.get(key, 0) != ver:      # the camera moved (params["sensor.to_world"]): re-flatten
+        # (... or a point / spot emitter did: its position, to_world or angles)
+        ver = (getattr(sensor, "version_", 0), sum(getattr(l, "version_", 0) for l in self.lights_.values()))
+        if key in self._data and self._data_ver.get(key, (0, 0)) != ver:      # the camera moved (params["sensor.to_world"]): re-flatten
             del self._data[key]
             self._drop_handles(key)
         self._data_ver[key] = ver
         if key not in self._data:
             self._data[key] = flatten_scene(self.dict_, sensor.film(), sensor.dict_, self.base_dir,
                                             self.relay_names_.get(key), self.approximate_materials, self.geometry_,
-                                            own_materials=self.own_materials_)
+                                            own_materials=self.own_materials_, lights=self.lights_)
             self._apply_params(self._data[key])
         sd = self._data[key]
         sd.film = film_desc_from(sensor.film())
@@ -424,6 +435,8 @@ class Scene:
             return
         self.ensure_own_records([key])
         self.param_values_[key] = [float(np.float32(x)) for x in v]
+        if key.endswith(".intensity.value") and key[:-len(".intensity.value")] in self.lights_:
+            self.lights_[key[:-len(".intensity.value")]].intensity = np.asarray(self.param_values_[key], np.float64)      # the live object shows it
         lib = _cabi.load_library()
         for skey, sd in self._data.items():
             self._apply_params(sd)
@@ -498,6 +511,9 @@ def load_dict(d: Dict[str, Any], base_dir: str = ".", approximate_materials: boo
         e = Projector(Properties("projector", d))
         e.dict_ = d
         return e
+    if t in ("point", "spot"):
+        from .emitters import make_delta_emitter
+        return make_delta_emitter(d)
     from . import integrators as _i, films as _f  # noqa: F401  (registers the plugins)
     if str(t).endswith("_film"):                                # stand-alone plugins, as 1-simple-nlos-scenes.ipynb builds them
         return plugins.create_film(t, Properties(t, d))
@@ -627,6 +643,9 @@ def traverse(obj):
         for k, v in obj.texture_param_keys().items():
             objs[k] = (obj, k)
             scene_keys[k] = v
+        # ... <emitter id>.position (point), <emitter id>.to_world / .cutoff_angle / .beam_width (spot): update() re-flattens the scene
+        for name, light in obj.lights_.items():
+            targets.append((f"{name}.", light))
         for i, s in enumerate(obj.sensors()):
             targets.append((f"sensor{'' if i == 0 else i}.film.", s.film()))
             if isinstance(s, PerspectiveSensor):

@@ -137,6 +137,8 @@ def _ior(v, default):
 
 
 _EMITTER_TYPES = ("area", "angulararea", "point", "spot", "projector", "constant", "envmap", "directional")
+_DELTA_EMITTER_TYPES = ("point", "spot")               # top-level emitters of transient_path (emitters.py), in the emitter table
+_UNSUPPORTED_EMITTER_TYPES = ("constant", "envmap", "directional")
 
 
 def fresnel_diffuse_reflectance(eta):
@@ -161,6 +163,7 @@ class _SceneBuilder:
         self.cur_shape = None
         self.shape_mat: Dict[str, int] = {}
         self.shape_em: Dict[str, int] = {}
+        self.light_em: Dict[str, int] = {}                    # top-level point / spot emitters: name -> emitter index
         self.base_dir = base_dir
         self.approx = approximate_materials
         self.mesh_cache: Dict[str, np.ndarray] = {}
@@ -446,7 +449,7 @@ class _SceneBuilder:
         if em is not None:
             et = em.get("type")
             if et not in ("area", "angulararea"):
-                raise ValueError(f"failed to instantiate unknown plugin of type \"{et}\" (supported emitters: area, angulararea)")
+                raise ValueError(f"failed to instantiate unknown plugin of type \"{et}\" (supported emitters on a shape: area, angulararea)")
             e = _cabi.mtr_emitter()
             rad = _color3(em.get("radiance", 1.0), f"{et}.radiance")
             if et == "angulararea":
@@ -494,6 +497,18 @@ class _SceneBuilder:
             for k in range(3):
                 sh.center[k], sh.du[k], sh.dv[k] = np.float32(c[k]), np.float32(du[k]), np.float32(dv[k])
         self.shapes.append(sh)
+
+
+def _add_delta_emitter(b: "_SceneBuilder", name: str, v: Dict[str, Any], obj=None):
+    """a top-level `point` / `spot` dictionary -> its record of the emitter table, at the place the dictionary's order gives it.
+    ``obj``: the live PointLight / SpotLight (mi.Scene keeps one per emitter, so that traversed parameters are seen); without
+    one the record is that of the dictionary's own object.  (mi.Scene refuses these emitters on the NLOS tier, derive_scene too.)"""
+    from .emitters import make_delta_emitter
+    light = obj if obj is not None else make_delta_emitter(v)
+    e = _cabi.mtr_emitter()
+    light.fill_record(e)
+    b.emitters.append(e)
+    b.light_em[name] = len(b.emitters) - 1
 
 
 def _angular_constants(e, em: Dict[str, Any]):
@@ -884,6 +899,9 @@ def load_geometry(path: str) -> Dict[str, Any]:
     if layout[1] == 60 and esize > 60:           # written with ABI <= 8: mtr_emitter grew by an appended field (flip_normals) only
         em_bytes = np.pad(em_bytes.reshape(-1, 60), ((0, 0), (0, esize - 60))).reshape(-1)
         layout[1] = esize
+    if layout[1] == 84 and esize > 84:           # written with ABI <= 21: mtr_emitter grew by appended fields (kind, axis) only
+        em_bytes = np.pad(em_bytes.reshape(-1, 84), ((0, 0), (0, esize - 84))).reshape(-1)
+        layout[1] = esize
     if layout != [msize, C.sizeof(_cabi.mtr_emitter), C.sizeof(_cabi.mtr_shape)]:
         raise ValueError(f"{path}: material / emitter record sizes {list(z['layout'])} do not match this C-ABI; "
                          "regenerate with tests/golden/make_golden.py")
@@ -930,13 +948,17 @@ def _check_polarized(b, film, sd):
     for e in b.emitters:
         if e.angular:
             raise ValueError(f"{v}: the angulararea emitter is not available with polarization (supported emitters: area)")
+        if e.kind != _cabi.MTR_EMITTER_AREA:
+            raise ValueError(f"{v}: the {'point' if e.kind == _cabi.MTR_EMITTER_POINT else 'spot'} emitter is not available "
+                             f"with polarization (supported emitters: area)")
     if sd.textures:
         raise ValueError(f"{v}: bitmap textures are not available with polarization")
 
 
 def flatten_scene(d: Dict[str, Any], film, sensor_dict: Dict[str, Any], base_dir: str = ".",
                   relay_shape_name: Optional[str] = None, approximate_materials: bool = False,
-                  geometry: Optional[Dict[str, Any]] = None, own_materials: bool = False) -> SceneData:
+                  geometry: Optional[Dict[str, Any]] = None, own_materials: bool = False,
+                  lights: Optional[Dict[str, Any]] = None) -> SceneData:
     b = _SceneBuilder(d, base_dir, approximate_materials, own_materials)
     for name, v in d.items():
         if not isinstance(v, dict):
@@ -944,6 +966,10 @@ def flatten_scene(d: Dict[str, Any], film, sensor_dict: Dict[str, Any], base_dir
         t = v.get("type")
         if t in ("rectangle", "cube", "obj", "ply", "sphere", "disk", "cylinder"):
             b.add_shape(name, v)
+        elif t in _DELTA_EMITTER_TYPES:            # emitters enter the table in the dictionary's order, shapes' and top-level ones alike
+            _add_delta_emitter(b, name, v, (lights or {}).get(name))
+        elif t in _UNSUPPORTED_EMITTER_TYPES:
+            raise ValueError(f"failed to instantiate unknown plugin of type \"{t}\" (supported emitters: area, angulararea, point, spot)")
     sd = SceneData()
     if geometry is not None:                     # pre-flattened geometry (load_geometry); the dictionary has no shapes
         if b.tri_verts:
@@ -1070,6 +1096,9 @@ def param_locations(d) -> Dict[str, tuple]:
         em = [v for v in sd.values() if isinstance(v, dict) and v.get("type") in ("area", "angulararea")]
         if em and _constant_rgb(em[0].get("radiance", 1.0)) is not None:
             out[f"{name}.emitter.radiance.value"] = ("emitter", ("shape", name), _constant_rgb(em[0].get("radiance", 1.0)))
+    for name, v in d.items():                      # top-level point / spot emitters: the constant intensity
+        if isinstance(v, dict) and v.get("type") in _DELTA_EMITTER_TYPES and _constant_rgb(v.get("intensity", 1.0)) is not None:
+            out[f"{name}.intensity.value"] = ("emitter", ("light", name), _constant_rgb(v.get("intensity", 1.0)))
     for rid in refs:                               # BSDFs declared at the top level and referenced by id
         v = d.get(rid)
         k = _bsdf_key(v, f"{rid}.") if isinstance(v, dict) else None
@@ -1243,8 +1272,9 @@ def differentiable_keys(d, b) -> Dict[str, tuple]:
     keys = {}
     for k, (kind, (how, name), _) in param_locations(d).items():
         if kind == "emitter":
-            if name in b.shape_em:
-                keys[k] = ("emitter", b.shape_em[name])
+            table = b.light_em if how == "light" else b.shape_em
+            if name in table:
+                keys[k] = ("emitter", table[name])
         elif how == "ref":
             if ("ref", name) in b.mat_cache:
                 keys[k] = ("material", b.mat_cache[("ref", name)])
