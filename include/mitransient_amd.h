@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 22
+#define MTR_ABI_VERSION 23
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -93,14 +93,19 @@ typedef struct mtr_texture {
     const float *rgb;      /* host, height * width * 3 floats, row 0 first (v = 0), already linear (sRGB decoded by the caller) */
 } mtr_texture;
 
-/* ---- emitters: `area` emitter attached to a `rectangle` (analytic sampling) or to a triangle mesh; (ABI 22) mitsuba's `point`
- *      and `spot` emitters, which no ray can hit and no triangle references ---- */
+/* ---- emitters: `area` emitter attached to a `rectangle` (analytic sampling), to a triangle mesh or (ABI 23) to an analytic
+ *      `sphere`; (ABI 22) mitsuba's `point` and `spot` emitters, which no ray can hit and no triangle references ---- */
 enum { MTR_EMITTER_AREA = 0,   /* `area` / `angulararea` on a shape: every caller up to ABI 21 */
        MTR_EMITTER_POINT = 1,  /* mitsuba `point`: position = center, intensity = radiance; sample_direction has ds.pdf = 1, ds.delta,
                                   weight intensity / dist^2 */
        MTR_EMITTER_SPOT = 2    /* mitsuba `spot`: the same from center along `axis`, times the falloff of the angle to the axis: 1 inside
                                   beam_width, linear in the angle down to 0 at cutoff_angle (cutoff / cos_cutoff / cos_beam /
-                                  inv_transition below, the curve `angulararea` copied from it) */ };
+                                  inv_transition below, the curve `angulararea` copied from it) */,
+       MTR_EMITTER_SPHERE = 3  /* (ABI 23) an `area` emitter on an analytic sphere (mtr_shape.kind = MTR_SHAPE_SPHERE, whose one carrier
+                                  triangle references it): center, radius, flip_normals (the emitting side is the inside).
+                                  mitsuba's Sphere::sample_direction [upstream-unverified]: from outside the cone the sphere subtends
+                                  is sampled, pdf 1 / (2 pi (1 - cos theta_max)); from inside the surface uniformly, pdf
+                                  dist^2 / (4 pi r^2 |cos|).  du, dv, is_mesh, first_tri, n_tris and angular are ignored */ };
 typedef struct mtr_emitter {
     float center[3];      /* rectangle: to_world * (0,0,0); point / spot: the position */
     float du[3];          /* rectangle: to_world * (1,0,0) - center  (half edge) */
@@ -122,6 +127,8 @@ typedef struct mtr_emitter {
     uint32_t kind;         /* MTR_EMITTER_*.  Point and spot: du, dv, is_mesh, first_tri, n_tris, flip_normals and angular are ignored,
                               `radiance` holds the intensity; a spot's four falloff constants are read (finite, cutoff >= beam; inv_transition +inf when equal)     */
     float axis[3];         /* spot: the unit world-space direction of the beam (to_world's +z axis); to_world is rigid                   */
+    /* ABI 23 */
+    float radius;          /* MTR_EMITTER_SPHERE: the world radius (> 0), about `center`                                                */
 } mtr_emitter;
 
 /* ---- sensor: `perspective` (utils.py:92-105 of the reference) ----------- */
@@ -168,6 +175,9 @@ enum { MTR_NLOS_LASER_SAMPLING = 1u,          /* nlos_laser_sampling            
        MTR_NLOS_FORCE_EQUAL_GRIDS = 64u       /* force_equal_illumination_scanning (Exhaustive)   */ };
 
 enum { MTR_RECT_ANALYTIC = 1u, MTR_RECT_FLIP_NORMALS = 2u };     /* mtr_shape.is_rectangle */
+enum { MTR_SHAPE_DEFAULT = 0u,          /* mtr_shape.kind (ABI 23): what is_rectangle says — an analytic rectangle or a triangle mesh */
+       MTR_SHAPE_SPHERE = 1u,           /* mitsuba's analytic `sphere` */
+       MTR_SHAPE_FLIP_NORMALS = 0x100u  /* ... with `flip_normals` (a bit beside the kind): both normals are -normalize(p - center) */ };
 typedef struct mtr_shape {          /* one scene shape = a contiguous triangle range */
     uint32_t first_tri, n_tris;
     uint32_t is_rectangle;          /* analytic `rectangle`: the shape is ONE primitive — mitsuba's Rectangle::ray_intersect
@@ -181,6 +191,15 @@ typedef struct mtr_shape {          /* one scene shape = a contiguous triangle r
     uint32_t has_to_world;          /* meshes: to_world below is the shape's object -> world transform (cube: of [-1,1]^3; obj / ply:
                                        of the file's coordinates).  Only an acceleration hint (oriented bounds); 0 = unknown */
     float    to_world[12];          /* row-major 3 x 4 affine */
+    /* ABI 23 */
+    uint32_t kind;                  /* MTR_SHAPE_*.  MTR_SHAPE_SPHERE: the shape is ONE primitive — mitsuba's Sphere [upstream-unverified]:
+                                       |o + t d - center|^2 = radius^2, roots from the point of closest approach; no hit for a ray wholly
+                                       inside; the far root when the origin is inside; n = normalize(p - center), p re-projected to
+                                       center + radius n; dp_du = to_world (-local.y, local.x, 0), coordinate_system(n) at the poles; no uv.
+                                       is_rectangle is 0, `center` and `radius` are the world sphere, to_world (has_to_world = 1; a rotation
+                                       times a uniform scale, then the translation) orients the tangent.  It owns ONE carrier triangle, which
+                                       only carries material / emitter / index: it is never intersected and never sampled. */
+    float    radius;                /* sphere only: |to_world (1,0,0) - center| > 0 */
 } mtr_shape;
 
 #define MTR_NLOS_NO_RELAY 0xffffffffu

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MITRANSIENT_AMD_LIB") or os.path.join(_HERE, "csrc", "libmitransient_amd.so")   # env override: kernel A/B experiments
 
-MTR_ABI_VERSION = 22
+MTR_ABI_VERSION = 23
 MTR_TRAIT_DIFFUSE, MTR_TRAIT_ONE_RECT_EMITTER, MTR_TRAIT_LEAF_PAIR, MTR_TRAIT_FLAT_TOP, MTR_TRAIT_FLAT_LEAVES, MTR_TRAIT_NO_LOBES, MTR_TRAIT_GREY = 1, 2, 4, 8, 16, 32, 64      # mtr_scene_traits
 MTR_SPLAT_FILM_ZERO = 0x100      # mtr_splat_add: OR into `variant` when the film is all-zero on entry
 
@@ -30,7 +30,8 @@ MTR_FLAG_DEVELOPED_ROWS = 64
 MTR_FLAG_POLARIZED = 256           # (ABI 14) the *_mono_polarized variants: Stokes film (H, W, T, 4), S0 steady
 MTR_MODE_AUTO, MTR_MODE_FUSED, MTR_MODE_WAVEFRONT = 0, 1, 2
 MTR_RECT_ANALYTIC, MTR_RECT_FLIP_NORMALS = 1, 2
-MTR_EMITTER_AREA, MTR_EMITTER_POINT, MTR_EMITTER_SPOT = 0, 1, 2      # mtr_emitter.kind (ABI 22)
+MTR_EMITTER_AREA, MTR_EMITTER_POINT, MTR_EMITTER_SPOT, MTR_EMITTER_SPHERE = 0, 1, 2, 3      # mtr_emitter.kind (ABI 22; the sphere light: ABI 23)
+MTR_SHAPE_DEFAULT, MTR_SHAPE_SPHERE, MTR_SHAPE_FLIP_NORMALS = 0, 1, 0x100      # mtr_shape.kind (ABI 23)
 MTR_GRAD_TEX_NONE, MTR_GRAD_TEX_SLAB, MTR_GRAD_TEX_GLOBAL = 0, 1, 2     # mtr_render_grad_tex_tier
 MTR_FWD_ROWS, MTR_FWD_GLOBAL = 1, 2     # mtr_render_fwd_tier
 
@@ -56,7 +57,8 @@ class mtr_emitter(C.Structure):
                 ("flip_normals", C.c_uint32),
                 ("angular", C.c_uint32), ("cutoff", C.c_float), ("cos_cutoff", C.c_float), ("cos_beam", C.c_float),
                 ("inv_transition", C.c_float),
-                ("kind", C.c_uint32), ("axis", _f3)]              # (ABI 22) MTR_EMITTER_*; the beam direction of a spot
+                ("kind", C.c_uint32), ("axis", _f3),              # (ABI 22) MTR_EMITTER_*; the beam direction of a spot
+                ("radius", C.c_float)]                            # (ABI 23) MTR_EMITTER_SPHERE
 
 
 class mtr_camera(C.Structure):
@@ -83,7 +85,8 @@ MTR_NLOS_HG_INCLUDES_WALL, MTR_NLOS_ACCOUNT_FIRST_LAST, MTR_NLOS_DISCARD_DIRECT 
 
 class mtr_shape(C.Structure):
     _fields_ = [("first_tri", C.c_uint32), ("n_tris", C.c_uint32), ("is_rectangle", C.c_uint32),
-                ("center", _f3), ("du", _f3), ("dv", _f3), ("has_to_world", C.c_uint32), ("to_world", C.c_float * 12)]
+                ("center", _f3), ("du", _f3), ("dv", _f3), ("has_to_world", C.c_uint32), ("to_world", C.c_float * 12),
+                ("kind", C.c_uint32), ("radius", C.c_float)]      # (ABI 23) MTR_SHAPE_*; a sphere's world radius
 
 
 class mtr_nlos_desc(C.Structure):

@@ -73,6 +73,7 @@ struct mtr_scene {
     uint32_t n_emitters_area = 0;
     bool polar_ok = false;                                   // every material and emitter has a polarized form (mtr_polar.h)
     bool grey_scene = false;                                 // kTrGrey without the NLOS laser (mtr_scene_set_nlos decides with it)
+    bool has_sphere = false;                                 // an analytic sphere: never kTrGrey (mtr_core.h tr_spheres)
     SceneDev dev{};
     Camera cam{};
     Film film{};
@@ -224,7 +225,7 @@ int mtr_scene_create(mtr_ctx *c, const mtr_scene_desc *d, mtr_scene **out)
     s->dev.n_nodes = (uint32_t)hs.nodes.size(); s->dev.n_slots = (uint32_t)hs.tshade.size();
     s->dev.n_mats = d->n_materials; s->dev.n_ems = d->n_emitters;
     // what the kernels are chosen by: decided over the host tables (mtr_scene_host.cpp classify_scene)
-    s->polar_ok = hs.polar_ok; s->grey_scene = hs.grey_scene;
+    s->polar_ok = hs.polar_ok; s->grey_scene = hs.grey_scene; s->has_sphere = hs.has_sphere;
     s->dev.has_rough = hs.needs_ext ? 1u : 0u; s->dev.traits = hs.traits; s->dev.flat = hs.flat;
     s->dev.bvh_depth = hs.bvh_depth; s->n_leaves = hs.n_leaves;
     s->dev.wide_levels = hs.wide_levels; s->dev.wide4_levels = hs.wide4_levels; s->dev.wide8q_levels = hs.wide8q_levels;
@@ -356,7 +357,7 @@ int mtr_scene_set_colors(mtr_scene *s, const float *material_a, const float *emi
     if (!mats.empty()) HIP_TRY(c, hipMemcpy((void *)s->dev.mats, mats.data(), mats.size() * sizeof(mtr_material), hipMemcpyHostToDevice));
     if (!ems.empty()) HIP_TRY(c, hipMemcpy((void *)s->dev.ems, ems.data(), ems.size() * sizeof(Emitter), hipMemcpyHostToDevice));
     // kTrGrey is the only trait that depends on colours: decided again over the new tables
-    const bool grey = colours_are_grey(mats.data(), (uint32_t)mats.size(), ems.data(), (uint32_t)ems.size(), s->dev.texels != nullptr);
+    const bool grey = scene_is_grey(s->has_sphere, mats.data(), (uint32_t)mats.size(), ems.data(), (uint32_t)ems.size(), s->dev.texels != nullptr);
     s->grey_scene = grey;
     s->dev.traits = grey ? (s->dev.traits | kTrGrey) : (s->dev.traits & ~kTrGrey);
     return MTR_OK;
@@ -382,7 +383,7 @@ int mtr_scene_set_tints(mtr_scene *s, const float *material_c, const float *mate
             if (slots[2u * i + 1u] >= 0) mats[i].c2[k] = material_c2[3 * i + k];
         }
     if (!mats.empty()) HIP_TRY(c, hipMemcpy((void *)s->dev.mats, mats.data(), mats.size() * sizeof(mtr_material), hipMemcpyHostToDevice));
-    const bool grey = colours_are_grey(mats.data(), (uint32_t)mats.size(), ems.data(), (uint32_t)ems.size(), s->dev.texels != nullptr);
+    const bool grey = scene_is_grey(s->has_sphere, mats.data(), (uint32_t)mats.size(), ems.data(), (uint32_t)ems.size(), s->dev.texels != nullptr);
     s->grey_scene = grey;
     s->dev.traits = grey ? (s->dev.traits | kTrGrey) : (s->dev.traits & ~kTrGrey);
     return MTR_OK;
@@ -544,6 +545,7 @@ static int wf_render(mtr_scene *s, const mtr_render_params *p, float *t4, float 
     const bool polar = (p->flags & MTR_FLAG_POLARIZED) != 0u;
     WfConfig cfg{};
     if (!wf_plan(s->dev, cfg)) return fail(c, MTR_ERR_UNSUPPORTED, "wavefront: BVH too deep for the LDS stack");
+    cfg.spheres = s->has_sphere;
     const uint32_t n_pixels = p->pixel_end - p->pixel_begin;
     const uint32_t spp_chunk = p->spp_end - p->spp_begin;
     // tile = P pixels x S samples (2^25 slots); segment = G whole pixels (about 4096 slots: with the persistent

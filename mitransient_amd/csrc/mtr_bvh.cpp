@@ -34,7 +34,7 @@ struct Box {
     }
 };
 
-enum : uint8_t { kItemTri = 0, kItemQuad = 1, kItemObject = 2 };
+enum : uint8_t { kItemTri = 0, kItemQuad = 1, kItemObject = 2, kItemSphere = 3 };
 struct Item { uint32_t first_tri, n_tris; uint8_t type; int32_t object; };
 
 // world box of a triangle / its image under a 3 x 4 affine map (f64, then outward-rounded to f32 by the caller's padding)
@@ -99,7 +99,7 @@ int tri_in_box(const float *v, const Box &b, double (*out)[3])
     return n;
 }
 
-struct Tmp { Box box; int left = -1, right = -1; uint32_t first = 0, count = 0; bool quad = false; int32_t object = -1; };
+struct Tmp { Box box; int left = -1, right = -1; uint32_t first = 0, count = 0; bool quad = false, sphere = false; int32_t object = -1; };
 
 struct Shared {                       // what every (sub-)builder appends to
     const float *verts = nullptr;
@@ -171,7 +171,7 @@ struct Builder {
         for (uint32_t r : refs) {
             const Item &it = items[r];
             t.box.grow(wbox[r]);
-            t.quad = it.type == kItemQuad;
+            t.quad = it.type == kItemQuad; t.sphere = it.type == kItemSphere;
             for (uint32_t k = 0; k < it.n_tris; ++k) {
                 bool dup = false;                         // two pieces of one triangle in the same leaf: one test
                 for (size_t j = t.first; j < S.leaf_tris.size(); ++j) dup = dup || S.leaf_tris[j] == it.first_tri + k;
@@ -576,6 +576,7 @@ void build_bvh(const float *verts, uint32_t n, const BvhPrims *prims, BvhBuild &
         const uint8_t kind = prims && prims->kind ? prims->kind[i] : 0;
         const int32_t obj = prims && prims->object ? prims->object[i] : -1;
         if (kind == 1 && i + 1 < n) { B.add_item(Item{ i, 2u, kItemQuad, -1 }, nullptr); i += 2; continue; }
+        if (kind == 3) { B.add_item(Item{ i, 1u, kItemSphere, -1 }, nullptr); ++i; continue; }      // one primitive, alone in its leaf like a rectangle
         if (obj >= 0) {
             uint32_t j = i;
             while (j < n && prims->object[j] == obj) ++j;
@@ -629,6 +630,7 @@ void build_bvh(const float *verts, uint32_t n, const BvhPrims *prims, BvhBuild &
         if (t.count & 1u) out.order.push_back(kPadSlot);
         uint32_t code = (first << 2) | (t.count - 1u);
         if (t.quad) code |= kLeafQuadBit;
+        if (t.sphere) code |= kLeafSphereBit;
         return (int32_t)~code;
     };
     struct Entry { int tmp; int packet; uint32_t depth; };

@@ -10,7 +10,8 @@ constexpr uint32_t kPadSlot = 0xffffffffu;
 
 // optional per-triangle annotations of the build (all arrays may be null)
 struct BvhPrims {
-    const uint8_t *kind = nullptr;      // [n] 0 mesh triangle, 1 first / 2 second carrier triangle of an analytic rectangle
+    const uint8_t *kind = nullptr;      // [n] 0 mesh triangle, 1 first / 2 second carrier triangle of an analytic rectangle,
+                                        // 3 the carrier triangle of an analytic sphere (its box is the sphere's: the caller's vertices say so)
     const int32_t *object = nullptr;    // [n] index of the OBJECT (small mesh shape with a known transform) the triangle belongs to, or -1
     const float *object_xf = nullptr;   // [n_objects][12] world -> object affine map (rows R | T)
 };

@@ -340,6 +340,12 @@ MTR_HD uint32_t hit_list_key(uint32_t type)
 }
 constexpr uint32_t kQuadMark = 0xffffffffu;
 constexpr uint32_t kLeafQuadBit = 0x40000000u;      // in the leaf code ~ref = (first_slot << 2) | (count - 1)
+// A `sphere` (analytic primitive, ABI 23) owns one pair of slots too — its one carrier triangle and the pad — and is alone in its
+// leaf, whose reference carries kLeafSphereBit (bit 29: the first slot of such a scene stays below 2^27).  Its record:
+//   g[0] = (c.x, c.y, c.z, r)  g[4] = (-, -, orig, kQuadMark)
+// A hit on it reports (u, v) = the octahedral code of the unit vector from the centre to the hit point (sphere_dir_encode): the
+// surface interaction is rebuilt from the hit record alone, as for every other primitive.
+constexpr uint32_t kLeafSphereBit = 0x20000000u;
 // shading record per slot (5 quads): flat frame, the three vertices (hit point = barycentric blend), material | emitter
 //   h[0] = (n.x, n.y, n.z, s.x)  h[1] = (s.y, s.z, t.x, t.y)  h[2] = (t.z, p1.x, p1.y, p1.z)  h[3] = (p2.x, p2.y, p2.z, p0.x)
 //   h[4] = (p0.y, p0.z, mat_em, orig)      mat_em: material index | (emitter index + 1) << 16
@@ -353,12 +359,18 @@ constexpr uint32_t kLeafQuadBit = 0x40000000u;      // in the leaf code ~ref = (
 struct alignas(16) TriShade { q4 h[MTR_TSHADE_QUADS]; };
 constexpr uint32_t kShadeQuadBit = 0x80000000u;
 constexpr uint32_t kShadeSmoothBit = 0x40000000u;
-// kind of an Emitter.  The delta emitters (mitsuba `point` / `spot`, ABI 22; kind >= kEmPoint) are positions no ray can hit: only
-// shade_hit's emitter sampling meets them, and never in a kTrOneRectEmitter kernel
-constexpr uint32_t kEmRect = 0u, kEmMesh = 1u, kEmPoint = 2u, kEmSpot = 3u;
+// sphere slots (ABI 23; orig |= kShadeSphereBit, original indices stay below 2^29): the world images of the object's x and y axes,
+// unit length, from which dp_du = to_world (-local.y, local.x, 0) is built at the hit, the sign of the normals, radius and centre
+//   h[0] = (ex.x, ex.y, ex.z, ey.x)  h[1] = (ey.y, ey.z, flip ? -1 : 1, -)  h[3] = (r, -, -, c.x)  h[4] = (c.y, c.z, mat_em, orig)
+constexpr uint32_t kShadeSphereBit = 0x20000000u;
+// kind of an Emitter.  The delta emitters (mitsuba `point` / `spot`, ABI 22) are positions no ray can hit: only
+// shade_hit's emitter sampling meets them, and never in a kTrOneRectEmitter kernel.  kEmSphere (ABI 23): an `area` emitter on an analytic
+// sphere — never in a kTrOneRectEmitter kernel either
+constexpr uint32_t kEmRect = 0u, kEmMesh = 1u, kEmPoint = 2u, kEmSpot = 3u, kEmSphere = 4u;
 struct alignas(16) Emitter {                       // 96 B
     float center[3], du[3], dv[3], n[3], radiance[3], inv_area;       // rectangle: analytic sampling; point / spot: center = position,
-                                                                       // n = the spot's axis, radiance = intensity
+                                                                       // n = the spot's axis, radiance = intensity; sphere: center,
+                                                                       // du[0] = radius, n[0] = -1 under flip_normals else 1, inv_area = 1 / (4 pi r^2)
     uint32_t kind, first_tri, n_tris, angular;                         // mesh: triangle range (ORIGINAL indices); angular: `angulararea`
     float cutoff, cos_cutoff, cos_beam, inv_transition;                // angulararea.py:55-72 (mtr_emitter), read only when `angular` or kEmSpot
 };
@@ -378,6 +390,43 @@ MTR_HD f3 to_local_about(f3 n, f3 v)
     const f3 s = mk((sign_neg(n.z) ? -((n.x * n.x) * a) : (n.x * n.x) * a) + 1.0f, sign_neg(n.z) ? -b : b, sign_neg(n.z) ? n.x : -n.x);
     const f3 t = mk(b, fmaf(n.y, n.y * a, sign), -n.y);
     return mk(dot(v, s), dot(v, t), dot(v, n));
+}
+// [mitsuba3: coordinate_system(n)] (Duff et al. 2017): the two tangents themselves — a sphere's frame at its poles, the frame about
+// the axis of the cone a sphere light subtends
+MTR_HD void coordinate_system(f3 n, f3 &s, f3 &t)
+{
+    const float sign = copysignf(1.0f, n.z), a = -(1.0f / (sign + n.z)), b = (n.x * n.y) * a;
+    s = mk((sign_neg(n.z) ? -((n.x * n.x) * a) : (n.x * n.x) * a) + 1.0f, sign_neg(n.z) ? -b : b, sign_neg(n.z) ? n.x : -n.x);
+    t = mk(b, fmaf(n.y, n.y * a, sign), -n.y);
+}
+// sin and cos of 2 pi u, u in [0, 1]: reduced to a multiple of pi/2 and the quarter-range polynomials, as phasor_term does
+MTR_HD void sincos_2pi(float u, float &s, float &c)
+{
+    const float phase = 6.283185307179586f * u;
+    const float k = floorf(fmaf(phase, 0.6366197723675814f, 0.5f));
+    float r = fmaf(-k, 1.5707962512969971f, phase);
+    r = fmaf(-k, 7.549789415861596e-08f, r);
+    float sq, cq;
+    sincos_quarter(r, sq, cq);
+    const uint32_t q = (uint32_t)(int32_t)k & 3u;
+    s = (q == 0u) ? sq : (q == 1u) ? cq : (q == 2u) ? -sq : -cq;
+    c = (q == 0u) ? cq : (q == 1u) ? -sq : (q == 2u) ? -cq : sq;
+}
+// A unit vector as two floats (the octahedral map: project onto |x| + |y| + |z| = 1, fold the lower half over the diagonals) and
+// back — what a hit on a sphere carries in (u, v).  Every component comes back to a few ulps of 1, wherever the vector points.
+MTR_HD void sphere_dir_encode(f3 n, float &u, float &v)
+{
+    const float inv = 1.0f / ((fabsf(n.x) + fabsf(n.y)) + fabsf(n.z));
+    const float px = n.x * inv, py = n.y * inv;
+    const bool low = n.z < 0.0f;
+    u = low ? copysignf(1.0f - fabsf(py), px) : px;
+    v = low ? copysignf(1.0f - fabsf(px), py) : py;
+}
+MTR_HD f3 sphere_dir_decode(float u, float v)
+{
+    const float z = (1.0f - fabsf(u)) - fabsf(v);
+    const bool low = z < 0.0f;
+    return normalize(mk(low ? copysignf(1.0f - fabsf(v), u) : u, low ? copysignf(1.0f - fabsf(u), v) : v, z));
 }
 
 struct Camera {
@@ -646,13 +695,50 @@ MTR_HD bool trav_quad_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hi
     return hit;
 }
 
+// a sphere leaf [mitsuba3: Sphere::ray_intersect_preliminary_impl, upstream-unverified]: the roots of |o + t d - c|^2 = r^2 for a
+// unit d, from the point of closest approach — t_c = dot(c - o, d), disc = r^2 - |c - (o + t_c d)|^2, roots t_c -+ sqrt(disc) — which
+// keeps a far-away ball and a ray that leaves the surface (the textbook B^2 - 4AC cancels both away).  No hit unless near <= maxt and
+// far >= 0, none for a ray wholly inside (near < 0 and far > maxt); t = the near root, or the far one when the origin is inside.
+// The vector from the centre to the hit point is d (t - t_c) - (c - o - t_c d): no difference of two large positions.
+template <class RaySrc = RayOfTrav, class Stack>
+MTR_HD bool trav_sphere_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hit, const RaySrc ray = RaySrc())
+{
+    st.count(1);
+    const uint32_t first = ((~(uint32_t)tr.cur) & ~kLeafSphereBit) >> 2;
+    const TriPair &tp = sc.tpairs[first >> 1];
+    const q4 S = tp.g[0];
+    const uint32_t orig = fbits(tp.g[4].z);
+    const f3 o = ray.o(tr), d = ray.d(tr);
+    const f3 l = mk(S.x - o.x, S.y - o.y, S.z - o.z);
+    const float tc = dot(l, d);
+    const f3 q = mk(fmaf(-d.x, tc, l.x), fmaf(-d.y, tc, l.y), fmaf(-d.z, tc, l.z));
+    const float disc = fmaf(S.w, S.w, -dot(q, q));
+    const float sq = sqrtf(disc > 0.0f ? disc : 0.0f);
+    const float near_t = tc - sq, far_t = tc + sq, maxt = ray.tmax(tr);
+    const bool in_bounds = (disc >= 0.0f) && (near_t <= maxt) && (far_t >= 0.0f) && !((near_t < 0.0f) && (far_t > maxt));
+    const float t = near_t < 0.0f ? far_t : near_t;
+    const bool hit = in_bounds;
+    const bool closer = (t < tr.h.t) | ((t == tr.h.t) & (orig < tr.best_orig));
+    const bool better = hit && (any_hit || closer);
+    if (better) {
+        const float k = t - tc;
+        const f3 n = normalize(mk(fmaf(d.x, k, -q.x), fmaf(d.y, k, -q.y), fmaf(d.z, k, -q.z)));
+        tr.h.t = t; sphere_dir_encode(n, tr.h.u, tr.h.v);
+        tr.h.prim = (int32_t)first; tr.best_orig = orig;
+    }
+    return hit;
+}
+
 // ONE_PAIR: the caller knows that no triangle leaf of the tree holds more than two triangles (scene trait kTrLeafPair): one
 // pass, no loop around it
-template <bool ONE_PAIR = false, class RaySrc = RayOfTrav, class Stack>
+// SPH: the tree may hold sphere leaves.  Never in a scene with kTrLeafPair (classify_scene): the walkers specialised on that trait —
+// and those a caller instantiates with SPH = false for another trait a sphere rules out (tr_spheres) — carry no sphere code
+template <bool ONE_PAIR = false, bool SPH = !ONE_PAIR, class RaySrc = RayOfTrav, class Stack>
 MTR_HD bool trav_leaf_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hit, const RaySrc ray = RaySrc())
 {
     const uint32_t code = ~(uint32_t)tr.cur;
     if (code & kLeafQuadBit) return trav_quad_test(tr, sc, st, any_hit, ray);
+    if constexpr (SPH) { if (code & kLeafSphereBit) return trav_sphere_test(tr, sc, st, any_hit, ray); }
     const uint32_t first = code >> 2, cnt = ONE_PAIR ? (code & 1u) + 1u : (code & 3u) + 1u;
     bool found = false;
     // Moller-Trumbore [mitsuba3: Mesh::ray_intersect_triangle]: pvec = cross(d, e2); inv_det = 1 / dot(e1, pvec);
@@ -710,10 +796,10 @@ MTR_HD bool trav_leaf_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hi
     }
     return found;
 }
-template <class Stack>
+template <bool SPH = true, class Stack>
 MTR_HD void trav_leaf_step(Trav &tr, const SceneView &sc, Stack &st, bool any_hit)
 {
-    const bool found = trav_leaf_test(tr, sc, st, any_hit);
+    const bool found = trav_leaf_test<false, SPH>(tr, sc, st, any_hit);
     if (any_hit & found) tr.cur = kTravDone;
     else tr.cur = st.empty() ? kTravDone : st.pop();
 }
@@ -870,10 +956,10 @@ MTR_HD void wide_node_step(Trav &tr, const void *nodes, Stack &st)
     const uint32_t g = wide_node_test<W, OFFS>(tr, nodes, st);
     wide_advance<W>(tr, nodes, st, g);
 }
-template <uint32_t W, bool ONE_PAIR = false, class Stack>
+template <uint32_t W, bool ONE_PAIR = false, bool SPH = !ONE_PAIR, class Stack>
 MTR_HD void wide_leaf_step(Trav &tr, const SceneView &sc, const void *nodes, Stack &st, bool any_hit)
 {
-    const bool found = trav_leaf_test<ONE_PAIR>(tr, sc, st, any_hit);
+    const bool found = trav_leaf_test<ONE_PAIR, SPH>(tr, sc, st, any_hit);
     if (any_hit & found) tr.cur = kTravDone;
     else wide_advance<W>(tr, nodes, st, tr.grp);
 }
@@ -931,10 +1017,10 @@ MTR_HD void qwide_node_step(Trav &tr, const QNode4 *nodes, Stack &st)
     }
     qwide_advance(tr, nodes, st, g);
 }
-template <class Stack>
+template <bool SPH = true, class Stack>
 MTR_HD void qwide_leaf_step(Trav &tr, const SceneView &sc, Stack &st, bool any_hit)
 {
-    const bool found = trav_leaf_test(tr, sc, st, any_hit);
+    const bool found = trav_leaf_test<false, SPH>(tr, sc, st, any_hit);
     if (any_hit & found) tr.cur = kTravDone;
     else qwide_advance(tr, sc.wnodes4, st, tr.grp);
 }
@@ -996,10 +1082,10 @@ MTR_HD void q8_node_step(Trav &tr, const QNode8 *nodes, Stack &st)
     }
     q8_advance(tr, nodes, st, g);
 }
-template <class Stack>
+template <bool SPH = true, class Stack>
 MTR_HD void q8_leaf_step(Trav &tr, const SceneView &sc, Stack &st, bool any_hit)
 {
-    const bool found = trav_leaf_test(tr, sc, st, any_hit);
+    const bool found = trav_leaf_test<false, SPH>(tr, sc, st, any_hit);
     if (any_hit & found) tr.cur = kTravDone;
     else q8_advance(tr, sc.wnodes8q, st, tr.grp);
 }
@@ -1017,7 +1103,7 @@ MTR_HD void q8_leaf_step(Trav &tr, const SceneView &sc, Stack &st, bool any_hit)
 // to a lane that was already done (ray over ds_bpermute, pairing through the empty LDS stack rows, results merged by the
 // (t, original index) rule; all parity tests green): 70.7 ms for closest-hit rays only against 68.2, and 92 ms with the
 // shadow rays included (the state alive across the shadow traversal left no registers: 30 -> 118 spilled).
-template <bool ANY_HIT, bool ONE_PAIR = false, class Stack>
+template <bool ANY_HIT, bool ONE_PAIR = false, bool SPH = !ONE_PAIR, class Stack>
 __device__ __forceinline__ void wide_walk_device(Trav &tr, const SceneView &sc, Stack &st)
 {
 #ifndef MTR_WALK_LANE_EXIT
@@ -1036,7 +1122,7 @@ __device__ __forceinline__ void wide_walk_device(Trav &tr, const SceneView &sc, 
         bool adv = false;
         if (__ballot(at_prim) != 0ull) {
             if (at_prim) {
-                const bool found = is_quad_leaf(tr.cur) ? trav_quad_test(tr, sc, st, ANY_HIT) : trav_leaf_test<ONE_PAIR>(tr, sc, st, ANY_HIT);
+                const bool found = is_quad_leaf(tr.cur) ? trav_quad_test(tr, sc, st, ANY_HIT) : trav_leaf_test<ONE_PAIR, SPH>(tr, sc, st, ANY_HIT);
                 if (ANY_HIT & found) tr.cur = kTravDone;
                 else adv = true;
             }
@@ -1059,7 +1145,7 @@ __device__ __forceinline__ void wide_walk_device(Trav &tr, const SceneView &sc, 
                 const bool found = trav_quad_test(tr, sc, st, ANY_HIT);
                 if (ANY_HIT & found) tr.cur = kTravDone;
                 else wide_advance<kWide>(tr, sc.wnodes, st, tr.grp);
-            } else if (at_prim) wide_leaf_step<kWide, ONE_PAIR>(tr, sc, sc.wnodes, st, ANY_HIT);
+            } else if (at_prim) wide_leaf_step<kWide, ONE_PAIR, SPH>(tr, sc, sc.wnodes, st, ANY_HIT);
         } else {
             wide_node_step<kWide, true>(tr, sc.wnodes, st);
         }
@@ -1222,7 +1308,7 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
                 tr.cur = *(const int32_t *)(root + N::kRefOff + 4u * k);
                 // (a rectangle or — only where the top level holds triangle leaves — a leaf of one or two pairs)
                 const bool found = (!TOP_LEAVES || is_quad_leaf(tr.cur)) ? trav_quad_test(tr, sc, st, ANY_HIT, ray)
-                                                                         : trav_leaf_test<ONE_PAIR>(tr, sc, st, ANY_HIT, ray);
+                                                                         : trav_leaf_test<ONE_PAIR, false>(tr, sc, st, ANY_HIT, ray);
                 if (ANY_HIT ? found : (it == 0u && tr.h.t < bitsf(key2 & ~7u))) qm = 0u;
             }
         }
@@ -1236,7 +1322,8 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
 // intersects leaves together)
 // FLAT: the scene has a flat top level (kTrFlatTop, FlatTop; 2: one that may hold triangle leaves, kTrFlatLeaves) — the device does not walk its
 // tree at all (flat_walk_device); a host build walks the tree, whose result is the same by construction
-template <bool ANY_HIT, bool ONE_PAIR = false, int FLAT = 0, class Stack>
+// SPH: the tree may hold sphere leaves (trav_leaf_test)
+template <bool ANY_HIT, bool ONE_PAIR = false, int FLAT = 0, bool SPH = !ONE_PAIR && FLAT == 0, class Stack>
 MTR_HD Hit traverse(const SceneView &sc, f3 o, f3 d, float tmax, Stack &st)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1251,7 +1338,7 @@ MTR_HD Hit traverse(const SceneView &sc, f3 o, f3 d, float tmax, Stack &st)
         // three kinds of steps, each run by the whole wave at once: inner nodes until no lane holds one, then one
         // rectangle test for the lanes holding a rectangle, else one triangle-leaf pass
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(MTR_NODES_FIRST)
-        wide_walk_device<ANY_HIT, ONE_PAIR>(tr, sc, st);
+        wide_walk_device<ANY_HIT, ONE_PAIR, SPH>(tr, sc, st);
 #else
         while (tr.cur != kTravDone) {
             while (tr.cur >= 0) {
@@ -1264,18 +1351,18 @@ MTR_HD Hit traverse(const SceneView &sc, f3 o, f3 d, float tmax, Stack &st)
                 const bool found = trav_quad_test(tr, sc, st, ANY_HIT);
                 if (ANY_HIT & found) tr.cur = kTravDone;
                 else wide_advance<kWide>(tr, sc.wnodes, st, tr.grp);
-            } else if (tr.cur != kTravDone) wide_leaf_step<kWide, ONE_PAIR>(tr, sc, sc.wnodes, st, ANY_HIT);
+            } else if (tr.cur != kTravDone) wide_leaf_step<kWide, ONE_PAIR, SPH>(tr, sc, sc.wnodes, st, ANY_HIT);
         }
 #endif
     } else if (sc.wnodes8q) {
         while (tr.cur != kTravDone) {
             while (tr.cur >= 0) q8_node_step(tr, sc.wnodes8q, st);
-            if (tr.cur != kTravDone) q8_leaf_step(tr, sc, st, ANY_HIT);
+            if (tr.cur != kTravDone) q8_leaf_step<SPH>(tr, sc, st, ANY_HIT);
         }
     } else if (sc.wnodes4) {
         while (tr.cur != kTravDone) {
             while (tr.cur >= 0) qwide_node_step(tr, sc.wnodes4, st);
-            if (tr.cur != kTravDone) qwide_leaf_step(tr, sc, st, ANY_HIT);
+            if (tr.cur != kTravDone) qwide_leaf_step<SPH>(tr, sc, st, ANY_HIT);
         }
     } else
     while (tr.cur != kTravDone) {
@@ -1285,7 +1372,7 @@ MTR_HD Hit traverse(const SceneView &sc, f3 o, f3 d, float tmax, Stack &st)
             ++my_nodes;
 #endif
         }
-        if (tr.cur != kTravDone) trav_leaf_step(tr, sc, st, ANY_HIT);
+        if (tr.cur != kTravDone) trav_leaf_step<SPH>(tr, sc, st, ANY_HIT);
     }
 #ifdef MTR_PROFILE_SIMT
     st.tail(my_nodes);
@@ -1839,6 +1926,13 @@ constexpr uint32_t kTrCornell = kTrDiffuse | kTrOneRectEmitter | kTrLeafPair;   
 constexpr uint32_t kTrCornellFlat = kTrCornell | kTrFlatTop;                       // ... and with the flat top level
 constexpr uint32_t kTrFlatFlags = kTrFlatTop | kTrLeafPair;                        // ... the flat top level alone (its box faces are pairs), any materials and emitters
 constexpr uint32_t kTrFlatGeneral = kTrFlatFlags | kTrFlatLeaves;                  // ... the instantiation for it: takes top levels with and without triangle leaves
+// A scene with an analytic sphere (ABI 23) never has kTrOneRectEmitter, kTrLeafPair, kTrFlatTop, kTrFlatLeaves or — the NLOS tier's
+// one-plane rows — kTrGrey (classify_scene): code specialised on one of them holds no sphere test, no sphere branch of the surface
+// interaction and no sphere light
+// kTrNoSphere: never a bit of a scene's trait word — a template argument alone, by which the wavefront kernels are instantiated a second
+// time for the scenes without a sphere (WfConfig::spheres): the staircase's trace and shade kernels are the ones they were
+constexpr uint32_t kTrNoSphere = 0x8000u;
+constexpr bool tr_spheres(uint32_t tr) { return (tr & (kTrOneRectEmitter | kTrLeafPair | kTrFlatTop | kTrFlatLeaves | kTrGrey | kTrNoSphere)) == 0u; }
 
 template <bool ROUGH = true, uint32_t TR = 0u>
 MTR_HD BsdfSample bsdf_sample(const mtr_material &m, f3 wi, float u1, float ua, float ub, f3 albedo)
@@ -1941,19 +2035,46 @@ MTR_HD f3 hit_point(q4 hc, q4 hd, q4 he, float b1, float b2)
               fmaf(he.x, b0, fmaf(hc.z, b1, hd.y * b2)),
               fmaf(he.y, b0, fmaf(hc.w, b1, hd.z * b2)));
 }
+// a sphere [mitsuba3: Sphere::compute_surface_interaction, upstream-unverified]: `dir` = normalize(p - c) as the hit carries it
+// (sphere_dir_decode); the point is re-projected, p = fmadd(dir, r, c)
+MTR_HD f3 sphere_point(q4 hd, q4 he, f3 dir) { return mk(fmaf(dir.x, hd.x, hd.w), fmaf(dir.y, hd.x, he.x), fmaf(dir.z, hd.x, he.y)); }
 // ... of a hit record alone: the vertex a path came from, rebuilt where it is needed (k_wf_shade: an emitter was hit) instead of carried
+template <bool SPH = true>
 MTR_HD f3 hit_point(const SceneView &sc, const Hit &h)
 {
     const TriShade &tsd = sc.tshade[h.prim];
+    if constexpr (SPH) { if (fbits(tsd.h[4].w) & kShadeSphereBit) return sphere_point(tsd.h[3], tsd.h[4], sphere_dir_decode(h.u, h.v)); }
     return hit_point(tsd.h[2], tsd.h[3], tsd.h[4], h.u, h.v);
 }
 
-template <bool SMOOTH = true>
+// SPH: the scene may hold spheres (tr_spheres of the caller's traits; true where a caller has none)
+template <bool SMOOTH = true, bool SPH = true>
 MTR_HD HitCtx hit_ctx(const SceneView &sc, f3 ray_d, const Hit &h)
 {
     HitCtx c;
     const TriShade &tsd = sc.tshade[h.prim];
     const q4 ha = tsd.h[0], hb = tsd.h[1], hc = tsd.h[2], hd = tsd.h[3], he = tsd.h[4];
+    if constexpr (SPH) {
+        if (fbits(he.w) & kShadeSphereBit) {
+            // geometric and shading normal are both n = +-dir; dp_du = to_world (-local.y, local.x, 0) with local = to_object p: with the
+            // unit images ex, ey of the object's x and y axes, ey dot(dir, ex) - ex dot(dir, ey) up to the (uniform) scale; the frame by
+            // initialize_sh_frame as for every other primitive, and coordinate_system(n) at the poles, where dp_du = 0
+            const f3 dir = sphere_dir_decode(h.u, h.v);
+            const f3 ex = mk(ha.x, ha.y, ha.z), ey = mk(ha.w, hb.x, hb.y);
+            const float lx = dot(dir, ex), ly = dot(dir, ey);
+            const f3 dp_du = mk(fmaf(ey.x, lx, -(ex.x * ly)), fmaf(ey.y, lx, -(ex.y * ly)), fmaf(ey.z, lx, -(ex.z * ly)));
+            c.sp = sphere_point(hd, he, dir);
+            c.sn = mk(dir.x * hb.z, dir.y * hb.z, dir.z * hb.z);
+            c.gn = c.sn;
+            if (dp_du.x == 0.0f && dp_du.y == 0.0f && dp_du.z == 0.0f) coordinate_system(c.sn, c.ss, c.stt);
+            else sh_frame_of(c.sn, dp_du, c.ss, c.stt);
+            const f3 mds = -ray_d;
+            c.wi = mk(dot(mds, c.ss), dot(mds, c.stt), dot(mds, c.sn));
+            const uint32_t mes = fbits(he.z);
+            c.mat = mes & 0xffffu; c.em_plus1 = mes >> 16;
+            return c;
+        }
+    }
     const float b1 = h.u, b2 = h.v, b0 = 1.0f - b1 - b2;
     c.sp = hit_point(hc, hd, he, b1, b2);
     c.sn = mk(ha.x, ha.y, ha.z); c.ss = mk(ha.w, hb.x, hb.y); c.stt = mk(hb.z, hb.w, hc.x);
@@ -2057,6 +2178,74 @@ MTR_HD f3 offset_point(f3 sp, f3 sn, f3 dir)
     return fma3(sn, mag, sp);
 }
 
+// ---- an `area` emitter on an analytic sphere [mitsuba3: Sphere::sample_direction / pdf_direction / sample_position, upstream-unverified]
+// Is the reference point outside?  |c - ref|^2 > (r (1 -+ RayEpsilon))^2, + under flip_normals (E.n[0] < 0)
+MTR_HD bool sphere_ref_outside(const Emitter &E, float dc2)
+{
+    const float radj = E.du[0] * (E.n[0] < 0.0f ? 1.0f + kRayEps : 1.0f - kRayEps);
+    return dc2 > radj * radj;
+}
+// 1 - cos(theta_max) of the cone the sphere subtends from a point at squared distance dc2 > r^2, as sin^2 / (1 + cos): the
+// difference 1 - sqrt(1 - sin^2) itself keeps three digits of a small cone
+MTR_HD float sphere_cone_one_minus_cos(const Emitter &E, float dc2, float &sin2_max, float &cos_max)
+{
+    sin2_max = (E.du[0] * E.du[0]) / dc2;
+    const float c2 = 1.0f - sin2_max;
+    cos_max = sqrtf(c2 > 0.0f ? c2 : 0.0f);
+    return sin2_max / (1.0f + cos_max);
+}
+// the solid-angle density of a direction towards the sphere from `ref`: uniform over the subtended cone outside, 1 / (2 pi (1 - cos
+// theta_max)); the area density 1 / (4 pi r^2) turned into solid angle inside, with the distance and |cos| at the sampled point
+MTR_HD float sphere_pdf_direction(const Emitter &E, f3 ref, float dist2, float adp)
+{
+    const f3 dc = ld3(E.center) - ref;
+    const float dc2 = dot(dc, dc);
+    if (sphere_ref_outside(E, dc2)) {
+        float s2, cm;
+        const float omc = sphere_cone_one_minus_cos(E, dc2, s2, cm);
+        const float pdf = 1.0f / ((2.0f * kPi) * omc);
+        return (fabsf(pdf) <= 3.402823466e+38f) ? pdf : 0.0f;
+    }
+    const float x = dist2 / adp;
+    return E.inv_area * ((fabsf(x) <= 3.402823466e+38f) ? x : 0.0f);
+}
+// ds.p and ds.n of a direction sample from `ref` (its density: sphere_pdf_direction, which takes the same branch)
+MTR_HD void sphere_sample_direction(const Emitter &E, f3 ref, float u1, float u2, f3 &ep, f3 &en)
+{
+    const f3 c = ld3(E.center);
+    const f3 dc = c - ref;
+    const float dc2 = dot(dc, dc), r = E.du[0];
+    f3 d;
+    if (sphere_ref_outside(E, dc2)) {
+        // the subtended cone, uniformly; the point where the sampled direction meets the sphere, as seen from its centre, makes the
+        // angle alpha with the axis towards ref
+        float sin2_max, cos_max;
+        const float omc = sphere_cone_one_minus_cos(E, dc2, sin2_max, cos_max);
+        const float sin_max = sqrtf(sin2_max);
+        const float ct = fmaf(-omc, u1, 1.0f);
+        const float sin2 = sin2_max > 0.00068523f ? fmaf(-ct, ct, 1.0f) : sin2_max * u1;
+        const float c2 = 1.0f - sin2, cos_t = sqrtf(c2 > 0.0f ? c2 : 0.0f);
+        const float w = 1.0f - sin2 / sin2_max;
+        const float cos_a = fmaf(cos_t, sqrtf(w > 0.0f ? w : 0.0f), sin2 / sin_max);
+        const float sa2 = fmaf(-cos_a, cos_a, 1.0f), sin_a = sqrtf(sa2 > 0.0f ? sa2 : 0.0f);
+        float sp, cp;
+        sincos_2pi(u2, sp, cp);
+        const f3 axis = -(dc / sqrtf(dc2));
+        f3 fs, ft;
+        coordinate_system(axis, fs, ft);
+        const float lx = cp * sin_a, ly = sp * sin_a;
+        d = mk(fmaf(axis.x, cos_a, fmaf(ft.x, ly, fs.x * lx)), fmaf(axis.y, cos_a, fmaf(ft.y, ly, fs.y * lx)), fmaf(axis.z, cos_a, fmaf(ft.z, ly, fs.z * lx)));
+    } else {
+        // sample_position: uniform on the sphere, z = 1 - 2 u2, phi = 2 pi u1
+        const float z = fmaf(-2.0f, u2, 1.0f), rho2 = fmaf(-z, z, 1.0f), rho = sqrtf(rho2 > 0.0f ? rho2 : 0.0f);
+        float sp, cp;
+        sincos_2pi(u1, sp, cp);
+        d = mk(rho * cp, rho * sp, z);
+    }
+    ep = mk(fmaf(d.x, r, c.x), fmaf(d.y, r, c.y), fmaf(d.z, r, c.z));
+    en = mk(d.x * E.n[0], d.y * E.n[0], d.z * E.n[0]);
+}
+
 // What shade_hit leaves pending while the shadow ray is in flight
 struct Pending {
     f3 Le;               // emission of this bounce (for L)
@@ -2080,7 +2269,7 @@ template <bool ROUGH = true, uint32_t TR = 0u, class Sink, class Pick = NoEmitte
 MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &film, const RenderConst &rc,
                       Sink &sink, Pending &pd, Ray &shadow, HitCtx *keep = nullptr, Pick pick = Pick())
 {
-    constexpr bool kDiff = (TR & kTrDiffuse) != 0u, kOneRect = (TR & kTrOneRectEmitter) != 0u;
+    constexpr bool kDiff = (TR & kTrDiffuse) != 0u, kOneRect = (TR & kTrOneRectEmitter) != 0u, kSph = tr_spheres(TR);
     const bool valid = h.prim >= 0;
     const float eta = kDiff ? 1.0f : p.eta;
     const bool prev_delta = kDiff ? (p.depth == 0u) : (p.prev_delta != 0u);
@@ -2093,7 +2282,7 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
     const bool in_film = (fx < film.width) & (fy < film.height);
     float u1 = rng_f32(p.rng), u2 = rng_f32(p.rng);                  // :193, unconditional for a live lane
     if (!valid) return;
-    const HitCtx c = hit_ctx<ROUGH>(sc, p.ray.d, h);
+    const HitCtx c = hit_ctx<ROUGH, tr_spheres(TR)>(sc, p.ray.d, h);
     if (keep) *keep = c;
     const mtr_material &mat = sc.mats[c.mat];
 
@@ -2112,6 +2301,7 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
             if (dp < 0.0f && (!ang || angular_falloff(E, unit_z(to_local_about(c.sn, -dd))) > 0.0f)) {
                 float adp = fabsf(dp);
                 em_pdf = E.inv_area * (adp != 0.0f ? (dist * dist) / adp : 0.0f);
+                if constexpr (kSph) { if (E.kind == kEmSphere) em_pdf = sphere_pdf_direction(E, p.prev_p, dist * dist, adp); }      // the density its sampling has
                 if (n_emitters > 1) em_pdf *= rc.inv_n_emitters;
             }
         }
@@ -2146,9 +2336,11 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
         const Emitter &E = sc.ems[ei];
         // a delta emitter [mitsuba3: point.cpp / spot.cpp sample_direction]: ds.p = the position, ds.pdf = 1, ds.delta, the weight
         // intensity * falloff / dist^2 — no random number, and mis_em = 1 below (transientpath.py:210)
-        const bool delta = !kOneRect && E.kind >= kEmPoint;
+        const bool delta = !kOneRect && (kSph ? (E.kind == kEmPoint || E.kind == kEmSpot) : E.kind >= kEmPoint);      // (without spheres: the table holds no kind beyond kEmSpot)
+        const bool sphere = kSph && E.kind == kEmSphere;
         f3 ep, en;
         if (delta) { ep = ld3(E.center); en = ld3(E.n); }                    // (en: the spot's axis; a point's is never read)
+        else if (sphere) sphere_sample_direction(E, c.sp, u1, u2, ep, en);
         else if (!kOneRect && E.kind == kEmMesh) {
             mesh_sample_position(sc.samp_tris, sc.face_cdf, sc.face_pmf, E.first_tri, E.n_tris, u1, u2, ep, en, ROUGH ? sc.samp_vn : nullptr);
         } else {
@@ -2165,6 +2357,7 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
         float x = dist2 / adp;
         float pdf_dir = E.inv_area * ((fabsf(x) <= 3.402823466e+38f) ? x : 0.0f);
         if (delta) pdf_dir = dist2 > 0.0f ? 1.0f : 0.0f;
+        if (sphere) pdf_dir = dist2 > 0.0f ? sphere_pdf_direction(E, c.sp, dist2, adp) : 0.0f;
         // angulararea sample_direction (angulararea.py:107-128): falloff of normalize(Frame3f(ds.n).to_local(-ds.d)), the term dropped where it is
         // zero, and radiance * (falloff * inv_dist^2) / ds.pdf — the reference's extra 1 / dist^2 on top of the solid-angle pdf
         // spot: the same curve of normalize(to_world^-1 (-ds.d)).z — to_world is rigid, so the frame about its +z axis gives that z
@@ -2239,7 +2432,7 @@ MTR_HD bool shade_finish(Path &p, const Hit &h, bool occluded, const Pending &pd
     f3 sp = mk(0, 0, 0);
     p.L = mk((p.L.x + pd.Le.x) + Lr.x, (p.L.y + pd.Le.y) + Lr.y, (p.L.z + pd.Le.z) + Lr.z);    // :230
     if (valid) {
-        const HitCtx c = kept ? *kept : hit_ctx<ROUGH>(sc, p.ray.d, h);
+        const HitCtx c = kept ? *kept : hit_ctx<ROUGH, tr_spheres(TR)>(sc, p.ray.d, h);
         sp = c.sp;
         if (active_next) {
             const f3 albedo = (ROUGH && pd.has_alb) ? pd.alb : material_albedo<ROUGH>(sc, sc.mats[c.mat], h);
@@ -2286,7 +2479,7 @@ MTR_HD bool path_bounce(Path &p, const SceneView &sc, const Film &film, const Re
                         Stack &st, Sink &sink, BounceStats &stats, const Refresh &refresh = Refresh(), bool unwarp_here = false)
 {
     st.prof_mark(2);
-    Hit h = traverse<false, (TR & kTrLeafPair) != 0u, flat_kind(TR)>(sc, p.ray.o, p.ray.d, p.ray.tmax, st);       // :148-151
+    Hit h = traverse<false, (TR & kTrLeafPair) != 0u, flat_kind(TR), tr_spheres(TR)>(sc, p.ray.o, p.ray.d, p.ray.tmax, st);       // :148-151
     st.prof_mark(0);
     stats.closest++;
     Pending pd; Ray shadow;
@@ -2303,7 +2496,7 @@ MTR_HD bool path_bounce(Path &p, const SceneView &sc, const Film &film, const Re
     bool occluded = false;
     if (pd.has_shadow) {
         stats.shadow++;
-        Hit sh = traverse<true, (TR & kTrLeafPair) != 0u, flat_kind(TR)>(sc, shadow.o, shadow.d, shadow.tmax, st);
+        Hit sh = traverse<true, (TR & kTrLeafPair) != 0u, flat_kind(TR), tr_spheres(TR)>(sc, shadow.o, shadow.d, shadow.tmax, st);
         occluded = sh.prim >= 0;
     }
     st.prof_mark(0);

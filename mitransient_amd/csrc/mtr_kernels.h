@@ -183,7 +183,8 @@ struct WfArgs {
     // (polarized transport keeps its Mueller / Stokes planes in the same allocation, behind the planes above: wf_polar_planes —
     // WfArgs itself is not extended, so that the argument layout of every existing kernel stays what it was)
 };
-struct WfConfig { int stack; bool scene_lds; size_t lds_bytes; };
+struct WfConfig { int stack; bool scene_lds; size_t lds_bytes;
+                  bool spheres = true; };      // the scene may hold analytic spheres (the caller knows: false picks the kernels without their code)
 
 size_t wf_planes_bytes(uint32_t n_slots);
 size_t wf_polar_planes_bytes(uint32_t n_slots);      // polarized transport: what follows wf_planes_bytes, rounded up to 16, in `planes`

@@ -15,6 +15,9 @@ namespace mtr {
 
 constexpr float kDrEps = 5.9604644775390625e-8f;      // dr.epsilon(Float) = 2^-24
 
+// is_rect: mtr_shape.is_rectangle, or kNlosSphere for an analytic sphere (ABI 23): center, du[0] = radius, n[0] = -1 under
+// flip_normals else 1, inv_area = 1 / (4 pi r^2)
+constexpr uint32_t kNlosSphere = 0x100u;
 struct alignas(16) NlosShape {       // 64 B
     float center[3], du[3], dv[3], n[3];
     uint32_t first_tri, n_tris, is_rect;
@@ -192,7 +195,7 @@ MTR_HD f3 nlos_emitter_nee(Path &p, const HitCtx &c, const mtr_material &mat, f3
     // visibility of the emitter origin (:441)
     const Ray sr = spawn_ray_to(c.sp, c.gn, nc.l_origin);
     stats.shadow++;
-    const bool blocked = traverse<true>(sc, sr.o, sr.d, sr.tmax, st).prim >= 0;
+    const bool blocked = traverse<true, false, 0, tr_spheres(TR)>(sc, sr.o, sr.d, sr.tmax, st).prim >= 0;
     reload();
     if (blocked) return mk(0, 0, 0);
     (void)rng_f32(p.rng); (void)rng_f32(p.rng);                      // sampler.next_2d(active_e): only visible lanes draw
@@ -233,15 +236,15 @@ MTR_HD f3 nlos_laser_targets(Path &p, const HitCtx &c, const mtr_material &mat, 
     dd = dd / dl;
     Ray rb = spawn_ray_to(c.sp, c.gn, lt);
     stats.shadow++;
-    if (traverse<true>(sc, rb.o, rb.d, rb.tmax, st).prim >= 0) { reload(); return mk(0, 0, 0); }             // :528
+    if (traverse<true, false, 0, tr_spheres(TR)>(sc, rb.o, rb.d, rb.tmax, st).prim >= 0) { reload(); return mk(0, 0, 0); }             // :528
     const f3 wo = mk(dot(dd, c.ss), dot(dd, c.stt), dot(dd, c.sn));
     const f3 bs = bsdf_eval_cos<EXT, TR>(mat, albedo, c.wi, wo);                              // :531-533
-    const Hit h2 = traverse<false>(sc, rb.o, rb.d, kInf, st);                                  // :535-537
+    const Hit h2 = traverse<false, false, 0, tr_spheres(TR)>(sc, rb.o, rb.d, kInf, st);                                  // :535-537
     reload();
     stats.closest++;
     if (h2.prim < 0) return mk(0, 0, 0);
     if (!(bs.x > kDrEps || bs.y > kDrEps || bs.z > kDrEps)) return mk(0, 0, 0);               // :539-540
-    const HitCtx c2 = hit_ctx<EXT>(sc, rb.d, h2);
+    const HitCtx c2 = hit_ctx<EXT, tr_spheres(TR)>(sc, rb.d, h2);
     const f3 md = -dd;
     const float wlz = dot(md, c2.sn);                                                          // cos_theta(si_bsdf.to_local(-d))
     if (!(wlz > 0.0f)) return mk(0, 0, 0);                                                     // :543
@@ -262,6 +265,14 @@ MTR_HD BsdfSample nlos_hidden_geometry(const HitCtx &c, const mtr_material &mat,
     const uint32_t s = distr_sample_reuse(nc.shape_cdf, nc.shape_pmf, nc.n_shapes, ua, reused, spmf);
     const NlosShape &S = nc.shapes[s];
     f3 pp, pn;
+    if (tr_spheres(TR) && (S.is_rect & kNlosSphere)) {      // [mitsuba3: Sphere::sample_position] z = 1 - 2 u2, phi = 2 pi u1
+        const float z = fmaf(-2.0f, ub, 1.0f), rho2 = fmaf(-z, z, 1.0f), rho = sqrtf(rho2 > 0.0f ? rho2 : 0.0f);
+        float sp, cp;
+        sincos_2pi(reused, sp, cp);
+        const f3 d = mk(rho * cp, rho * sp, z);
+        pp = mk(fmaf(d.x, S.du[0], S.center[0]), fmaf(d.y, S.du[0], S.center[1]), fmaf(d.z, S.du[0], S.center[2]));
+        pn = mk(d.x * S.n[0], d.y * S.n[0], d.z * S.n[0]);
+    } else
     if (S.is_rect) {
         pp = rect_point(ld3(S.center), ld3(S.du), ld3(S.dv), reused, ub);
         pn = ld3(S.n);
@@ -297,7 +308,7 @@ template <bool EXT = false, uint32_t TR = 0u, class Stack, class Sink, class Rel
 MTR_HD bool nlos_bounce(Path &p, const SceneView &sc, const NlosConst &nc, const Film &film, const RenderConst &rc,
                         Stack &st, Sink &sink, BounceStats &stats, const Reload &reload = Reload(), Hook hook = Hook())
 {
-    const Hit h = traverse<false>(sc, p.ray.o, p.ray.d, p.ray.tmax, st);
+    const Hit h = traverse<false, false, 0, tr_spheres(TR)>(sc, p.ray.o, p.ray.d, p.ray.tmax, st);
     reload();
     stats.closest++;
     const bool valid = h.prim >= 0;
@@ -306,7 +317,7 @@ MTR_HD bool nlos_bounce(Path &p, const SceneView &sc, const NlosConst &nc, const
     f3 Lr = mk(0, 0, 0);
     HitCtx c;
     c.sp = mk(0, 0, 0); c.sn = mk(0, 0, 1); c.gn = mk(0, 0, 1); c.ss = mk(1, 0, 0); c.stt = mk(0, 1, 0); c.wi = mk(0, 0, 0); c.mat = 0; c.em_plus1 = 0;
-    if (valid) c = hit_ctx<EXT>(sc, p.ray.d, h);
+    if (valid) c = hit_ctx<EXT, tr_spheres(TR)>(sc, p.ray.d, h);
     const mtr_material &mat = sc.mats[c.mat];
     const f3 albedo = valid ? material_albedo<EXT>(sc, mat, h) : mk(0, 0, 0);
     if constexpr (Hook::kOn) hook.vertex(c.mat, active_next);

@@ -153,11 +153,34 @@ const char *derive_scene(const mtr_scene_desc &d, HostScene &s)
     std::vector<int32_t> object(d.n_tris, -1);
     std::vector<float> object_xf;
     std::vector<const mtr_shape *> rect_of(d.n_tris, nullptr);
+    std::vector<const mtr_shape *> sphere_of;             // (sized on the first sphere)
+    std::vector<float> sphere_verts;                      // ... and then the caller's vertices with every sphere's carrier triangle spanning its box
+    const float *verts = d.tri_verts;
+    s.has_sphere = false;
     uint32_t covered = 0;
     for (uint32_t k = 0; k < d.n_shapes && d.shapes; ++k) {
         const mtr_shape &S = d.shapes[k];
         if (S.first_tri != covered || (uint64_t)S.first_tri + S.n_tris > d.n_tris) return "shapes must tile the triangle array in order";
         covered += S.n_tris;
+        if ((S.kind & 0xffu) == MTR_SHAPE_SPHERE) {
+            // analytic sphere (ABI 23): ONE primitive with the box c +- r; its carrier triangle is never intersected, so the builders
+            // are handed a triangle whose corners span that box
+            if (S.n_tris != 1 || S.is_rectangle) return "a sphere shape owns exactly one carrier triangle (and is no rectangle)";
+            if (!(S.radius > 0.0f) || !std::isfinite(S.radius) || !std::isfinite(S.center[0]) || !std::isfinite(S.center[1]) || !std::isfinite(S.center[2]))
+                return "sphere: the radius must be positive and finite, the centre finite";
+            if (d.materials[d.tri_material[S.first_tri]].albedo_texture != 0u) return "sphere: bitmap textures are not supported (a sphere has no uv)";
+            // its carrier triangle is never sampled: the only emitter it may reference is the sphere light
+            if (d.tri_emitter[S.first_tri] >= 0 && d.emitters[d.tri_emitter[S.first_tri]].kind != MTR_EMITTER_SPHERE)
+                return "sphere: the carrier triangle may reference a MTR_EMITTER_SPHERE emitter only";
+            if (sphere_of.empty()) { sphere_of.assign(d.n_tris, nullptr); sphere_verts.assign(d.tri_verts, d.tri_verts + 9 * (size_t)d.n_tris); verts = sphere_verts.data(); }
+            sphere_of[S.first_tri] = &S; kind[S.first_tri] = 3; s.has_sphere = true;
+            const float rr = S.radius * 1.000001f;
+            const float lo[3] = { S.center[0] - rr, S.center[1] - rr, S.center[2] - rr }, hi[3] = { S.center[0] + rr, S.center[1] + rr, S.center[2] + rr };
+            float *v = &sphere_verts[9 * (size_t)S.first_tri];
+            v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = hi[0]; v[4] = hi[1]; v[5] = lo[2]; v[6] = lo[0]; v[7] = hi[1]; v[8] = hi[2];
+            continue;
+        }
+        if (S.kind != MTR_SHAPE_DEFAULT) return "shape: unknown kind";
         if (S.is_rectangle) {
             if (S.n_tris != 2) return "a rectangle shape owns exactly two carrier triangles";
             kind[S.first_tri] = 1; kind[S.first_tri + 1] = 2;
@@ -170,7 +193,7 @@ const char *derive_scene(const mtr_scene_desc &d, HostScene &s)
         // (an axis-aligned transform gains nothing from object-space boxes — unless the shape is an affine cube, which
         // becomes a box node whatever its orientation)
         if (S.has_to_world && S.n_tris >= 4 && S.n_tris <= 16 && object_space_of(S.to_world, inv, &aligned) &&
-            (!aligned || (S.n_tris == 12 && mesh_is_affine_box(d.tri_verts, S.first_tri, inv, faces)))) {
+            (!aligned || (S.n_tris == 12 && mesh_is_affine_box(verts, S.first_tri, inv, faces)))) {
             for (uint32_t t = 0; t < S.n_tris; ++t) object[S.first_tri + t] = (int32_t)(object_xf.size() / 12);
             object_xf.insert(object_xf.end(), inv, inv + 12);
         }
@@ -185,12 +208,12 @@ const char *derive_scene(const mtr_scene_desc &d, HostScene &s)
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_phase = now();
     auto phase = [&](const char *what) { if (verbose) { const double t = now(); fprintf(stderr, "derive_scene: %-28s %.3f s\n", what, t - t_phase); t_phase = t; } };
-    build_bvh(d.tri_verts, d.n_tris, &prims, bvh);
+    build_bvh(verts, d.n_tris, &prims, bvh);
     phase("build_bvh");
     s.nodes = bvh.nodes; s.bvh_depth = bvh.max_depth; s.n_leaves = bvh.n_leaves;
     s.wnodes.clear();
     s.has_wide = bvh.nodes.size() <= 2048;
-    s.wide_levels = s.has_wide ? build_wide(bvh, &prims, d.tri_verts, s.wnodes) : 0;
+    s.wide_levels = s.has_wide ? build_wide(bvh, &prims, verts, s.wnodes) : 0;
     s.wnodes4.clear();
     s.wide4_levels = build_wide4(bvh, s.wnodes4);
     phase("build_wide + build_wide4");
@@ -220,6 +243,7 @@ const char *derive_scene(const mtr_scene_desc &d, HostScene &s)
     if (d.n_tris >= (1u << 29)) return "too many triangles (the tie-break word holds 29 bits of triangle index)";
     // (a leaf's code is (first slot << 2 | count - 1) under kLeafQuadBit = bit 30; spatial splits duplicate references: up to 2 slots per triangle)
     if (n_slots >= (1u << 28)) return "too many triangle slots (a leaf code holds 28 bits of slot index)";
+    if (s.has_sphere && n_slots >= (1u << 27)) return "too many triangle slots beside a sphere (kLeafSphereBit takes the slot index's top bit)";
     // the tie-break word of an intersection record: (original index << 3) | list key of the triangle's material (mtr_core.h hit_list_key)
     auto tie_word = [&](uint32_t orig) { return (orig << 3) | hit_list_key(d.materials[d.tri_material[orig]].type); };
     for (uint32_t slot = 0; slot < n_slots; ++slot) {
@@ -228,6 +252,31 @@ const char *derive_scene(const mtr_scene_desc &d, HostScene &s)
         const float *v = d.tri_verts + 9 * (size_t)o;
         TriShade &h = s.tshade[slot];
         const uint32_t mat_em = d.tri_material[o] | ((uint32_t)(d.tri_emitter[o] + 1) << 16);
+        if (const mtr_shape *P = sphere_of.empty() ? nullptr : sphere_of[o]) {
+            // analytic sphere [mitsuba3: src/shapes/sphere.cpp, upstream-unverified]: both slots of its pair (the carrier and the pad)
+            // describe the ONE primitive; ex, ey: the unit world images of the object's x and y axes (to_world is a rotation times a
+            // uniform scale: scene.py refuses anything else), Gram-Schmidt'ed in f64 so that dp_du stays tangent
+            const uint32_t prim = P->first_tri;
+            double ax[3] = { 1, 0, 0 }, ay[3] = { 0, 1, 0 };
+            if (P->has_to_world) for (int k = 0; k < 3; ++k) { ax[k] = P->to_world[4 * k]; ay[k] = P->to_world[4 * k + 1]; }
+            const double lx = sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+            if (!(lx > 0.0)) return "sphere: singular to_world";
+            for (int k = 0; k < 3; ++k) ax[k] /= lx;
+            const double dxy = ax[0] * ay[0] + ax[1] * ay[1] + ax[2] * ay[2];
+            for (int k = 0; k < 3; ++k) ay[k] -= dxy * ax[k];
+            const double ly = sqrt(ay[0] * ay[0] + ay[1] * ay[1] + ay[2] * ay[2]);
+            if (!(ly > 0.0)) return "sphere: singular to_world";
+            for (int k = 0; k < 3; ++k) ay[k] /= ly;
+            TriPair &tp = s.tpairs[slot >> 1];
+            tp.g[0] = q4{ P->center[0], P->center[1], P->center[2], P->radius };
+            tp.g[1] = tp.g[2] = tp.g[3] = q4{ 0, 0, 0, 0 }; tp.g[4] = q4{ 0, 0, bitsf(tie_word(prim)), bitsf(kQuadMark) };
+            h.h[0] = q4{ (float)ax[0], (float)ax[1], (float)ax[2], (float)ay[0] };
+            h.h[1] = q4{ (float)ay[1], (float)ay[2], (P->kind & MTR_SHAPE_FLIP_NORMALS) ? -1.0f : 1.0f, 0.0f };
+            h.h[2] = q4{ 0, 0, 0, 0 };
+            h.h[3] = q4{ P->radius, 0.0f, 0.0f, P->center[0] };
+            h.h[4] = q4{ P->center[1], P->center[2], bitsf(mat_em), bitsf(prim | kShadeSphereBit) };
+            continue;
+        }
         if (const mtr_shape *R = rect_of[o]) {
             // analytic rectangle [mitsuba3: src/shapes/rectangle.cpp]: both slots of its pair describe the ONE primitive
             // (index = its first carrier triangle)
@@ -306,6 +355,27 @@ const char *derive_scene(const mtr_scene_desc &d, HostScene &s)
         E.kind = e.is_mesh ? kEmMesh : kEmRect; E.first_tri = e.first_tri; E.n_tris = e.n_tris;
         E.angular = e.angular ? 1u : 0u;
         E.cutoff = E.cos_cutoff = E.cos_beam = E.inv_transition = 0.0f;
+        if (e.kind == MTR_EMITTER_SPHERE) {    // (ABI 23) an `area` emitter on an analytic sphere
+            if (!(e.radius > 0.0f) || !std::isfinite(e.radius)) return "sphere emitter: the radius must be positive and finite";
+            if (e.angular) return "sphere emitter: angulararea is not supported on a sphere";
+            if (d.nlos) return "NLOS: area emitters are not supported next to the projector";
+            bool carried = false;         // ... that a sphere shape with the same centre and radius carries
+            for (uint32_t k = 0; k < d.n_shapes && d.shapes && !carried; ++k) {
+                const mtr_shape &S = d.shapes[k];
+                carried = (S.kind & 0xffu) == MTR_SHAPE_SPHERE && S.n_tris == 1 && d.tri_emitter[S.first_tri] == (int32_t)i && S.radius == e.radius &&
+                          S.center[0] == e.center[0] && S.center[1] == e.center[1] && S.center[2] == e.center[2] &&
+                          ((S.kind & MTR_SHAPE_FLIP_NORMALS) != 0u) == (e.flip_normals != 0u);
+            }
+            if (!carried) return "sphere emitter: no sphere shape with this centre, radius and flip_normals references it";
+            E.kind = kEmSphere; E.first_tri = E.n_tris = 0u; E.angular = 0u;
+            for (int k = 0; k < 3; ++k) {
+                if (!std::isfinite(e.center[k]) || !std::isfinite(e.radiance[k])) return "sphere emitter: centre and radiance must be finite";
+                E.center[k] = e.center[k]; E.du[k] = E.dv[k] = E.n[k] = 0.0f; E.radiance[k] = e.radiance[k];
+            }
+            E.du[0] = e.radius; E.n[0] = e.flip_normals ? -1.0f : 1.0f;
+            E.inv_area = (float)(1.0 / (4.0 * 3.14159265358979323846 * (double)e.radius * (double)e.radius));
+            continue;
+        }
         if (e.kind != MTR_EMITTER_AREA) {      // (ABI 22) a delta emitter: the position, the intensity, and a spot's axis and falloff constants
             if (e.kind != MTR_EMITTER_POINT && e.kind != MTR_EMITTER_SPOT) return "emitter: unknown kind";
             if (d.nlos) return "NLOS: point / spot emitters are not supported next to the projector";
@@ -397,7 +467,7 @@ void classify_scene(const mtr_scene_desc &d, HostScene &hs)
         if (!polar_bsdf_supported(d.materials[i].type)) hs.polar_ok = false;
         if (bsdf_is_lobe(d.materials[i].type)) lobes = true;
     }
-    for (const Emitter &e : hs.ems) if (e.angular || e.kind >= kEmPoint) hs.polar_ok = false;
+    for (const Emitter &e : hs.ems) if (e.angular || e.kind >= kEmPoint) hs.polar_ok = false;      // (point, spot and the sphere light: mtr_polar.h samples rectangles and meshes)
     hs.needs_ext = lobes || !hs.vnormals.empty() || !hs.texels.empty();      // smooth-shaded triangles, bitmap textures: the extended shading code as well
     // scene traits (mtr_core.h): facts about the tables that let the kernels drop shading code no hit can reach
     hs.traits = 0u;
@@ -406,20 +476,20 @@ void classify_scene(const mtr_scene_desc &d, HostScene &hs)
         for (uint32_t i = 0; i < d.n_materials; ++i)
             if (d.materials[i].type != MTR_BSDF_DIFFUSE || (d.materials[i].flags & MTR_MAT_TWOSIDED)) diffuse_only = false;
         if (diffuse_only) hs.traits |= kTrDiffuse;
-        if (d.n_emitters == 1 && hs.ems[0].kind == kEmRect && !hs.ems[0].angular) hs.traits |= kTrOneRectEmitter;     // (its kernels have no falloff code, and no delta emitter)
+        if (d.n_emitters == 1 && hs.ems[0].kind == kEmRect && !hs.ems[0].angular && !hs.has_sphere) hs.traits |= kTrOneRectEmitter;     // (its kernels have no falloff code, and no delta emitter)
         bool leaf_pairs = hs.has_wide;
         for (const WNode &n : hs.wnodes)
             for (uint32_t k = 0; k < n.count; ++k) {
                 const uint32_t code = ~(uint32_t)n.ref[k];
                 if (n.ref[k] < 0 && !(code & kLeafQuadBit) && (code & 3u) + 1u > 2u) leaf_pairs = false;
             }
-        if (leaf_pairs) hs.traits |= kTrLeafPair;
+        if (leaf_pairs && !hs.has_sphere) hs.traits |= kTrLeafPair;      // (a sphere: none of the traits of tr_spheres, mtr_core.h — the walkers specialised on them hold no sphere test)
     } else if (!lobes) hs.traits |= kTrNoLobes;          // the extended shading code is needed for normals / bitmaps only
-    hs.grey_scene = colours_are_grey(d.materials, d.n_materials, hs.ems.data(), d.n_emitters, !hs.texels.empty());
+    hs.grey_scene = scene_is_grey(hs.has_sphere, d.materials, d.n_materials, hs.ems.data(), d.n_emitters, !hs.texels.empty());
     if (hs.grey_scene) hs.traits |= kTrGrey;             // (the scene's part; the NLOS tier adds the laser's: traits_with_laser)
     // kTrFlatTop (any materials): the root's children are rectangles and box nodes, the boxes' nodes follow the root in order
     memset(&hs.flat, 0, sizeof hs.flat);
-    if (hs.has_wide && !hs.wnodes.empty() && hs.wide_levels <= 2 && !mtr::knob("MTR_NO_FLAT")) {
+    if (hs.has_wide && !hs.wnodes.empty() && hs.wide_levels <= 2 && !hs.has_sphere && !mtr::knob("MTR_NO_FLAT")) {
         const WNode &root = hs.wnodes[0];
         bool flat = root.flags == 0u && root.count >= 1u;
         uint32_t n_inner = 0u, prim_mask = 0u;
@@ -514,6 +584,17 @@ const char *derive_nlos(const mtr_scene_desc &d, HostNlos &o)
         const mtr_shape &S = n->shapes[s];
         NlosShape &D = o.shapes[s];
         D.first_tri = S.first_tri; D.n_tris = S.n_tris; D.is_rect = S.is_rectangle;
+        if ((S.kind & 0xffu) == MTR_SHAPE_SPHERE) {      // (ABI 23) [mitsuba3: Sphere::sample_position / surface_area]: its carrier triangle is never sampled
+            D.is_rect = kNlosSphere;
+            for (int c = 0; c < 3; ++c) { D.center[c] = S.center[c]; D.du[c] = D.dv[c] = D.n[c] = 0.0f; }
+            D.du[0] = S.radius; D.n[0] = (S.kind & MTR_SHAPE_FLIP_NORMALS) ? -1.0f : 1.0f;
+            const double a = 4.0 * 3.14159265358979323846 * (double)S.radius * (double)S.radius;
+            D.inv_area = (float)(1.0 / a);
+            o.face_pmf[S.first_tri] = o.face_cdf[S.first_tri] = 1.0f;
+            area[s] = (s == n->relay_shape && !(n->flags & MTR_NLOS_HG_INCLUDES_WALL)) ? 0.0 : a;
+            total += area[s];
+            continue;
+        }
         double a = fill_mesh_tables(d.tri_verts, S.first_tri, S.n_tris, o.face_pmf.data(), o.face_cdf.data(), o.hg_tris.data());
         if (!S.is_rectangle) fill_mesh_normals(d.tri_normals, S.first_tri, S.n_tris, d.n_tris, o.hg_vn);
         if (S.is_rectangle) {

@@ -37,12 +37,20 @@ struct HostScene {
     bool needs_ext = false;                    // the extended shading code: a lobe, a smooth-shaded triangle, a bitmap (SceneDev::has_rough)
     bool polar_ok = false;                     // every material and emitter has a polarized form (mtr_polar.h)
     bool grey_scene = false;                   // kTrGrey without the NLOS laser (traits_with_laser decides with it)
+    bool has_sphere = false;                   // an analytic sphere among the shapes: none of the traits tr_spheres (mtr_core.h) names
     FlatTop flat{};                            // traits & kTrFlatTop: the top level as scalar kernel arguments
 };
 
 inline bool bsdf_is_lobe(uint32_t type) { return bsdf_is_rough(type) || type == MTR_BSDF_THINDIELECTRIC; }     // what only the extended shading code evaluates
 // the colour-dependent trait (kTrGrey, the scene's part): three equal channels in every colour, no bitmap
 bool colours_are_grey(const mtr_material *mats, uint32_t n_mats, const Emitter *ems, uint32_t n_ems, bool textured);
+// ... as the scene's own part of kTrGrey: a scene with an analytic sphere never has it, whatever its colours (mtr_core.h tr_spheres: the
+// one-plane NLOS kernels hold no sphere code) — a grey NLOS scene with a hidden ball renders with three-plane rows.  The one place that
+// rule lives: classify_scene and the colour updates of the API layer all decide through it
+inline bool scene_is_grey(bool has_sphere, const mtr_material *mats, uint32_t n_mats, const Emitter *ems, uint32_t n_ems, bool textured)
+{
+    return !has_sphere && colours_are_grey(mats, n_mats, ems, n_ems, textured);
+}
 // fills traits, needs_ext, polar_ok, grey_scene and flat from the tables (derive_scene ends with it)
 void classify_scene(const mtr_scene_desc &d, HostScene &s);
 // kTrGrey of the NLOS tier: the scene's colours and the laser's irradiance

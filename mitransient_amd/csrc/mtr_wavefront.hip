@@ -405,7 +405,8 @@ __global__ void __launch_bounds__(kBlock) k_wf_raygen(const WfArgs a)
 // FIRST: the closest hits of bounce 0 — the live list is the identity and a camera ray is a function of (pixel, sample): both are
 // computed here (path_begin, as k_wf_shade<FIRST> does for the rest of the state) instead of written by k_wf_raygen and read back,
 // 36 B per slot each way (config 2: 9.7 GB written + 9.7 GB read per render)
-template <int STACK, bool SCENE_LDS, bool ANY, bool FIRST = false>
+// SPH: the tree may hold sphere leaves (false: the scene has none, WfConfig::spheres — no sphere test in the leaf step)
+template <int STACK, bool SCENE_LDS, bool ANY, bool FIRST = false, bool SPH = true>
 __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_TRACE_WAVES_LDS : (ANY ? MTR_WF_TRACE_WAVES_ANY : MTR_WF_TRACE_WAVES)) k_wf_trace(const WfArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -496,7 +497,7 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_TRACE_WAVES_LDS : (
 #endif
             if (SCENE_LDS) {
                 if (n_node >= n_leaf) { if (at_node) wide_node_step<kWide, true>(tr, sv.wnodes, st); }
-                else { if (at_leaf) wide_leaf_step<kWide>(tr, sv, sv.wnodes, st, any_hit); }
+                else { if (at_leaf) wide_leaf_step<kWide, false, SPH>(tr, sv, sv.wnodes, st, any_hit); }
             } else {
                 // (release builds always hold the quantised 8-wide tree of a scene walked in HBM — mtr_scene_host.cpp — so the
                 // 4-wide walker is compiled only where a knob can switch the tree off: half the code, no spills in either instantiation)
@@ -506,12 +507,12 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_TRACE_WAVES_LDS : (
                 {
 #endif
                     if (n_node >= n_leaf) { if (at_node) q8_node_step(tr, sv.wnodes8q, st); }
-                    else { if (at_leaf) q8_leaf_step(tr, sv, st, any_hit); }
+                    else { if (at_leaf) q8_leaf_step<SPH>(tr, sv, st, any_hit); }
                 }
 #ifdef MTR_EXPERIMENTS
                 else {
                     if (n_node >= n_leaf) { if (at_node) qwide_node_step(tr, sv.wnodes4, st); }
-                    else { if (at_leaf) qwide_leaf_step(tr, sv, st, any_hit); }
+                    else { if (at_leaf) qwide_leaf_step<SPH>(tr, sv, st, any_hit); }
                 }
 #endif
             }
@@ -686,7 +687,7 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_SHADE_WAVES_LDS : M
                         const uint32_t prev_pos = __float_as_uint(r_cur[2 * (size_t)lpos].w);
                         const float4 hq = P.ld(hit_plane(par ^ 1u), sg * a.seg + prev_pos);
                         Hit hp; hp.t = hq.x; hp.u = hq.y; hp.v = hq.z; hp.prim = (int32_t)__float_as_uint(hq.w);
-                        p.prev_p = hit_point(sv, hp);
+                        p.prev_p = hit_point<tr_spheres(TR)>(sv, hp);
                     }
                     ++n_closest;
                     RecordSink sink = make_sink(pl, p.lane);
@@ -709,7 +710,7 @@ __global__ void __launch_bounds__(kBlock, SCENE_LDS ? MTR_WF_SHADE_WAVES_LDS : M
                     if (pd.has_shadow) {
                         ++n_shadow;
                         if (SCENE_LDS) {                  // short rays out of LDS: tracing them right here is cheaper (config 2: 168 vs 243 ms)
-                            Hit sh = traverse<true, (TR & kTrLeafPair) != 0u, flat_kind(TR)>(sv, shadow.o, shadow.d, shadow.tmax, st);
+                            Hit sh = traverse<true, (TR & kTrLeafPair) != 0u, flat_kind(TR), tr_spheres(TR)>(sv, shadow.o, shadow.d, shadow.tmax, st);
                             occluded = sh.prim >= 0;
                         } else {
                             // the ray goes to the segment's shadow list (k_wf_trace, any-hit, runs next), the term is parked and
@@ -1296,8 +1297,10 @@ __global__ void __launch_bounds__(kBlock) k_wf_polar_scatter(const WfArgs a)
 // hit material types / occlusion flags)
 uint32_t bounce_lds_tail(const WfArgs &a) { return al16(a.G * 4u) + al16(a.G * 16u) + al16(a.seg); }
 
+// sph: the scene may hold analytic spheres; without them the trace and shade kernels are the instantiations that lack the sphere
+// test and the sphere branches (kTrNoSphere, mtr_core.h)
 template <int STACK, bool SL>
-hipError_t launch_set(const WfArgs &a, WfKernel which, int grid, size_t lds, hipStream_t stream)
+hipError_t launch_set(const WfArgs &a, WfKernel which, int grid, size_t lds, hipStream_t stream, bool sph)
 {
     const bool ext = a.sc.has_rough != 0u;
     if constexpr (SL) {          // scenes staged in LDS whose tables allow it: the specialised shading code (as k_fused)
@@ -1326,6 +1329,11 @@ hipError_t launch_set(const WfArgs &a, WfKernel which, int grid, size_t lds, hip
                             : which == WfKernel::NlosBounce ? (ext ? k_wf_nlos_bounce<STACK, SL, true> : k_wf_nlos_bounce<STACK, SL, false>)
                             : a.first_bounce ? (ext ? k_wf_shade<STACK, SL, true, 0u, true> : k_wf_shade<STACK, SL, false, 0u, true>)
                             : (ext ? k_wf_shade<STACK, SL, true> : k_wf_shade<STACK, SL, false>);
+    if (!sph && which == WfKernel::Trace)
+        k = a.trace_any ? k_wf_trace<STACK, SL, true, false, false> : a.first_bounce ? k_wf_trace<STACK, SL, false, true, false> : k_wf_trace<STACK, SL, false, false, false>;
+    if (!sph && which == WfKernel::Shade)
+        k = a.first_bounce ? (ext ? k_wf_shade<STACK, SL, true, kTrNoSphere, true> : k_wf_shade<STACK, SL, false, kTrNoSphere, true>)
+                           : (ext ? k_wf_shade<STACK, SL, true, kTrNoSphere> : k_wf_shade<STACK, SL, false, kTrNoSphere>);
     lds += bounce_lds_tail(a);
     hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -1384,8 +1392,8 @@ hipError_t launch_wf(const WfArgs &a, const WfConfig &cfg, WfKernel which, int g
     }
     // (the traversal stack is sized by the levels of the tree that is walked — wf_stack_rows — not by a compile-time class: ONE
     // instantiation of every kernel; rounds 1-4 compiled four identical copies, for stack classes 8 / 16 / 32 / 64)
-    return cfg.scene_lds ? launch_set<64, true>(a, which, grid, cfg.lds_bytes, stream)
-                         : launch_set<64, false>(a, which, grid, cfg.lds_bytes, stream);
+    return cfg.scene_lds ? launch_set<64, true>(a, which, grid, cfg.lds_bytes, stream, cfg.spheres)
+                         : launch_set<64, false>(a, which, grid, cfg.lds_bytes, stream, cfg.spheres);
 }
 
 } // namespace mtr

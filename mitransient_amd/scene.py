@@ -418,9 +418,14 @@ class _SceneBuilder:
                 nt = vn.reshape(-1, 3) @ np.linalg.inv(tw.matrix[:3, :3])
                 ln = np.linalg.norm(nt, axis=1, keepdims=True)
                 normals = np.where(ln > 0, nt / np.where(ln > 0, ln, 1.0), 0.0).reshape(-1, 9)
+        elif t == "sphere":
+            # an analytic primitive [mitsuba3: src/shapes/sphere.cpp] (mtr_shape.kind): to_world . translate(center) . scale(radius);
+            # its one triangle only carries the material / emitter / index (the host scene builder gives it the sphere's box)
+            sph_c, sph_r, tw = _sphere_of(name, sd, tw)
+            tris = np.stack([sph_c + sph_r * np.array([[-1, -1, -1], [1, 1, -1], [-1, 1, 1]], dtype=np.float64)])
         else:
-            raise ValueError(f"failed to instantiate unknown plugin of type \"{t}\" (supported shapes: rectangle, cube, obj, ply)")
-        if sd.get("flip_normals", False):
+            raise ValueError(f"failed to instantiate unknown plugin of type \"{t}\" (supported shapes: rectangle, cube, obj, ply, sphere)")
+        if sd.get("flip_normals", False) and t != "sphere":
             tris = tris[:, [0, 2, 1], :]
             if uv is not None:
                 uv = uv.reshape(-1, 3, 2)[:, [0, 2, 1], :].reshape(-1, 6)
@@ -445,6 +450,8 @@ class _SceneBuilder:
         mi_ = self.material_index(bsdf)
         self.cur_shape = None
         self.shape_mat[name] = mi_
+        if t == "sphere" and self.materials[mi_].albedo_texture:
+            raise ValueError(f"{name}: a bitmap texture is not available on a sphere (the analytic sphere computes no uv)")
         em_index = -1
         if em is not None:
             et = em.get("type")
@@ -452,6 +459,8 @@ class _SceneBuilder:
                 raise ValueError(f"failed to instantiate unknown plugin of type \"{et}\" (supported emitters on a shape: area, angulararea)")
             e = _cabi.mtr_emitter()
             rad = _color3(em.get("radiance", 1.0), f"{et}.radiance")
+            if et == "angulararea" and t == "sphere":
+                raise ValueError(f"{name}: the angulararea emitter is not available on a sphere (supported there: area)")
             if et == "angulararea":
                 if self.nlos:      # transientnlospath.py:256-260: the NLOS tier takes exactly one emitter, a projector
                     raise ValueError("transient_nlos_path: an angulararea emitter cannot light a NLOS scene (one projector is required)")
@@ -463,6 +472,12 @@ class _SceneBuilder:
                 for k in range(3):
                     e.center[k], e.du[k], e.dv[k] = np.float32(c[k]), np.float32(du[k]), np.float32(dv[k])
                 e.flip_normals = 1 if sd.get("flip_normals", False) else 0      # [Rectangle::sample_position: ps.n = -frame.n]
+            elif t == "sphere":                     # [Sphere::sample_direction: the subtended cone from outside, the surface from inside]
+                e.kind = _cabi.MTR_EMITTER_SPHERE
+                for k in range(3):
+                    e.center[k] = np.float32(sph_c[k])
+                e.radius = np.float32(sph_r)
+                e.flip_normals = 1 if sd.get("flip_normals", False) else 0
             else:                                   # triangle-mesh emitter: sampled by face area [Mesh::sample_position]
                 e.is_mesh = 1
                 e.first_tri = sum(a.shape[0] for a in self.tri_verts)
@@ -496,7 +511,33 @@ class _SceneBuilder:
             dv = tw.transform_affine(np.array([0, 1.0, 0])) - c
             for k in range(3):
                 sh.center[k], sh.du[k], sh.dv[k] = np.float32(c[k]), np.float32(du[k]), np.float32(dv[k])
+        if t == "sphere":
+            sh.kind = _cabi.MTR_SHAPE_SPHERE | (_cabi.MTR_SHAPE_FLIP_NORMALS if sd.get("flip_normals", False) else 0)
+            sh.radius = np.float32(sph_r)
+            for k in range(3):
+                sh.center[k] = np.float32(sph_c[k])
         self.shapes.append(sh)
+
+
+def _sphere_of(name: str, sd: Dict[str, Any], tw):
+    """world centre, world radius and the whole object -> world transform of a `sphere` dictionary [mitsuba3: Sphere's constructor and
+    update(), upstream-unverified]: to_world . translate(center) . scale(radius); the centre is to_world (0,0,0), the radius
+    |to_world (1,0,0) - centre|; a to_world whose linear part is not a rotation times a uniform scale is refused."""
+    from .transform import ScalarTransform4f
+    radius = float(sd.get("radius", 1.0))
+    center = np.asarray(sd.get("center", [0.0, 0.0, 0.0]), dtype=np.float64).reshape(3)
+    if not radius > 0.0:
+        raise ValueError(f"{name}: the radius of a sphere must be positive (radius = {radius})")
+    m = np.asarray(tw.matrix, dtype=np.float64)
+    lin = m[:3, :3]
+    gram = lin.T @ lin
+    s2 = float(np.trace(gram)) / 3.0
+    if not s2 > 0.0 or np.abs(gram - s2 * np.eye(3)).max() > 1e-4 * s2 or np.abs(m[3] - np.array([0, 0, 0, 1.0])).max() > 0:
+        raise ValueError(f"{name}: 'to_world' contains non-uniform scaling or shear: a sphere takes a rotation, a uniform scale and a translation")
+    total = tw @ ScalarTransform4f().translate(list(center)) @ ScalarTransform4f().scale(radius)
+    c = total.transform_affine(np.zeros(3))
+    r = float(np.linalg.norm(total.transform_affine(np.array([1.0, 0.0, 0.0])) - c))
+    return c, r, total
 
 
 def _add_delta_emitter(b: "_SceneBuilder", name: str, v: Dict[str, Any], obj=None):
@@ -902,10 +943,18 @@ def load_geometry(path: str) -> Dict[str, Any]:
     if layout[1] == 84 and esize > 84:           # written with ABI <= 21: mtr_emitter grew by appended fields (kind, axis) only
         em_bytes = np.pad(em_bytes.reshape(-1, 84), ((0, 0), (0, esize - 84))).reshape(-1)
         layout[1] = esize
+    if layout[1] == 100 and esize > 100:         # written with ABI 22: mtr_emitter grew by an appended field (radius) only
+        em_bytes = np.pad(em_bytes.reshape(-1, 100), ((0, 0), (0, esize - 100))).reshape(-1)
+        layout[1] = esize
+    sh_bytes = z["shapes"]
+    ssize = C.sizeof(_cabi.mtr_shape)
+    if layout[2] == 100 and ssize > 100:         # written with ABI <= 22: mtr_shape grew by appended fields (kind, radius) only
+        sh_bytes = np.pad(sh_bytes.reshape(-1, 100), ((0, 0), (0, ssize - 100))).reshape(-1)
+        layout[2] = ssize
     if layout != [msize, C.sizeof(_cabi.mtr_emitter), C.sizeof(_cabi.mtr_shape)]:
         raise ValueError(f"{path}: material / emitter record sizes {list(z['layout'])} do not match this C-ABI; "
                          "regenerate with tests/golden/make_golden.py")
-    z = dict(z.items()); z["materials"] = mat_bytes; z["emitters"] = em_bytes
+    z = dict(z.items()); z["materials"] = mat_bytes; z["emitters"] = em_bytes; z["shapes"] = sh_bytes
     nm = z["materials"].size // C.sizeof(_cabi.mtr_material)
     ne = z["emitters"].size // C.sizeof(_cabi.mtr_emitter)
     mats = (_cabi.mtr_material * max(1, nm)).from_buffer_copy(z["materials"].tobytes().ljust(C.sizeof(_cabi.mtr_material), b"\0"))
@@ -948,6 +997,9 @@ def _check_polarized(b, film, sd):
     for e in b.emitters:
         if e.angular:
             raise ValueError(f"{v}: the angulararea emitter is not available with polarization (supported emitters: area)")
+        if e.kind == _cabi.MTR_EMITTER_SPHERE:
+            raise ValueError(f"{v}: the area emitter on a sphere is not available with polarization "
+                             f"(supported emitters: area on a rectangle or a mesh)")
         if e.kind != _cabi.MTR_EMITTER_AREA:
             raise ValueError(f"{v}: the {'point' if e.kind == _cabi.MTR_EMITTER_POINT else 'spot'} emitter is not available "
                              f"with polarization (supported emitters: area)")
@@ -965,6 +1017,8 @@ def flatten_scene(d: Dict[str, Any], film, sensor_dict: Dict[str, Any], base_dir
             continue
         t = v.get("type")
         if t in ("rectangle", "cube", "obj", "ply", "sphere", "disk", "cylinder"):
+            if t == "sphere" and name == relay_shape_name:
+                raise ValueError(f"{name}: NLOS: the relay wall must be a rectangle (a sphere cannot carry the nlos_capture_meter)")
             b.add_shape(name, v)
         elif t in _DELTA_EMITTER_TYPES:            # emitters enter the table in the dictionary's order, shapes' and top-level ones alike
             _add_delta_emitter(b, name, v, (lights or {}).get(name))
