@@ -20,6 +20,7 @@
 // atomic's return value is the record's rank), claims the bucket's next range with one global atomic per (tile, bucket),
 // and writes.
 #include "mtr_kernels.h"
+#include "mtr_splat_plan.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -29,7 +30,7 @@ namespace mtr {
 
 namespace {
 
-constexpr uint32_t kPartMaxDigits = 2048;               // LDS counters per tile (11 bits per half: films up to 2^22 pixels)
+constexpr uint32_t kPartMaxDigits = kSplatPlanMaxDigits; // LDS counters per tile (11 bits per half: films up to 2^22 pixels)
 constexpr uint32_t kDropped = 0xffffffffu;
 
 __device__ __forceinline__ unsigned long long splat_fixed(float v)
@@ -246,6 +247,7 @@ __global__ void __launch_bounds__(kBlock) k_part_hist_lo(const PartArgs a)
 // workgroup adds up the sums of the blocks before it (at most 1024 values) and scans its own 4096 entries.  (The first
 // version scanned the 2^18 entries in ONE workgroup: 0.59 ms, as long as the histogram pass over 2^28 records.)
 constexpr uint32_t kScanBlock = kBlock * 16u;
+static_assert(kScanBlock == kSplatPlanScanBlock, "mtr_splat_plan.h sizes the block sums for scan blocks of 4096 entries");
 __global__ void __launch_bounds__(kBlock) k_part_scan_lo_sums(const PartArgs a, uint32_t *block_sums)
 {
     __shared__ uint32_t s_sum[kBlock / 64];
@@ -440,46 +442,30 @@ __global__ void __launch_bounds__(kBlock) k_splat_rows_rec(const PartArgs a, flo
 
 } // namespace
 
-// Can the partition path take this call?  (record key = pixel | bin << bits_pix in 32 bits; LDS counters for either half)
-bool splat_partition_supported(const mtr_splat_soa &s, const Film &film)
+// The three readers of the plan (mtr_splat_plan.h: support rule, digit split, workspace layout)
+static SplatPlan plan_of(const mtr_splat_soa &s, const Film &film)
 {
-    const uint64_t npix = (uint64_t)film.width * film.height;
-    if (film.n_freq || s.n == 0 || s.n >= 0xffffffffull || npix < 2 || npix > (1ull << 22)) return false;
-    uint32_t bits_pix = 1; while ((1ull << bits_pix) < npix) ++bits_pix;
-    uint32_t bits_bin = 1; while ((1ull << bits_bin) < film.bins) ++bits_bin;
-    if (bits_pix + bits_bin > 32u) return false;
-    // the record key pixel | bin << bits_pix shares its value space with the sentinel kDropped = 0xffffffff: when both counts are
-    // exact powers of two that fill the 32 bits, the last pixel's last bin WOULD be that key and its contribution would vanish
-    if (bits_pix + bits_bin == 32u && (((uint64_t)(film.bins - 1u) << bits_pix) | (npix - 1u)) == 0xffffffffull) return false;
-    return (size_t)film.bins * 12u <= 150u * 1024u;             // the row must fit LDS
+    return splat_partition_plan(film.width, film.height, film.bins, film.n_freq, s.n);
 }
 
-size_t splat_partition_scratch_bytes(const mtr_splat_soa &s, const Film &film)
-{
-    const size_t npix = (size_t)film.width * film.height;
-    return 2 * (size_t)s.n * 16u + (2 * (size_t)kPartMaxDigits + 2 * npix + npix / 4096u + 128) * 4u;
-}
+// Can the partition path take this call?  (record key = pixel | bin << bits_pix in 32 bits; LDS counters for either half)
+bool splat_partition_supported(const mtr_splat_soa &s, const Film &film) { return plan_of(s, film).supported; }
+
+size_t splat_partition_scratch_bytes(const mtr_splat_soa &s, const Film &film) { return plan_of(s, film).total_bytes; }
 
 hipError_t launch_splat_partitioned(const mtr_splat_soa &s, const Film &film, float *film_out, bool film_zero, DevCounters *counters,
                                     void *scratch, int n_cu, hipStream_t stream)
 {
     PartArgs a{};
     a.s = s; a.film = film;
+    const SplatPlan plan = plan_of(s, film);
     a.npix = film.width * film.height;
-    a.bits_pix = 1; while ((1u << a.bits_pix) < a.npix) ++a.bits_pix;
-    // (an 8 + 10 bit split — fewer cursors for the first scatter's same-address claims, 64-byte runs in the second — measured
-    // the same as 9 + 9: 12.3 against 12.4 ms for 2^28; the claims are not what bounds the scatters)
-    a.bits_lo = a.bits_pix / 2u;
-    a.n_lo = 1u << a.bits_lo;
-    a.n_hi = ((a.npix - 1u) >> a.bits_lo) + 1u;
+    a.bits_pix = plan.bits_pix; a.bits_lo = plan.bits_lo; a.n_lo = plan.n_lo; a.n_hi = plan.n_hi;
     unsigned char *p = (unsigned char *)scratch;
-    a.rec_a = (uint4 *)p; p += (size_t)s.n * 16u;
-    a.rec_b = (uint4 *)p; p += (size_t)s.n * 16u;
-    a.hist_hi = (uint32_t *)p; p += (size_t)kPartMaxDigits * 4u;
-    a.base_hi = (uint32_t *)p; p += ((size_t)kPartMaxDigits + 16u) * 4u;
-    a.starts = (uint32_t *)p; p += ((size_t)a.npix + 16u) * 4u;
-    a.cur_lo = (uint32_t *)p; p += ((size_t)a.npix + 16u) * 4u;
-    uint32_t *block_sums = (uint32_t *)p;                                           // [npix / 4096 + 1]
+    a.rec_a = (uint4 *)(p + plan.rec_a); a.rec_b = (uint4 *)(p + plan.rec_b);
+    a.hist_hi = (uint32_t *)(p + plan.hist_hi); a.base_hi = (uint32_t *)(p + plan.base_hi);
+    a.starts = (uint32_t *)(p + plan.starts); a.cur_lo = (uint32_t *)(p + plan.cur_lo);
+    uint32_t *block_sums = (uint32_t *)(p + plan.block_sums);                       // [n_scan]
     hipError_t e = hipMemsetAsync(a.hist_hi, 0, (size_t)kPartMaxDigits * 4u, stream);
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(a.starts, 0, ((size_t)a.npix + 16u) * 4u, stream);
@@ -500,7 +486,7 @@ hipError_t launch_splat_partitioned(const mtr_splat_soa &s, const Film &film, fl
     // per bucket: as many workgroups as an even share of the chip (buckets of uniform input are equally long)
     const unsigned per_bucket_h = std::max(1u, (unsigned)((uint64_t)n_cu * 8u / a.n_hi));
     hipLaunchKernelGGL(k_part_hist_lo, dim3(per_bucket_h, a.n_hi), dim3(kBlock), 0, stream, a);
-    const unsigned n_scan = (a.npix + 1u + kScanBlock - 1u) / kScanBlock;            // <= 1025 (films up to 2^22 pixels)
+    const unsigned n_scan = plan.n_scan;                                             // <= 1025 (films up to 2^22 pixels)
     hipLaunchKernelGGL(k_part_scan_lo_sums, dim3(n_scan), dim3(kBlock), 0, stream, a, block_sums);
     hipLaunchKernelGGL(k_part_scan_lo, dim3(n_scan), dim3(kBlock), 0, stream, a, (const uint32_t *)block_sums);
     const unsigned per_bucket_s = std::max(1u, (unsigned)((uint64_t)n_cu * wg_cu_lo / a.n_hi));

@@ -183,9 +183,14 @@ class TransientHDRFilm:
         """pos: (n,2) pixel coordinates (incl. crop offset); distance: (n,); spec: (n,3) already
         multiplied by the sample scale.  Device torch tensors (or anything torch.as_tensor takes).
         ``variant`` (extension): 1 (default) = the library looks whether the contributions come pixel by pixel — the order
-        of the reference's own lanes, pixel * spp + s — and then adds each pixel's run through an LDS row (31 % of the HBM
-        roofline); any other order falls back, on the device, to variant 0 = one f32 atomic per channel (the contract form,
-        2 %)."""
+        of the reference's own lanes, pixel * spp + s — and then adds each pixel's run through an LDS row (about half of the
+        HBM roofline).  Any other order is PARTITIONED BY PIXEL on the device first (two scatter passes over 16-byte records,
+        then the same rows: 9 %); that costs one stream synchronisation, to read the sortedness flag back, and 32 bytes of
+        device workspace per contribution for the call (at most 256 MiB of it stays with the context afterwards).  Where the
+        partition cannot be used — a film of more than 2^22 pixels, a pixel index and row position that do not fit a 32-bit
+        record key together, a row too long for LDS (more than 12800 bins), 2^32 - 1 contributions or more, or no room for the
+        workspace — unsorted input falls back to variant 0 = one f32 atomic per channel (the contract form, 2 %).  The film
+        is the same to rounding whichever path a call takes."""
         torch = require_gpu()
         dev = self._device
         pos = torch.as_tensor(pos, dtype=torch.float32, device=dev)
