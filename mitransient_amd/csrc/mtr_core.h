@@ -1179,6 +1179,29 @@ __device__ __forceinline__ T kernarg_copy(size_t offset)
     for (size_t k = 0; k < sizeof(T) / 4; ++k) o[k] = w[k];
     return out;
 }
+// BATCHED REQUESTS (round 10; k_fused's lean kernels).  The compiler sinks every word of a kernarg_copy to its first use, so a section
+// may wait for its arguments in several scalar-load round trips, one after the other, with nothing between request and wait.
+// kernarg_pin names every word of a copy as an input of empty asm statements at ONE point: the loads are issued in front of it and
+// awaited once (scalar loads return out of order — the first s_waitcnt behind them waits for all of them anyway).  No request is
+// added; words the section never read before are loaded with the rest.  (-DMTR_BATCH=<mask>, experiments: 1 slab reads, 2 refresh.)
+#ifndef MTR_BATCH
+#define MTR_BATCH 3
+#endif
+template <size_t N>
+__device__ __forceinline__ void kernarg_pin_words(const uint32_t *o)
+{
+#define MTR_PIN_W(k) "s"(o[(k) < N ? (k) : N - 1])
+    asm volatile("" :: MTR_PIN_W(0), MTR_PIN_W(1), MTR_PIN_W(2), MTR_PIN_W(3), MTR_PIN_W(4), MTR_PIN_W(5), MTR_PIN_W(6), MTR_PIN_W(7),
+                       MTR_PIN_W(8), MTR_PIN_W(9), MTR_PIN_W(10), MTR_PIN_W(11), MTR_PIN_W(12), MTR_PIN_W(13), MTR_PIN_W(14), MTR_PIN_W(15));
+#undef MTR_PIN_W
+    if constexpr (N > 16) kernarg_pin_words<N - 16>(o + 16);
+}
+template <class T>
+__device__ __forceinline__ void kernarg_pin(const T &v)
+{
+    static_assert(sizeof(T) % 4 == 0, "dword-sized fields");
+    kernarg_pin_words<sizeof(T) / 4>((const uint32_t *)&v);
+}
 #endif
 
 // (a traversal stack type may name the form of kernarg_copy its kernel reads the flat top level with: Stack::kOneKernargBase)
@@ -1189,14 +1212,27 @@ template <class S> struct stack_one_kernarg_base<S, decltype((void)S::kOneKernar
 // One pair of children of the root against a ray: the slab tests of flat_walk_device's rectangle stage.  `p0`, `p1`: the children exist.
 // (A function of values, not a lambda over the walk's locals: a closure is memory, and see trav_quad_test for what becomes of a ray
 // that is read from memory next to a splat.)
-template <bool ANY_HIT, uint32_t J>
+// BATCH (k_fused's lean kernels, BATCHED REQUESTS): the step's six plane pairs are read into locals FIRST and only then used.  Written read by
+// read beside its fma, the compiler keeps that order — a ds_read_b64, an s_waitcnt, four instructions, six times over in the first
+// step; requested together they are awaited once per step (config 2's loop: 98 -> 87 s_waitcnt).  A pin on the six adds nothing.
+template <bool ANY_HIT, uint32_t J, bool BATCH = false>
 __device__ __forceinline__ void flat_slab_pair(const f3 id, const f3 noid, const float tb, const uint32_t sel0, const uint32_t sel1, const uint32_t sel2,
                                                const char *root, const bool p0, const bool p1, uint32_t &qm, uint32_t &key1, uint32_t &key2)
 {
     const char *pb = root + 48u * J;
-    const f2 nx = fma2<kPkSlabs>(*(const f2 *)(pb + sel0), id.x, noid.x), fx = fma2<kPkSlabs>(*(const f2 *)(pb + (sel0 ^ 8u)), id.x, noid.x);
-    const f2 ny = fma2<kPkSlabs>(*(const f2 *)(pb + sel1), id.y, noid.y), fy = fma2<kPkSlabs>(*(const f2 *)(pb + (sel1 ^ 8u)), id.y, noid.y);
-    const f2 nz = fma2<kPkSlabs>(*(const f2 *)(pb + sel2), id.z, noid.z), fz = fma2<kPkSlabs>(*(const f2 *)(pb + (sel2 ^ 8u)), id.z, noid.z);
+    f2 nx, fx, ny, fy, nz, fz;
+    if constexpr (BATCH) {
+        const f2 pnx = *(const f2 *)(pb + sel0), pfx = *(const f2 *)(pb + (sel0 ^ 8u));
+        const f2 pny = *(const f2 *)(pb + sel1), pfy = *(const f2 *)(pb + (sel1 ^ 8u));
+        const f2 pnz = *(const f2 *)(pb + sel2), pfz = *(const f2 *)(pb + (sel2 ^ 8u));
+        nx = fma2<kPkSlabs>(pnx, id.x, noid.x); fx = fma2<kPkSlabs>(pfx, id.x, noid.x);
+        ny = fma2<kPkSlabs>(pny, id.y, noid.y); fy = fma2<kPkSlabs>(pfy, id.y, noid.y);
+        nz = fma2<kPkSlabs>(pnz, id.z, noid.z); fz = fma2<kPkSlabs>(pfz, id.z, noid.z);
+    } else {
+        nx = fma2<kPkSlabs>(*(const f2 *)(pb + sel0), id.x, noid.x); fx = fma2<kPkSlabs>(*(const f2 *)(pb + (sel0 ^ 8u)), id.x, noid.x);
+        ny = fma2<kPkSlabs>(*(const f2 *)(pb + sel1), id.y, noid.y); fy = fma2<kPkSlabs>(*(const f2 *)(pb + (sel1 ^ 8u)), id.y, noid.y);
+        nz = fma2<kPkSlabs>(*(const f2 *)(pb + sel2), id.z, noid.z); fz = fma2<kPkSlabs>(*(const f2 *)(pb + (sel2 ^ 8u)), id.z, noid.z);
+    }
     const float tn0 = fmaxf(fmaxf(nx.x, ny.x), fmaxf(nz.x, 0.0f));
     const float tf0 = fminf(fminf(fx.x, fy.x), fminf(fz.x, tb));
     const float tn1 = fmaxf(fmaxf(nx.y, ny.y), fmaxf(nz.y, 0.0f));
@@ -1286,7 +1322,7 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
         uint32_t key1 = 0xffffffffu, key2 = 0xffffffffu;
         // one pair of children of the root per step; the offsets are compile-time constants (the loop is unrolled: a pair whose
         // children are absent has inverted boxes and fails by itself), a shadow ray keeps no entry distances
-#define MTR_FLAT_SLAB_PAIR(J) flat_slab_pair<ANY_HIT, J>(id, noid, tb, sel0, sel1, sel2, root, \
+#define MTR_FLAT_SLAB_PAIR(J) flat_slab_pair<ANY_HIT, J, kOneBase && (MTR_BATCH & 1) != 0>(id, noid, tb, sel0, sel1, sel2, root, \
             TOP_LEAVES ? ((fh.prim_mask >> (2u * J)) & 1u) != 0u : 2u * J < fh.n_quads, \
             TOP_LEAVES ? ((fh.prim_mask >> (2u * J + 1u)) & 1u) != 0u : 2u * J + 1u < fh.n_quads, qm, key1, key2)
         if (TOP_LEAVES) {

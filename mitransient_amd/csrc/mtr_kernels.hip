@@ -57,7 +57,10 @@ struct LdsStackT {
 #endif
 #ifdef MTR_PROFILE_CYCLES      // experiment build: wave-clock per code section (time since the previous mark)
     unsigned long long t0, cyc[6];
-#if MTR_PROFILE_CYCLES == 2     // ... the flat walk's stages in sections 0 (box selection), 5 (box faces), 2 (rectangle slabs), 4 (rectangle tests); everything else but shading in 3
+#if MTR_PROFILE_CYCLES == 3     // ... no sections: the price of ONE round trip, bracketed in `refresh` (tools/cycles_rt.py)
+    __device__ __forceinline__ void prof_mark(int) {}
+    __device__ __forceinline__ void prof_flat(int) {}
+#elif MTR_PROFILE_CYCLES == 2   // ... the flat walk's stages in sections 0 (box selection), 5 (box faces), 2 (rectangle slabs), 4 (rectangle tests); everything else but shading in 3
     __device__ __forceinline__ void prof_mark(int sec) { unsigned long long t = __builtin_readcyclecounter(); cyc[sec == 1 ? 1 : 3] += t - t0; t0 = t; }
     __device__ __forceinline__ void prof_flat(int sec) { unsigned long long t = __builtin_readcyclecounter(); cyc[sec] += t - t0; t0 = t; }
 #else
@@ -513,6 +516,32 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                 uint32_t w = xy; asm volatile("" : "+v"(w));
                 pp.px = w & 0xffffu; pp.py = w >> 16;
                 if (!NLOS) { film_l = kernarg_copy<Film, kLean>(offsetof(FusedArgs, film)); rc_l = kernarg_copy<RenderConst, kLean>(offsetof(FusedArgs, rc)); }
+                // (BATCHED REQUESTS, mtr_core.h: one group after either walk — after the shadow walk the words came in four round trips, sunk to their uses)
+                if constexpr (kLean && (MTR_BATCH & 2) != 0) { kernarg_pin(film_l); kernarg_pin(rc_l); }
+#if defined(MTR_PROFILE_CYCLES) && MTR_PROFILE_CYCLES == 3
+                // (experiment build) the wave clock around nothing, around one kernarg_copy<Film, true> awaited at once, and around one
+                // ds_read_b64 of the staged scene awaited at once.  Every bracket's FIRST clock read is awaited before anything else is
+                // issued (the clock is a scalar memory instruction itself), so a bracket is clock round trip + content + the next clock's
+                // issue, and a content's price is its bracket minus the empty one.  The LDS read goes through an address_space(3) pointer:
+                // through the generic sv.wnodes it is a flat_load, counted in vmcnt, not the instruction the loop's LDS reads are.  The
+                // assembly is the check: s_memtime / s_waitcnt / s_memtime, then s_load_* / s_waitcnt, then ds_read_b64 / s_waitcnt.
+                if constexpr (kLean) {
+                    typedef const volatile unsigned long long __attribute__((address_space(3))) *LdsWord;
+                    const unsigned long long c0 = __builtin_readcyclecounter();
+                    asm volatile("" :: "s"(c0));
+                    const unsigned long long c1 = __builtin_readcyclecounter();
+                    asm volatile("" :: "s"(c1));
+                    const Film fr = kernarg_copy<Film, true>(offsetof(FusedArgs, film)); kernarg_pin(fr);
+                    const unsigned long long c2 = __builtin_readcyclecounter();
+                    asm volatile("" :: "s"(c2));
+                    const unsigned long long c3 = __builtin_readcyclecounter();
+                    asm volatile("" :: "s"(c3));
+                    const unsigned long long w = *((LdsWord)(const char *)sv.wnodes + (tid & 1));
+                    asm volatile("" :: "v"(w));
+                    const unsigned long long c4 = __builtin_readcyclecounter();
+                    st.cyc[0] += c2 - c1; st.cyc[1] += c4 - c3; st.cyc[2] += c1 - c0; st.cyc[3] += 1ull;
+                }
+#endif
             };
             if (PHASOR && NLOS) {
                 LdsPhasorSinkNlos sink; sink.row = s_hist + slot * T;
@@ -738,9 +767,14 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     if ((tid & 63) == 0 && a.counters) {      // one lane per wave; sections: see the top of the persistent loop
         st.prof_mark(5);
         unsigned long long *c = &a.counters->splats_overflow;      // reuse 3 spare u64 slots: packed pairs of 32-bit Mcycles
+#if MTR_PROFILE_CYCLES == 3      // (round trips: clocks of the scalar bracket | of the LDS bracket | brackets << 32 + (clocks of the empty bracket) / 64:
+        // room for 2^32 brackets and 2^38 clocks of empty brackets per render — config 2 has 3.5e7 and 1.2e9)
+        atomicAdd(c + 0, st.cyc[0]); atomicAdd(c + 1, st.cyc[1]); atomicAdd(c + 2, (st.cyc[3] << 32) | ((st.cyc[2] >> 6) & 0xffffffffull));
+#else
         atomicAdd(c + 0, ((st.cyc[0] >> 10) << 32) | (st.cyc[1] >> 10));
         atomicAdd(c + 1, ((st.cyc[2] >> 10) << 32) | (st.cyc[3] >> 10));
         atomicAdd(c + 2, ((st.cyc[4] >> 10) << 32) | (st.cyc[5] >> 10));
+#endif
     }
 #endif
 }
