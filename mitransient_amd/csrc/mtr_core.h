@@ -19,10 +19,14 @@
 #ifndef MTR_WIDE
 #define MTR_WIDE 8          // children per wide node (even, <= 16)
 #endif
+#ifndef MTR_BATCH
+#define MTR_BATCH 15        // k_fused's lean kernels: which BATCHED REQUESTS are built (a mask; see kernarg_pin)
+#endif
 
 #include <stdint.h>
 #include <math.h>
 #include "../../include/mitransient_amd.h"
+#include "mtr_flat_prims.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -673,12 +677,32 @@ struct RayByValue {
     MTR_HD f3 d(const Trav &) const { return rd; }
     MTR_HD float tmax(const Trav &) const { return rtmax; }
 };
-template <class RaySrc = RayOfTrav, class Stack>
-MTR_HD bool trav_quad_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hit, const RaySrc ray = RaySrc())
+// Where a primitive test takes its intersection record from.  RecOfLeaf (every tree walker, the default; flat_walk_device where it
+// keeps the loaded references): the leaf code in tr.cur names the first slot, the record is sc.tpairs[slot / 2].  RecByValue
+// (flat_walk_device over the CHILD-ORDERED PRIMITIVE TABLE, mtr_flat_prims.h): the caller has read record and first slot already, as
+// one group of requests, and hands them over; tr.cur is not read.  A TYPE for the reason RaySrc is one: the arithmetic of a test
+// stays one body, and the tree walkers compile to what they were.
+// kPairsOnly: the record is known to be a pair of triangles — trav_leaf_test does not look for a rectangle or a sphere in the code.
+struct RecOfLeaf {
+    static constexpr bool kPairsOnly = false;
+    MTR_HD uint32_t quad_first(const Trav &tr) const { return ((~(uint32_t)tr.cur) & ~kLeafQuadBit) >> 2; }
+    MTR_HD uint32_t leaf_code(const Trav &tr) const { return ~(uint32_t)tr.cur; }
+    MTR_HD const TriPair &pair(const SceneView &sc, uint32_t slot) const { return sc.tpairs[slot >> 1]; }
+};
+struct RecByValue {
+    static constexpr bool kPairsOnly = true;
+    TriPair tp;
+    uint32_t first;
+    MTR_HD uint32_t quad_first(const Trav &) const { return first; }
+    MTR_HD uint32_t leaf_code(const Trav &) const { return (first << 2) | 1u; }       // (a cube face: both triangles of the pair)
+    MTR_HD const TriPair &pair(const SceneView &, uint32_t) const { return tp; }
+};
+template <class RaySrc = RayOfTrav, class RecSrc = RecOfLeaf, class Stack>
+MTR_HD bool trav_quad_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hit, const RaySrc ray = RaySrc(), const RecSrc rec = RecSrc())
 {
     st.count(1);
-    const uint32_t first = ((~(uint32_t)tr.cur) & ~kLeafQuadBit) >> 2;
-    const TriPair &tp = sc.tpairs[first >> 1];
+    const uint32_t first = rec.quad_first(tr);
+    const TriPair &tp = rec.pair(sc, first);
     const q4 Z = tp.g[0], X = tp.g[1], Y = tp.g[2];
     const uint32_t orig = fbits(tp.g[4].z);
     const f3 o = ray.o(tr), d = ray.d(tr);
@@ -733,12 +757,16 @@ MTR_HD bool trav_sphere_test(Trav &tr, const SceneView &sc, Stack &st, bool any_
 // pass, no loop around it
 // SPH: the tree may hold sphere leaves.  Never in a scene with kTrLeafPair (classify_scene): the walkers specialised on that trait —
 // and those a caller instantiates with SPH = false for another trait a sphere rules out (tr_spheres) — carry no sphere code
-template <bool ONE_PAIR = false, bool SPH = !ONE_PAIR, class RaySrc = RayOfTrav, class Stack>
-MTR_HD bool trav_leaf_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hit, const RaySrc ray = RaySrc())
+// RecSrc::kPairsOnly (flat_walk_device over its primitive table: a cube face, the record by value): the pair test itself, no
+// look at the code for a rectangle
+template <bool ONE_PAIR = false, bool SPH = !ONE_PAIR, class RaySrc = RayOfTrav, class RecSrc = RecOfLeaf, class Stack>
+MTR_HD bool trav_leaf_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hit, const RaySrc ray = RaySrc(), const RecSrc rec = RecSrc())
 {
-    const uint32_t code = ~(uint32_t)tr.cur;
-    if (code & kLeafQuadBit) return trav_quad_test(tr, sc, st, any_hit, ray);
-    if constexpr (SPH) { if (code & kLeafSphereBit) return trav_sphere_test(tr, sc, st, any_hit, ray); }
+    const uint32_t code = rec.leaf_code(tr);
+    if constexpr (!RecSrc::kPairsOnly) {
+        if (code & kLeafQuadBit) return trav_quad_test(tr, sc, st, any_hit, ray);
+        if constexpr (SPH) { if (code & kLeafSphereBit) return trav_sphere_test(tr, sc, st, any_hit, ray); }
+    }
     const uint32_t first = code >> 2, cnt = ONE_PAIR ? (code & 1u) + 1u : (code & 3u) + 1u;
     bool found = false;
     // Moller-Trumbore [mitsuba3: Mesh::ray_intersect_triangle]: pvec = cross(d, e2); inv_det = 1 / dot(e1, pvec);
@@ -756,7 +784,7 @@ MTR_HD bool trav_leaf_test(Trav &tr, const SceneView &sc, Stack &st, bool any_hi
         st.count(1);
         const bool two = (i + 1u) < cnt;
         const int32_t pa = (int32_t)(first + i), pb = pa + 1;
-        const TriPair &tp = sc.tpairs[(first + i) >> 1];
+        const TriPair &tp = rec.pair(sc, first + i);
         const q4 g0 = tp.g[0], g1 = tp.g[1], g2 = tp.g[2], g3 = tp.g[3], g4 = tp.g[4];
         const f2 p0x{ g0.x, g0.y }, p0y{ g0.z, g0.w }, p0z{ g1.x, g1.y };
         const f2 e1x{ g1.z, g1.w }, e1y{ g2.x, g2.y }, e1z{ g2.z, g2.w };
@@ -1183,10 +1211,11 @@ __device__ __forceinline__ T kernarg_copy(size_t offset)
 // may wait for its arguments in several scalar-load round trips, one after the other, with nothing between request and wait.
 // kernarg_pin names every word of a copy as an input of empty asm statements at ONE point: the loads are issued in front of it and
 // awaited once (scalar loads return out of order — the first s_waitcnt behind them waits for all of them anyway).  No request is
-// added; words the section never read before are loaded with the rest.  (-DMTR_BATCH=<mask>, experiments: 1 slab reads, 2 refresh.)
-#ifndef MTR_BATCH
-#define MTR_BATCH 3
-#endif
+// added; words the section never read before are loaded with the rest.  (-DMTR_BATCH=<mask>, experiments: 1 slab reads, 2 refresh,
+// 4 the flat walk's primitive table — CHILD-ORDERED PRIMITIVE TABLE, below —, 8 the surface interaction handed from shade_hit to
+// shade_finish: path_bounce.  The default is set at the head of the file: host builds read it too.)
+// (which kernels stage and read the primitive table: k_fused, flat_walk_device and fused_plan ask this one function)
+constexpr bool flat_prim_table_on(bool lean, bool top_leaves) { return lean && !top_leaves && (MTR_BATCH & 4) != 0 && kWide <= kFlatPrimQuads; }
 template <size_t N>
 __device__ __forceinline__ void kernarg_pin_words(const uint32_t *o)
 {
@@ -1247,6 +1276,24 @@ __device__ __forceinline__ void flat_slab_pair(const f3 id, const f3 noid, const
         key2 = min(key2, max(key1, kb)); key1 = min(key1, kb);
     }
 }
+// CHILD-ORDERED PRIMITIVE TABLE (round 11; mtr_flat_prims.h; MTR_BATCH & 4).  flat_walk_device knows WHICH primitive it wants as a
+// number in a register — the child index k of the slab stage, the face bit of box_select — and used to turn it into a record in
+// dependent LDS trips with nothing between request and wait: the reference WNode::ref[k], then the record (a rectangle's in two
+// groups, for `first` stands between the reads of one leaf code).  The lean kernels without top-level triangle leaves (Stack::
+// kOneKernargBase, !TOP_LEAVES) stage a copy of the records in child order in front of the tree (k_fused), with the `first` slot
+// the tests report beside them: entry, record and slot are one group of requests and one wait.  The kTrFlatLeaves kernels keep the
+// loaded references: a top-level leaf may hold more than one pair.  Nothing that is computed changes — the same records, the same tests.
+// one entry, record and first slot, read into locals FIRST (the BATCH pattern of flat_slab_pair: independent LDS reads are issued in
+// source order).  `root`: the staged tree; the table ends where it begins.
+__device__ __forceinline__ RecByValue flat_prim_fetch(const char *root, const uint32_t n_boxes, const uint32_t entry)
+{
+    const char *tab = root - flat_prim_bytes(n_boxes);
+    const TriPair *p = (const TriPair *)(tab + flat_prim_rec_off(entry));
+    RecByValue r;
+    r.tp.g[0] = p->g[0]; r.tp.g[1] = p->g[1]; r.tp.g[2] = p->g[2]; r.tp.g[3] = p->g[3]; r.tp.g[4] = p->g[4];
+    r.first = *(const uint32_t *)(tab + flat_prim_first_off(n_boxes, entry));
+    return r;
+}
 // The "walk" of a scene with a FLAT TOP LEVEL (FlatTop).  Nothing here decides a hit: rectangles are intersected by
 // trav_quad_test, cube faces by trav_leaf_test, ties go to the original index — the arithmetic of every other walker; what
 // is different is only WHICH primitives a ray is spared, and every rule that spares one is one the tree walk applies too:
@@ -1275,7 +1322,8 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
     if (!sc.n_slots) return tr.h;
     const char *root = (const char *)sc.wnodes;
     constexpr bool kOneBase = stack_one_kernarg_base<Stack>::value;
-    const FlatHdr fh = kernarg_copy<FlatHdr, kOneBase>(sc.flat_off);
+    constexpr bool kTable = flat_prim_table_on(kOneBase, TOP_LEAVES);      // CHILD-ORDERED PRIMITIVE TABLE, above
+    const FlatHdr fh =kernarg_copy<FlatHdr, kOneBase>(sc.flat_off);
     bool live = true;
     // ---- boxes: face selection per box, uniform over the wave
     uint32_t fm = 0u;
@@ -1297,10 +1345,17 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
         if (live && fm != 0u) {
             const uint32_t k = (uint32_t)__builtin_ctz(fm);
             fm &= fm - 1u;
-            const uint32_t box = (k * 43u) >> 8, face = k - 6u * box;
-            tr.cur = *(const int32_t *)(root + (size_t)(fh.node0 + box) * N::kBytes + N::kRefOff + 4u * face);
-            const bool found = trav_leaf_test<true>(tr, sc, st, ANY_HIT, ray);
-            if (ANY_HIT && found) live = false;
+            if constexpr (kTable) {
+                // (bit k = 6 box + face of box_select's mask IS the entry; a face is its two triangles and never a rectangle: the pair test itself)
+                const RecByValue rec = flat_prim_fetch(root, fh.n_boxes, kFlatPrimQuads + k);
+                const bool found = trav_leaf_test<true, false>(tr, sc, st, ANY_HIT, ray, rec);
+                if (ANY_HIT && found) live = false;
+            } else {
+                const uint32_t box = (k * 43u) >> 8, face = k - 6u * box;
+                tr.cur = *(const int32_t *)(root + (size_t)(fh.node0 + box) * N::kBytes + N::kRefOff + 4u * face);
+                const bool found = trav_leaf_test<true>(tr, sc, st, ANY_HIT, ray);
+                if (ANY_HIT && found) live = false;
+            }
         }
     }
     st.prof_flat(5);
@@ -1341,11 +1396,17 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
             if (qm != 0u) {
                 const uint32_t k = (!ANY_HIT && it == 0u) ? (key1 & 7u) : (uint32_t)__builtin_ctz(qm);
                 qm &= ~(1u << k);
-                tr.cur = *(const int32_t *)(root + N::kRefOff + 4u * k);
-                // (a rectangle or — only where the top level holds triangle leaves — a leaf of one or two pairs)
-                const bool found = (!TOP_LEAVES || is_quad_leaf(tr.cur)) ? trav_quad_test(tr, sc, st, ANY_HIT, ray)
-                                                                         : trav_leaf_test<ONE_PAIR, false>(tr, sc, st, ANY_HIT, ray);
-                if (ANY_HIT ? found : (it == 0u && tr.h.t < bitsf(key2 & ~7u))) qm = 0u;
+                if constexpr (kTable) {
+                    const RecByValue rec = flat_prim_fetch(root, fh.n_boxes, flat_prim_quad_entry(k));
+                    const bool found = trav_quad_test(tr, sc, st, ANY_HIT, ray, rec);
+                    if (ANY_HIT ? found : (it == 0u && tr.h.t < bitsf(key2 & ~7u))) qm = 0u;
+                } else {
+                    tr.cur = *(const int32_t *)(root + N::kRefOff + 4u * k);
+                    // (a rectangle or — only where the top level holds triangle leaves — a leaf of one or two pairs)
+                    const bool found = (!TOP_LEAVES || is_quad_leaf(tr.cur)) ? trav_quad_test(tr, sc, st, ANY_HIT, ray)
+                                                                             : trav_leaf_test<ONE_PAIR, false>(tr, sc, st, ANY_HIT, ray);
+                    if (ANY_HIT ? found : (it == 0u && tr.h.t < bitsf(key2 & ~7u))) qm = 0u;
+                }
             }
         }
     }
@@ -2526,8 +2587,12 @@ MTR_HD bool path_bounce(Path &p, const SceneView &sc, const Film &film, const Re
     refresh(p, sink);
     if (unwarp_here && p.depth == 0u && h.prim >= 0) p.dist = -h.t;
     // (the surface interaction handed over to shade_finish instead of rebuilt — 11 more spilled registers across the shadow walk —
-    // was measured on the flat walk in round 6: 53.4 against 53.4 ms)
-    shade_hit<ROUGH, TR>(p, h, sc, film, rc, sink, pd, shadow);
+    // was measured on the flat walk in round 6: 53.4 against 53.4 ms; round 11, MTR_BATCH & 8, the lean kernels of the flat walk
+    // without top-level leaves: HISTORY.md.  shade_hit writes `kept` for a valid hit only and shade_finish reads it for one only.)
+    // (Only under the specialised shading code, kTrCornell: the four-wave kernel of the general one pays for it with 6 spilled VGPRs.)
+    constexpr bool kHandOver = stack_one_kernarg_base<Stack>::value && flat_kind(TR) == 1 && (TR & kTrCornell) == kTrCornell && (MTR_BATCH & 8) != 0;
+    HitCtx kept;
+    shade_hit<ROUGH, TR>(p, h, sc, film, rc, sink, pd, shadow, kHandOver ? &kept : nullptr);
     st.prof_mark(1);
     bool occluded = false;
     if (pd.has_shadow) {
@@ -2538,7 +2603,7 @@ MTR_HD bool path_bounce(Path &p, const SceneView &sc, const Film &film, const Re
     st.prof_mark(0);
     if (Stack::kPark) p.rng.inc = st.unpark_inc();
     refresh(p, sink);
-    const bool an = shade_finish<ROUGH, TR>(p, h, occluded, pd, sc, film, rc, sink);
+    const bool an = shade_finish<ROUGH, TR>(p, h, occluded, pd, sc, film, rc, sink, kHandOver ? &kept : nullptr);
     if (Stack::kPark) { st.park_prev_p(p.prev_p); st.park_prev_pdf(p.prev_pdf); }
     st.prof_mark(1);
     return an;

@@ -277,6 +277,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     // v_writelane in the loop, no spilled VGPR.  The other instantiations keep the former code: they spill vector registers, and the
     // same changes moved their allocation the wrong way (more spilled VGPRs, more scratch) in most of them.
     constexpr bool kLean = SCENE_LDS && HIST_LDS && !NLOS && !PHASOR && !FIXED && !ROUGH && flat_kind(TR) != 0;
+    constexpr bool kPrimTable = flat_prim_table_on(kLean, flat_kind(TR) == 2);
 #ifdef MTR_PROFILE_TAIL
     const unsigned long long t0_wall = wall_clock64();
 #endif
@@ -294,6 +295,28 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     if (SCENE_LDS) {
         // a scene staged in LDS is walked through its 8-wide tree (fused_plan); the BVH2 packets stay in HBM, unused
         const uint32_t tree_bytes = a.sc.n_wnodes * (uint32_t)sizeof(WNode);
+        // CHILD-ORDERED PRIMITIVE TABLE (mtr_core.h, mtr_flat_prims.h): in front of the tree, where flat_prim_fetch looks for it.  Built from the
+        // scene's own arrays in HBM — the copies beside it are still being written — word by word: 20 of the record, then the first slot.
+        // Its bytes are fused_plan's (fused_prim_table_bytes); the first barrier of the chunk loop publishes it with the rest.
+        if constexpr (kPrimTable) {
+            static_assert(sizeof(TriPair) == kFlatPrimRecBytes && kFlatMaxBoxes * kFlatPrimFaces + kFlatPrimQuads <= 32u, "mtr_flat_prims.h");
+            const uint32_t nb = a.sc.flat.n_boxes, n_ent = flat_prim_entries(nb);
+            unsigned char *tab = smem + off; off += flat_prim_bytes(nb);
+            constexpr uint32_t kWords = kFlatPrimEntryBytes / 4u;
+            for (uint32_t w = tid; w < n_ent * kWords; w += kBlock) {
+                const uint32_t e = w / kWords, j = w - kWords * e;
+                const bool quad = e < kFlatPrimQuads;
+                const uint32_t b = quad ? 0u : (e - kFlatPrimQuads) / kFlatPrimFaces, f = quad ? e : (e - kFlatPrimQuads) - kFlatPrimFaces * b;
+                const uint32_t node = quad ? 0u : a.sc.flat.node0 + b;
+                uint32_t v = 0u;
+                if ((!quad || e < a.sc.flat.n_quads) && node < a.sc.n_wnodes) {
+                    const uint32_t code = ~(uint32_t)a.sc.wnodes[node].ref[f];
+                    const uint32_t first = (quad ? code & ~kLeafQuadBit : code) >> 2;      // (what trav_quad_test / trav_leaf_test make of a reference)
+                    if (first < a.sc.n_slots) v = j < kWords - 1u ? ((const uint32_t *)(a.sc.tpairs + (first >> 1)))[j] : first;
+                }
+                *(uint32_t *)(tab + (j < kWords - 1u ? flat_prim_rec_off(e) + 4u * j : flat_prim_first_off(nb, e))) = v;
+            }
+        }
         WNode *n = (WNode *)(smem + off); off += align16(tree_bytes);
         TriPair *tg = (TriPair *)(smem + off); off += align16(a.sc.n_slots / 2 * sizeof(TriPair));
         TriShade *ts = (TriShade *)(smem + off); off += align16(a.sc.n_slots * sizeof(TriShade));
@@ -795,6 +818,18 @@ uint32_t fused_chunk(uint32_t n_pixels, uint32_t spp_chunk, uint32_t grid)
     return fused_chunk_cap(chunk, spp_chunk);       // (k_fused's per-chunk counters are 32 bits wide)
 }
 
+// THE predicate of the lean flat-walk kernels without top-level triangle leaves — the instantiations that stage and read the
+// CHILD-ORDERED PRIMITIVE TABLE (mtr_core.h).  launch_fused_s picks those kernels under it and fused_plan reserves the table's bytes
+// under it: one function, because a kernel that carves a table nobody planned for overruns its LDS.
+static bool fused_lean_flat_quads(bool nlos_on, uint32_t n_freq, const FusedConfig &cfg)
+{
+    return !nlos_on && !n_freq && !cfg.rough && !cfg.fixed && cfg.scene_lds && cfg.hist_lds && (cfg.traits & kTrFlatGeneral) == kTrFlatFlags;
+}
+static uint32_t fused_prim_table_bytes(const SceneDev &sc, bool nlos_on, uint32_t n_freq, const FusedConfig &cfg)
+{
+    return flat_prim_table_on(true, false) && fused_lean_flat_quads(nlos_on, n_freq, cfg) ? flat_prim_bytes(sc.flat.n_boxes) : 0u;
+}
+
 bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t spp_chunk, int n_cu,
                 FusedArgs &args, FusedConfig &cfg)
 {
@@ -843,6 +878,8 @@ bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_
         fixed_b -= rows * kBlock * 4;
         args.stack_rows = 0u;
     }
+    // ... and the lean ones among them that hold no top-level leaves stage their primitive table in front of the tree
+    fixed_b += fused_prim_table_bytes(sc, args.nlos_on != 0u, film.n_freq, cfg);
     // ROW SLOTS AGAINST WORKGROUPS PER CU (round 6).  A workgroup is one wave per SIMD; how many are resident is bounded by LDS (rows) and by
     // registers: the kernels launch_fused_s picks hold 168 registers (three workgroups per CU: the extended shading, the fixed-point rows, the
     // NLOS loop — whose 128-register form is 18 % SLOWER at four per CU than the 168-register one at three, measured) or 128 (four).  Residency is
@@ -922,10 +959,14 @@ static hipError_t launch_fused_s(const FusedArgs &args, const FusedConfig &cfg, 
         // deterministic rows over a Cornell-class scene: the specialised shading code and the flat top level as well
         if constexpr (!NLOS) if (cfg.scene_lds && cfg.traits == kTrCornellFlat) k = k_fused<true, true, false, 3, false, true, false, kTrCornellFlat>;
     }
-    else if (!NLOS && cfg.scene_lds && cfg.hist_lds && cfg.traits == kTrCornellFlat)      // ... and a flat top level: no tree walk either (flat_walk_device)
-        k = cfg.per_cu <= 3 ? k_fused<true, true, false, 3, false, false, false, kTrCornellFlat> : k_fused<true, true, false, MTR_FUSED_MIN_WAVES, false, false, false, kTrCornellFlat>;
-    else if (!NLOS && cfg.scene_lds && cfg.hist_lds && (cfg.traits & kTrFlatGeneral) == kTrFlatFlags)    // the flat top level under the general shading code (a mirror box, two lights ...)
-        k = cfg.per_cu <= 3 ? k_fused<true, true, false, 3, false, false, false, kTrFlatFlags> : k_fused<true, true, false, MTR_FUSED_MIN_WAVES, false, false, false, kTrFlatFlags>;
+    else if (fused_lean_flat_quads(NLOS, 0u, cfg)) {      // (the kernels with the primitive table: fused_plan has reserved it under this very predicate)
+        if constexpr (!NLOS) {
+            if (cfg.traits == kTrCornellFlat)      // ... and a flat top level: no tree walk either (flat_walk_device)
+                k = cfg.per_cu <= 3 ? k_fused<true, true, false, 3, false, false, false, kTrCornellFlat> : k_fused<true, true, false, MTR_FUSED_MIN_WAVES, false, false, false, kTrCornellFlat>;
+            else                                   // the flat top level under the general shading code (a mirror box, two lights ...)
+                k = cfg.per_cu <= 3 ? k_fused<true, true, false, 3, false, false, false, kTrFlatFlags> : k_fused<true, true, false, MTR_FUSED_MIN_WAVES, false, false, false, kTrFlatFlags>;
+        }
+    }
     else if (!NLOS && cfg.scene_lds && cfg.hist_lds && (cfg.traits & kTrFlatGeneral) == kTrFlatGeneral)  // ... with triangle leaves among the top level's children
         k = cfg.per_cu <= 3 ? k_fused<true, true, false, 3, false, false, false, kTrFlatGeneral> : k_fused<true, true, false, MTR_FUSED_MIN_WAVES, false, false, false, kTrFlatGeneral>;
     else if (!NLOS && cfg.scene_lds && cfg.hist_lds && (cfg.traits & kTrCornell) == kTrCornell)          // diffuse materials, one rectangle emitter: the specialised shading code
