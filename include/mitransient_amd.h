@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MTR_ABI_VERSION 23
+#define MTR_ABI_VERSION 24
 
 typedef enum mtr_status {
     MTR_OK = 0,
@@ -311,8 +311,21 @@ enum { MTR_FLAG_CAMERA_UNWARP = 1u,        /* common.py:25, transientpath.py:133
 /* which kernel organisation executes the path */
 enum { MTR_MODE_AUTO = 0,
        MTR_MODE_FUSED = 1,      /* one persistent launch per tile; per-pixel LDS time histogram */
-       MTR_MODE_WAVEFRONT = 2   /* per-bounce launches over SoA path queues in HBM + splat
-                                   records + the stand-alone time-bin scatter-add kernel        */ };
+       MTR_MODE_WAVEFRONT = 2,  /* per-bounce launches over SoA path queues in HBM + splat
+                                   records + the stand-alone time-bin scatter-add kernel        */
+       MTR_MODE_SAMPLES = 3     /* (ABI 24) a pixel's samples spread over workgroups: work item = (pixel, slab of the call's samples),
+                                   one LDS row per workgroup, the slabs' rows summed by a second kernel in slab order.  For films of
+                                   one or a few pixels with very many samples (a `radiancemeter`, a SPAD array), which the two
+                                   organisations above — a whole pixel per workgroup — leave on a handful of workgroups.  On request
+                                   only: MTR_MODE_AUTO never resolves to it.  transient_path into a plain transient_hdr_film with f32
+                                   rows; honours sample and pixel sub-ranges, spp_scale, crop windows, MTR_FLAG_CAMERA_UNWARP,
+                                   _DISCARD_DIRECT_LIGHT, _FILM_ZERO, _KEEP_COUNTERS and the seeding flags.  MTR_ERR_UNSUPPORTED,
+                                   before any launch and with both tensors untouched: the NLOS tier, a phasor film, an
+                                   exhaustive_scan film, MTR_FLAG_POLARIZED, MTR_FLAG_DETERMINISTIC, MTR_FLAG_DEVELOPED_ROWS, band
+                                   words, and a time-bin row that with the traversal stack (and the scene, when even the HBM walk
+                                   leaves no room) exceeds 160 KiB of LDS.  The splat log is not written.  The slabs' rows live in a
+                                   context-owned workspace ((pixels, slabs, 3 T + 4) f32; above 256 MiB released by the call,
+                                   otherwise by mtr_ctx_trim).                                                              */ };
 
 typedef struct mtr_render_params {
     uint32_t spp_total;     /* samples per pixel of the WHOLE render: sample_scale = 1/spp_total
@@ -400,6 +413,10 @@ void mtr_scene_destroy(mtr_scene *);
 /* transient_hdr_film traverse()/parameters_changed (transient_hdr_film.py:295-311):
  * change T / start / width between renders. */
 int  mtr_scene_set_film(mtr_scene *, const mtr_film_desc *);
+/* (ABI 24) Replace the sensor: the next render's camera rays come from `camera`; nothing else is rebuilt (a scanned
+ * `radiancemeter` is a loop over this call and mtr_render).  Renders already enqueued keep the camera they were launched with.
+ * MTR_ERR_UNSUPPORTED for a scene with the NLOS tier, whose tables are derived from the sensor (mtr_scene_set_nlos). */
+int  mtr_scene_set_camera(mtr_scene *, const mtr_camera *);
 /* NLOS tier: (re)derive the laser / relay-wall / hidden-geometry tables and the scanned points
  * (TransientNLOSPath.prepare, transientnlospath.py:251-383) after mitransient.nlos.focus_emitter_*
  * (nlos.py:5-70) or an integrator property changed.  The shape table must match the scene's triangles. */
@@ -473,11 +490,18 @@ int  mtr_render(mtr_scene *, const mtr_render_params *,
                 mtr_counters *counters_out /*host*/, mtr_kernel_times *times_out /*host*/);
 
 /* Which kernel organisation mtr_render would run for these parameters on this scene (MTR_MODE_AUTO resolved exactly as
- * mtr_render resolves it; MTR_MODE_FUSED or MTR_MODE_WAVEFRONT in *mode_out).  A caller that overlaps several mtr_render
+ * mtr_render resolves it; MTR_MODE_FUSED or MTR_MODE_WAVEFRONT in *mode_out; (ABI 24) MTR_MODE_SAMPLES for MTR_MODE_SAMPLES, or
+ * its refusal).  A caller that overlaps several mtr_render
  * calls of ONE scene on different streams needs this: only the fused organisation keeps its per-launch state apart
  * (rotating work tickets); the wavefront organisation has one workspace per scene and must stay on one stream. */
 int  mtr_render_plan(mtr_scene *, const mtr_render_params *, uint32_t *mode_out,
                      uint32_t *developed_rows_ok /* may be NULL: 1 when MTR_FLAG_DEVELOPED_ROWS would be honoured */);
+/* (ABI 24) What MTR_MODE_SAMPLES would run for these parameters (params.mode is not read): samples per slab, slabs per pixel
+ * (the last one ragged; never more slabs than samples), whether the scene is staged in LDS (0: walked in HBM) and whether the
+ * extended shading code runs — together the instantiation of the path kernel.  Any pointer may be NULL.  Refuses what
+ * mtr_render refuses in that mode. */
+int  mtr_render_samples_plan(mtr_scene *, const mtr_render_params *, uint32_t *slab_len, uint32_t *n_slabs,
+                             uint32_t *scene_in_lds, uint32_t *extended);
 
 /* (ABI 15) Reverse-mode gradients of transient_path: TransientADIntegrator.render_backward (common.py:325-409) with
  * TransientPath.sample's backward pass (transientpath.py:88-326, :284-299).  For the lanes of `params` (the same lanes, seeds
@@ -604,7 +628,7 @@ int  mtr_splat_add(mtr_ctx *, const mtr_splat_soa *, const mtr_film_desc *, int 
 
 /* Release the device workspaces the context keeps between calls (ABI 10: the partition workspace of mtr_splat_add on
  * unsorted input — 32 bytes per contribution; a workspace above 256 MiB is released by the call itself, a smaller one
- * stays with the context).  Synchronises the context's stream. */
+ * stays with the context; ABI 24: the slabs' rows of MTR_MODE_SAMPLES, under the same rule).  Synchronises the context's stream. */
 int  mtr_ctx_trim(mtr_ctx *);
 
 /* Debug/test aid: per-lane splat log of one render (records of 8 x u32:

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MITRANSIENT_AMD_LIB") or os.path.join(_HERE, "csrc", "libmitransient_amd.so")   # env override: kernel A/B experiments
 
-MTR_ABI_VERSION = 23
+MTR_ABI_VERSION = 24
 MTR_TRAIT_DIFFUSE, MTR_TRAIT_ONE_RECT_EMITTER, MTR_TRAIT_LEAF_PAIR, MTR_TRAIT_FLAT_TOP, MTR_TRAIT_FLAT_LEAVES, MTR_TRAIT_NO_LOBES, MTR_TRAIT_GREY = 1, 2, 4, 8, 16, 32, 64      # mtr_scene_traits
 MTR_SPLAT_FILM_ZERO = 0x100      # mtr_splat_add: OR into `variant` when the film is all-zero on entry
 
@@ -28,7 +28,7 @@ MTR_FLAG_KEEP_COUNTERS = 16
 MTR_FLAG_DETERMINISTIC = 32
 MTR_FLAG_DEVELOPED_ROWS = 64
 MTR_FLAG_POLARIZED = 256           # (ABI 14) the *_mono_polarized variants: Stokes film (H, W, T, 4), S0 steady
-MTR_MODE_AUTO, MTR_MODE_FUSED, MTR_MODE_WAVEFRONT = 0, 1, 2
+MTR_MODE_AUTO, MTR_MODE_FUSED, MTR_MODE_WAVEFRONT, MTR_MODE_SAMPLES = 0, 1, 2, 3      # (SAMPLES: ABI 24)
 MTR_RECT_ANALYTIC, MTR_RECT_FLIP_NORMALS = 1, 2
 MTR_EMITTER_AREA, MTR_EMITTER_POINT, MTR_EMITTER_SPOT, MTR_EMITTER_SPHERE = 0, 1, 2, 3      # mtr_emitter.kind (ABI 22; the sphere light: ABI 23)
 MTR_SHAPE_DEFAULT, MTR_SHAPE_SPHERE, MTR_SHAPE_FLIP_NORMALS = 0, 1, 0x100      # mtr_shape.kind (ABI 23)
@@ -165,6 +165,7 @@ EXPORTS = [
     "mtr_render_grad_tex", "mtr_render_grad_tex_tier", "mtr_scene_set_texture", "mtr_scene_texture_layout",
     "mtr_render_fwd", "mtr_render_fwd_tier",
     "mtr_scene_tint_layout", "mtr_scene_set_tints", "mtr_render_grad_tint", "mtr_render_fwd_tint",
+    "mtr_scene_set_camera", "mtr_render_samples_plan",
 ]
 
 _lib = None
@@ -226,6 +227,8 @@ def load_library() -> C.CDLL:
     lib.mtr_scene_set_tints.argtypes = [vp, vp, vp]
     lib.mtr_render_grad_tint.argtypes = [vp, C.POINTER(mtr_render_params), vp, vp, vp, vp, vp, vp]
     lib.mtr_render_fwd_tint.argtypes = [vp, C.POINTER(mtr_render_params), vp, vp, vp, vp, vp, vp]
+    lib.mtr_scene_set_camera.argtypes = [vp, C.POINTER(mtr_camera)]      # (ABI 24)
+    lib.mtr_render_samples_plan.argtypes = [vp, C.POINTER(mtr_render_params)] + [C.POINTER(C.c_uint32)] * 4
     if lib.mtr_abi_version() != MTR_ABI_VERSION:
         raise MitransientAMDError("libmitransient_amd.so ABI version mismatch; rebuild")
     _lib = lib

@@ -12,6 +12,7 @@
 #include "mtr_grad.h"
 #include "mtr_fwd_args.h"
 #include "mtr_tint_args.h"
+#include "mtr_samples_args.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -40,6 +41,7 @@ struct mtr_ctx {
     void *d_runs = nullptr; size_t runs_cap = 0;         // mtr_splat_add variant 1: sortedness flag + run table
     uint32_t *d_band_count = nullptr; size_t band_cap = 0;       // mtr_render_params.n_bands: flushed pixels per band of the launch in flight
     void *d_part = nullptr; size_t part_cap = 0;         // ... and the partition workspace of unsorted input (at most 256 MiB of it kept between calls, until mtr_ctx_trim / destroy)
+    void *d_samples = nullptr; size_t samples_cap = 0;   // MTR_MODE_SAMPLES: the slabs' rows (at most 256 MiB kept between calls, until mtr_ctx_trim / destroy)
 };
 
 struct WfWorkspace {            // MTR_MODE_WAVEFRONT buffers, sized for one tile, reused across renders
@@ -141,7 +143,7 @@ void mtr_ctx_destroy(mtr_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (void *p : { (void *)c->d_counters, (void *)c->d_ticket, (void *)c->d_freq, c->d_runs, c->d_part, (void *)c->d_band_count }) if (p) (void)hipFree(p);
+    for (void *p : { (void *)c->d_counters, (void *)c->d_ticket, (void *)c->d_freq, c->d_runs, c->d_part, c->d_samples, (void *)c->d_band_count }) if (p) (void)hipFree(p);
     for (hipEvent_t e : { c->ev0, c->ev1, c->ev2, c->ev3 }) if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -794,6 +796,26 @@ static int resolve_mode(mtr_scene *s, const mtr_render_params *p, uint32_t n_pix
     return MTR_OK;
 }
 
+// MTR_MODE_SAMPLES (mtr_samples.hip): what it refuses — before any launch, both tensors untouched — and its plan
+static int samples_check(mtr_scene *s, const mtr_render_params *p, uint32_t n_pixels, uint32_t spp_chunk, SamplesPlan *pl)
+{
+    mtr_ctx *c = s->ctx;
+    const Film &f = s->film;
+    const char *why = nullptr;
+    if (s->nlos.on) why = "the NLOS tier";
+    else if (f.n_freq) why = "a phasor_hdr_film";
+    else if (f.lasers > 1u) why = "an exhaustive_scan film";
+    else if (p->flags & MTR_FLAG_POLARIZED) why = "polarized transport (MTR_FLAG_POLARIZED)";
+    else if (p->flags & MTR_FLAG_DETERMINISTIC) why = "deterministic rows (MTR_FLAG_DETERMINISTIC)";
+    else if (p->flags & MTR_FLAG_DEVELOPED_ROWS) why = "MTR_FLAG_DEVELOPED_ROWS";
+    else if (p->n_bands) why = "band completion words";
+    if (why) return fail(c, MTR_ERR_UNSUPPORTED, std::string("mtr_render: MTR_MODE_SAMPLES renders transient_path into a plain transient_hdr_film with f32 rows: not ") + why);
+    SamplesPlan local;
+    if (n_pixels && spp_chunk && !samples_plan(s->dev, f, n_pixels, spp_chunk, usable_cus(c, p), pl ? *pl : local))
+        return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: MTR_MODE_SAMPLES: the time-bin row, the traversal stack and the scene exceed the 160 KiB of LDS");
+    return MTR_OK;
+}
+
 // the ranges of mtr_render_params that every render entry point checks; `who` prefixes the message, `advice` ends the lane-count one
 static int check_render_ranges(mtr_ctx *c, const Film &f, const mtr_render_params *p, const char *who, const char *advice)
 {
@@ -851,7 +873,10 @@ int mtr_render(mtr_scene *s, const mtr_render_params *p, float *t4, float *s4,
     mtr_ctx *c = s->ctx;
     const Film &f = s->film;
     if (int r = check_render_ranges(c, f, p, "mtr_render", "shard the render")) return r;
-    if (p->mode > MTR_MODE_WAVEFRONT) return fail(c, MTR_ERR_INVALID, "mtr_render: unknown mode");
+    if (p->mode > MTR_MODE_SAMPLES) return fail(c, MTR_ERR_INVALID, "mtr_render: unknown mode");
+    SamplesPlan spl{};
+    if (p->mode == MTR_MODE_SAMPLES)
+        if (int r = samples_check(s, p, p->pixel_end - p->pixel_begin, p->spp_end - p->spp_begin, &spl)) return r;
     HIP_TRY(c, hipSetDevice(c->device));
 
     FusedArgs a{};
@@ -875,7 +900,23 @@ int mtr_render(mtr_scene *s, const mtr_render_params *p, float *t4, float *s4,
     if (s->log.count) HIP_TRY(c, hipMemsetAsync(s->log.count, 0, sizeof(unsigned long long), c->stream));
     if (times_out) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
     RenderStats st;
-    if (n_pixels && a.spp_chunk) {
+    if (n_pixels && a.spp_chunk && p->mode == MTR_MODE_SAMPLES) {
+        // the slabs' rows: context-owned, like the partition workspace of mtr_splat_add (kept up to 256 MiB between calls)
+        constexpr size_t kSamplesRetain = (size_t)256 << 20;
+        if (int r = grow_device_buffer(c, &c->d_samples, &c->samples_cap, spl.partial_bytes)) return r;
+        SamplesArgs sa{};
+        sa.sc = s->dev; sa.cam = s->cam; sa.film = f; sa.rc = a.rc;
+        sa.pixel_begin = p->pixel_begin; sa.n_pixels = n_pixels; sa.spp_begin = p->spp_begin; sa.spp_chunk = a.spp_chunk;
+        sa.film_zero = (p->flags & MTR_FLAG_FILM_ZERO) ? 1u : 0u;
+        sa.partial = (float *)c->d_samples; sa.film_out = t4; sa.steady_out = s4; sa.counters = c->d_counters;
+        HIP_TRY(c, launch_samples(sa, spl, c->stream));
+        st.launches = 2;
+        if (c->samples_cap > kSamplesRetain) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            (void)hipFree(c->d_samples);
+            c->d_samples = nullptr; c->samples_cap = 0;
+        }
+    } else if (n_pixels && a.spp_chunk) {
         uint32_t mode = p->mode, dev_ok = 0u;
         if (int r = resolve_mode(s, p, n_pixels, a.spp_chunk, &mode, &dev_ok)) return r;
         if ((p->flags & MTR_FLAG_DEVELOPED_ROWS) && !dev_ok)
@@ -921,8 +962,14 @@ int mtr_render(mtr_scene *s, const mtr_render_params *p, float *t4, float *s4,
 int mtr_render_plan(mtr_scene *s, const mtr_render_params *p, uint32_t *mode_out, uint32_t *developed_rows_ok)
 {
     if (!s || !p || !mode_out) return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_render_plan: NULL argument");
-    if (p->mode > MTR_MODE_WAVEFRONT) return fail(s->ctx, MTR_ERR_INVALID, "mtr_render_plan: unknown mode");
+    if (p->mode > MTR_MODE_SAMPLES) return fail(s->ctx, MTR_ERR_INVALID, "mtr_render_plan: unknown mode");
     if (p->pixel_begin > p->pixel_end || p->spp_begin > p->spp_end) return fail(s->ctx, MTR_ERR_INVALID, "mtr_render_plan: bad range");
+    if (p->mode == MTR_MODE_SAMPLES) {           // on request only: MTR_MODE_AUTO never resolves to it
+        if (int r = samples_check(s, p, p->pixel_end - p->pixel_begin, p->spp_end - p->spp_begin, nullptr)) return r;
+        *mode_out = MTR_MODE_SAMPLES;
+        if (developed_rows_ok) *developed_rows_ok = 0u;
+        return MTR_OK;
+    }
     uint32_t mode = p->mode;
     if (int r = resolve_mode(s, p, p->pixel_end - p->pixel_begin, p->spp_end - p->spp_begin, &mode, developed_rows_ok)) return r;
     *mode_out = mode;
@@ -1249,6 +1296,32 @@ int mtr_ctx_trim(mtr_ctx *c)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->d_part) (void)hipFree(c->d_part);
     c->d_part = nullptr; c->part_cap = 0;
+    if (c->d_samples) (void)hipFree(c->d_samples);
+    c->d_samples = nullptr; c->samples_cap = 0;
+    return MTR_OK;
+}
+
+int mtr_render_samples_plan(mtr_scene *s, const mtr_render_params *p, uint32_t *slab_len, uint32_t *n_slabs, uint32_t *scene_in_lds, uint32_t *extended)
+{
+    if (!s || !p) return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_render_samples_plan: NULL argument");
+    if (p->pixel_begin > p->pixel_end || p->spp_begin > p->spp_end) return fail(s->ctx, MTR_ERR_INVALID, "mtr_render_samples_plan: bad range");
+    SamplesPlan pl{};
+    if (int r = samples_check(s, p, p->pixel_end - p->pixel_begin, p->spp_end - p->spp_begin, &pl)) return r;
+    if (slab_len) *slab_len = pl.slab_len;
+    if (n_slabs) *n_slabs = pl.n_slabs;
+    if (scene_in_lds) *scene_in_lds = pl.scene_lds ? 1u : 0u;
+    if (extended) *extended = s->dev.has_rough ? 1u : 0u;
+    return MTR_OK;
+}
+
+int mtr_scene_set_camera(mtr_scene *s, const mtr_camera *cam)
+{
+    if (!s || !cam) return fail(s ? s->ctx : nullptr, MTR_ERR_INVALID, "mtr_scene_set_camera: NULL argument");
+    mtr_ctx *c = s->ctx;
+    if (s->nlos.on) return fail(c, MTR_ERR_UNSUPPORTED, "mtr_scene_set_camera: not for the NLOS tier (its tables are derived from the sensor: mtr_scene_set_nlos)");
+    memcpy(s->cam.s2c, cam->sample_to_camera, sizeof s->cam.s2c);
+    memcpy(s->cam.tw, cam->to_world, sizeof s->cam.tw);
+    s->cam.near_clip = cam->near_clip; s->cam.far_clip = cam->far_clip;
     return MTR_OK;
 }
 

@@ -44,6 +44,14 @@ class _Seed:
         self.shape = tuple(shape)
 
 
+_MODES = {"auto": _cabi.MTR_MODE_AUTO, "fused": _cabi.MTR_MODE_FUSED, "wavefront": _cabi.MTR_MODE_WAVEFRONT,
+          "samples": _cabi.MTR_MODE_SAMPLES}
+
+# A scene whose sensor is a `radiancemeter` renders in the sample-parallel organisation when amd_mode is unset and the library's
+# plan accepts the render (MTR_MODE_AUTO otherwise).  DESIGN.md §6 has the measurement this rests on.
+RADIANCEMETER_DEFAULTS_TO_SAMPLES = True
+
+
 class TransientADIntegrator:
     def __init__(self, props: Properties):
         # [mitsuba3: ADIntegrator.__init__] max_depth default 6 (-1 = infinite), rr_depth default 5
@@ -81,7 +89,7 @@ class TransientADIntegrator:
         self.mode = _cabi.MTR_MODE_AUTO            # kernel organisation (extension; not a reference key)
         m = props.get("amd_mode", None)
         if m is not None:
-            self.mode = {"auto": 0, "fused": 1, "wavefront": 2}[m]
+            self.mode = _MODES[m]
         self.max_wavefront_size = 2 ** 32          # common.py:51: lanes of one pass
         self.pass_wavefront_size = 2 ** 26 - 1     # common.py:60: lanes per pass once the render is split
         self.last_counters = None      # counters / kernel times of the last mtr_render call ...
@@ -92,12 +100,13 @@ class TransientADIntegrator:
 
     @property
     def amd_mode(self):
-        """kernel organisation (extension): "auto" | "fused" | "wavefront" """
-        return {0: "auto", 1: "fused", 2: "wavefront"}[int(self.mode)]
+        """kernel organisation (extension): "auto" | "fused" | "wavefront" | "samples" (a pixel's samples spread over workgroups:
+        films of one or a few pixels with very many samples; transient_path, plain transient_hdr_film)"""
+        return {v: k for k, v in _MODES.items()}[int(self.mode)]
 
     @amd_mode.setter
     def amd_mode(self, m):
-        self.mode = {"auto": 0, "fused": 1, "wavefront": 2}[m]
+        self.mode = _MODES[m]
 
     def aov_names(self):
         return []
@@ -155,6 +164,14 @@ class TransientADIntegrator:
             sensor = scene.sensors()[sensor]
         if not isinstance(sensor.film(), TransientHDRFilm):
             raise AssertionError("The film of the sensor must be of type transient_hdr_film or phasor_hdr_film")
+        from ..sensors import RadianceMeter
+        if isinstance(sensor, RadianceMeter) and variant.is_polarized():
+            raise ValueError(f"{variant.get()}: a radiancemeter renders with the unpolarized variants only")
+
+    def _samples_by_default(self, sensor):
+        """amd_mode unset and the sensor a radiancemeter: ask the plan for the sample-parallel organisation first"""
+        from ..sensors import RadianceMeter
+        return RADIANCEMETER_DEFAULTS_TO_SAMPLES and int(self.mode) == _cabi.MTR_MODE_AUTO and isinstance(sensor, RadianceMeter)
 
     def add_transient_f(self, film, pos, ray_weight, sample_scale):
         """common.py:411-422: closure that pre-multiplies the sample scale and splats."""
@@ -219,6 +236,8 @@ class TransientADIntegrator:
         film = sensor.film()
         if not self.direct_develop or type(film) is not TransientHDRFilm:
             return False
+        if int(self.mode) == _cabi.MTR_MODE_SAMPLES or self._samples_by_default(sensor):
+            return False                                    # the slabs' rows are ADDED into the raw block
         if tuple(film.crop_size()) != tuple(film.size()) or tuple(film.crop_offset()) != (0, 0):
             return False                                    # rows outside the crop window would never be written
         spp = spp if spp != 0 else sensor.sampler().sample_count()
@@ -271,6 +290,10 @@ class TransientADIntegrator:
             elif film.film_is_zero or (rows_are_zero and i == 0):
                 params.flags |= _cabi.MTR_FLAG_FILM_ZERO      # first pass after clear(): row flushes may store
             film.film_is_zero = False
+            if bands is None and direct is None and self._samples_by_default(sensor):
+                params.mode = _cabi.MTR_MODE_SAMPLES          # ... when the plan accepts it (a refusal: MTR_MODE_AUTO as before)
+                if ctx.lib.mtr_render_plan(handle, C.byref(params), C.byref(C.c_uint32(0)), None) != 0:
+                    params.mode = _cabi.MTR_MODE_AUTO
             stats_now = self.collect_stats and defer_stats is None
             if defer_stats == "more" or (defer_stats == "first" and i > 0):
                 params.flags |= _cabi.MTR_FLAG_KEEP_COUNTERS
@@ -298,6 +321,8 @@ class TransientADIntegrator:
         film = sensor.film()
         if not self.direct_develop or type(film) is not TransientHDRFilm:
             return False
+        if int(self.mode) == _cabi.MTR_MODE_SAMPLES or self._samples_by_default(sensor):
+            return False
         if tuple(film.crop_size()) != tuple(film.size()) or tuple(film.crop_offset()) != (0, 0):
             return False
         W, H = film.size()
@@ -313,7 +338,8 @@ class TransientADIntegrator:
         return bool(ok.value)
 
     def resolved_mode(self, scene, sensor, total_spp, spp_range=None, pixel_range=None):
-        """the kernel organisation mtr_render would run (MTR_MODE_AUTO resolved by the library): "fused" | "wavefront".
+        """the kernel organisation mtr_render would run (MTR_MODE_AUTO resolved by the library): "fused" | "wavefront"
+        ("samples" on request, or by default for a radiancemeter).
         Callers that overlap several calls of one render on different streams need it: only the fused organisation
         keeps its per-launch state apart."""
         film = sensor.film()
@@ -323,8 +349,13 @@ class TransientADIntegrator:
         p0, p1 = (0, None) if pixel_range is None else pixel_range
         params = self.render_params(film, 0, total_spp, s0, s1, p0, p1)
         mode = C.c_uint32(0)
+        if self._samples_by_default(sensor):
+            params.mode = _cabi.MTR_MODE_SAMPLES
+            if ctx.lib.mtr_render_plan(handle, C.byref(params), C.byref(mode), None) == 0:
+                return "samples"
+            params.mode = _cabi.MTR_MODE_AUTO
         ctx.check(ctx.lib.mtr_render_plan(handle, C.byref(params), C.byref(mode), None), "mtr_render_plan")
-        return {_cabi.MTR_MODE_FUSED: "fused", _cabi.MTR_MODE_WAVEFRONT: "wavefront"}[int(mode.value)]
+        return {v: k for k, v in _MODES.items()}[int(mode.value)]
 
     def reset_counters(self, film):
         """zero the device counters on the CURRENT stream (then every call of the render passes defer_stats="more")"""

@@ -17,7 +17,7 @@ from typing import Any, Dict
 from . import _cabi, plugins
 from . import variant as _variant_mod
 from .scene import Properties, flatten_scene, film_desc_from
-from .sensors import IndependentSampler, PerspectiveSensor
+from .sensors import IndependentSampler, PerspectiveSensor, RadianceMeter
 from .transform import ScalarTransform4f
 from .tensor import TensorXf
 
@@ -112,13 +112,15 @@ def _make_sensor(sd, shape_obj=None):
     sampler = IndependentSampler(Properties("independent", smp))
     if sd["type"] == "perspective":
         return PerspectiveSensor(sd, film, sampler)
+    if sd["type"] == "radiancemeter":
+        return RadianceMeter(sd, film, sampler)
     if sd["type"] == "nlos_capture_meter":
         from .sensors.nloscapturemeter import NLOSCaptureMeter
         s = NLOSCaptureMeter(Properties("nlos_capture_meter", sd), film, sampler)
         s.dict_, s.shape_ = sd, shape_obj
         return s
     raise ValueError(f"failed to instantiate unknown plugin of type \"{sd['type']}\" "
-                     "(supported sensors: perspective, nlos_capture_meter)")
+                     "(supported sensors: perspective, radiancemeter, nlos_capture_meter)")
 
 
 def _load_shape(d):
@@ -198,8 +200,13 @@ class Scene:
             raise ValueError(f"transient_nlos_path: a {next(iter(self.lights_.values())).KIND} emitter cannot light a NLOS scene "
                              "(one projector is required)")
         for k, v in flat.items():
-            if isinstance(v, dict) and v.get("type") == "perspective":
+            if isinstance(v, dict) and v.get("type") in ("perspective", "radiancemeter"):
                 self.sensors_.append(_make_sensor(v))
+            elif isinstance(v, RadianceMeter):                                     # loaded on its own: mi.load_dict(radiancemeter)
+                self.sensors_.append(v)
+        if isinstance(self.integrator_, TransientNLOSPath) and any(isinstance(s, RadianceMeter) for s in self.sensors_):
+            raise ValueError("transient_nlos_path: a radiancemeter cannot capture a NLOS scene (use transient_path, or a "
+                             "nlos_capture_meter / perspective sensor)")
         self.relay_names_ = {}
         for k, sh in self.shape_objs_.items():
             if sh.sensor() is not None:
@@ -237,7 +244,20 @@ class Scene:
         key = id(sensor)
         # (... or a point / spot emitter did: its position, to_world or angles)
         ver = (getattr(sensor, "version_", 0), sum(getattr(l, "version_", 0) for l in self.lights_.values()))
-        if key in self._data and self._data_ver.get(key, (0, 0)) != ver:      # the camera moved (params["sensor.to_world"]): re-flatten
+        if isinstance(sensor, RadianceMeter) and _variant_mod.is_polarized():
+            raise ValueError(f"{_variant_mod.get()}: a radiancemeter renders with the unpolarized variants only")
+        old = self._data_ver.get(key, (0, 0))
+        if key in self._data and old != ver and old[1] == ver[1] and isinstance(sensor, RadianceMeter):
+            # a radiancemeter moved (a scan: params["sensor.to_world"] in a loop): the camera record alone is flattened again and
+            # handed to the device scenes (mtr_scene_set_camera) — geometry, tables and BVH stay
+            from .scene import flatten_radiancemeter
+            flatten_radiancemeter(self._data[key], sensor.dict_)
+            lib = _cabi.load_library() if any(h[0] == key for h in self._handles) else None
+            for hkey in [h for h in self._handles if h[0] == key]:
+                if lib.mtr_scene_set_camera(self._handles[hkey], C.byref(self._data[key].camera)) != 0:
+                    lib.mtr_scene_destroy(self._handles.pop(hkey))
+                    self._nlos_fp.pop(hkey, None)
+        elif key in self._data and old != ver:      # the camera moved (params["sensor.to_world"]): re-flatten
             del self._data[key]
             self._drop_handles(key)
         self._data_ver[key] = ver
@@ -517,7 +537,7 @@ def load_dict(d: Dict[str, Any], base_dir: str = ".", approximate_materials: boo
     from . import integrators as _i, films as _f  # noqa: F401  (registers the plugins)
     if str(t).endswith("_film"):                                # stand-alone plugins, as 1-simple-nlos-scenes.ipynb builds them
         return plugins.create_film(t, Properties(t, d))
-    if t in ("nlos_capture_meter", "perspective"):
+    if t in ("nlos_capture_meter", "perspective", "radiancemeter"):
         return _make_sensor(d)
     if str(t).startswith("transient"):
         return plugins.create_integrator(t, Properties(t, d))
@@ -621,7 +641,8 @@ class _Params(dict):
 
 def traverse(obj):
     """``mi.traverse`` for the film parameters the reference exports (transient_hdr_film.py:295-308) and a perspective
-    sensor's ``to_world`` (settable: ``update()`` re-flattens the camera)."""
+    sensor's or a radiancemeter's ``to_world`` (settable: ``update()`` re-flattens the camera; a radiancemeter's scene stays on
+    the device)."""
     objs = {}
 
     class _CB:

@@ -811,6 +811,17 @@ def perspective_matrices(sd: Dict[str, Any], film_size, crop_size, crop_offset):
     return sample_to_camera.matrix, to_world.matrix, near, far
 
 
+def flatten_radiancemeter(sd, sensor_dict):
+    """the camera record of a ``radiancemeter`` (sensors.radiancemeter_camera) into ``sd.camera``: all of the sensor that is
+    flattened, so a moved meter re-flattens this alone"""
+    from .sensors import radiancemeter_camera
+    s2c, tw, near, far = radiancemeter_camera(sensor_dict.get("to_world"))
+    for i in range(16):
+        sd.camera.sample_to_camera[i] = np.float32(s2c.reshape(-1)[i])
+        sd.camera.to_world[i] = np.float32(tw.reshape(-1)[i])
+    sd.camera.near_clip, sd.camera.far_clip = np.float32(near), np.float32(far)
+
+
 class SceneData:
     """Flat, float32 description of a scene: exactly what crosses the C-ABI."""
 
@@ -1086,6 +1097,8 @@ def flatten_scene(d: Dict[str, Any], film, sensor_dict: Dict[str, Any], base_dir
             sd.camera.sample_to_camera[i] = np.float32(s2c.reshape(-1)[i])
             sd.camera.to_world[i] = np.float32(tw.reshape(-1)[i])
         sd.camera.near_clip, sd.camera.far_clip = np.float32(near), np.float32(far)
+    elif sensor_dict.get("type") == "radiancemeter":
+        flatten_radiancemeter(sd, sensor_dict)
     sd.film = film_desc_from(film)
     sd.shape_names, sd.shape_ranges = b.shape_names, b.shape_ranges
     sd.relay_shape = b.shape_names.index(relay_shape_name) if relay_shape_name is not None else -1

@@ -92,3 +92,53 @@ class PerspectiveSensor:
 
     def sampler(self):
         return self.sampler_
+
+
+def coordinate_system(n):
+    """[mitsuba3: coordinate_system (Duff et al.)] two unit vectors (s, t) that complete the unit vector ``n`` to a frame"""
+    import math
+    x, y, z = (float(v) for v in n)
+    sign = math.copysign(1.0, z)
+    a = -1.0 / (sign + z)
+    b = x * y * a
+    return [sign * (x * x * a) + 1.0, sign * b, -sign * x], [b, sign + y * y * a, -y]
+
+
+class RadianceMeter(PerspectiveSensor):
+    """``radiancemeter`` [mitsuba3: src/sensors/radiancemeter.cpp]: every sample of its 1 x 1 film is the ray from ``origin``
+    along ``direction`` (or the local +z axis of ``to_world``) — the receiver of a single-pixel transient measurement.  It is
+    flattened to the library's general camera record (radiancemeter_camera): no kernel knows about it."""
+
+    def __init__(self, sensor_dict, film, sampler):
+        from ..transform import ScalarTransform4f
+        import numpy as np
+        d = dict(sensor_dict)
+        has_od = "origin" in d or "direction" in d
+        if "to_world" in d and has_od:
+            raise ValueError("radiancemeter: only one of the parameters 'origin' / 'direction' and 'to_world' can be specified "
+                             "at the same time")
+        if has_od:
+            if "origin" not in d or "direction" not in d:
+                raise ValueError("radiancemeter: if the sensor is specified through origin and direction both values must be set")
+            o = np.asarray(d.pop("origin"), np.float64).reshape(3)
+            v = np.asarray(d.pop("direction"), np.float64).reshape(3)
+            if not np.linalg.norm(v) > 0:
+                raise ValueError("radiancemeter: 'direction' must not be the zero vector")
+            up, _ = coordinate_system(v / np.linalg.norm(v))
+            d["to_world"] = ScalarTransform4f().look_at(o, o + v, up)
+        if tuple(int(x) for x in film.size()) != (1, 1):
+            raise ValueError("radiancemeter: This sensor only supports films of size 1x1 Pixels!")
+        super().__init__(d, film, sampler)
+
+
+def radiancemeter_camera(to_world):
+    """(sample_to_camera, to_world, near_clip, far_clip) of a radiancemeter as the library's camera record: a degenerate
+    projection that sends every film sample to the local direction (0, 0, 1) — camera_ray (mtr_core.h) then returns the origin
+    and the +z axis of ``to_world`` whatever the jitter —, near_clip 0 (the ray starts AT the origin) and the largest finite f32
+    as far_clip (tmax stays finite)."""
+    import numpy as np
+    from ..transform import to_transform
+    s2c = np.zeros((4, 4), np.float64)
+    s2c[2, 3] = 1.0
+    s2c[3, 3] = 1.0
+    return s2c, to_transform(to_world).matrix, 0.0, float(np.finfo(np.float32).max)
