@@ -22,6 +22,9 @@
 #ifndef MTR_BATCH
 #define MTR_BATCH 15        // k_fused's lean kernels: which BATCHED REQUESTS are built (a mask; see kernarg_pin)
 #endif
+#ifndef MTR_PATH_STATE
+#define MTR_PATH_STATE 3    // k_fused's lean kernels: ONE COPY OF THE PATH STATE (a mask; 1 dead lanes let go, mtr_kernels.hip; 2 single fills, shade_hit)
+#endif
 
 #include <stdint.h>
 #include <math.h>
@@ -2094,6 +2097,18 @@ struct Path {
 
 struct BounceStats { uint32_t closest, shadow; };
 
+// ONE COPY OF THE PATH STATE (round 12; k_fused's lean kernels, mtr_kernels.hip): a value nobody reads again is given a definition that
+// costs no instruction, so that the merge it flows into has one defined input.  Device code only; a host build never asks for it.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MTR_FORGET(x) asm volatile("" : "=v"(x))
+#else
+#define MTR_FORGET(x) ((void)0)
+#endif
+MTR_HD void forget_ray(Ray &r)
+{
+    MTR_FORGET(r.o.x); MTR_FORGET(r.o.y); MTR_FORGET(r.o.z); MTR_FORGET(r.d.x); MTR_FORGET(r.d.y); MTR_FORGET(r.d.z); MTR_FORGET(r.tmax);
+}
+
 // lane -> pixel, RNG seeding, jitter, camera ray, loop-state init (transientpath.py:118-131);
 // the camera_unwarp pre-pass is done by the caller (it needs a traversal).
 MTR_HD void path_begin(Path &p, const Camera &cam, const Film &f, const RenderConst &rc, uint32_t pixel, uint32_t s)
@@ -2360,7 +2375,7 @@ struct Pending {
 // pick: (optional) told the index of the emitter the emitter-sampling term samples (mtr_grad.h: whose radiance the term carries);
 // the default does nothing
 struct NoEmitterPick { MTR_HD void operator()(uint32_t) const {} };
-template <bool ROUGH = true, uint32_t TR = 0u, class Sink, class Pick = NoEmitterPick>
+template <bool ROUGH = true, uint32_t TR = 0u, bool LEAN = false, class Sink, class Pick = NoEmitterPick>
 // keep: (optional) the surface interaction for shade_finish — a caller that runs nothing between the two parts (k_wf_shade over scenes
 // in HBM: the shadow ray goes to a list) hands it over instead of having shade_finish fetch the shading record a second time
 MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &film, const RenderConst &rc,
@@ -2374,6 +2389,9 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
     p.dist += kDiff ? h.t : h.t * eta;                               // :154 (inf on a miss)
     pd.active_next = (((p.depth + 1u) < rc.max_depth) & valid) ? 1u : 0u;   // :185
     pd.Le = mk(0, 0, 0); pd.Lr = mk(0, 0, 0); pd.opl = 0.0f; pd.has_shadow = 0u;
+    // (LEAN, SINGLE FILLS: Lr and opl are read under has_shadow alone — shade_finish — so they are filled where has_shadow is set: a
+    // shadow ray is traced for a back-facing pair of directions too, and its term is the zero filled in there)
+    if constexpr (LEAN && (MTR_PATH_STATE & 2) != 0) { MTR_FORGET(pd.Lr.x); MTR_FORGET(pd.Lr.y); MTR_FORGET(pd.Lr.z); MTR_FORGET(pd.opl); }
     pd.alb = mk(0, 0, 0); pd.has_alb = 0u;
     const uint32_t fx = p.px - film.crop_x, fy = p.py - film.crop_y;       // transient_image_block.py:132
     const bool in_film = (fx < film.width) & (fy < film.height);
@@ -2477,6 +2495,7 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
                 float sdist = sqrtf(dot(sd, sd));
                 shadow.o = so; shadow.d = sd / sdist; shadow.tmax = sdist * (1.0f - kShadowEps);
                 pd.has_shadow = 1u;
+                if constexpr (LEAN && (MTR_PATH_STATE & 2) != 0) { pd.Lr = mk(0, 0, 0); pd.opl = 0.0f; }
                 if (lobes_on<ROUGH, TR>() && bsdf_is_rough(mat.type)) {
                     f3 bval; float bpdf;
                     pd.alb = material_albedo<ROUGH>(sc, mat, h); pd.has_alb = 1u;
@@ -2504,7 +2523,7 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
 // Part B (transientpath.py:216-257, :318): commits the emitter-sampling term given the shadow-ray
 // answer, samples the BSDF, updates the loop state and applies Russian roulette.
 // RNG: next_1d, next_2d (:223-224), next_1d (:256).  Returns active_next.
-template <bool ROUGH = true, uint32_t TR = 0u, class Sink>
+template <bool ROUGH = true, uint32_t TR = 0u, bool LEAN = false, class Sink>
 MTR_HD bool shade_finish(Path &p, const Hit &h, bool occluded, const Pending &pd, const SceneView &sc,
                          const Film &film, const RenderConst &rc, Sink &sink, const HitCtx *kept = nullptr)
 {
@@ -2527,9 +2546,17 @@ MTR_HD bool shade_finish(Path &p, const Hit &h, bool occluded, const Pending &pd
     BsdfSample bs;
     bs.wo = mk(0, 0, 0); bs.pdf = 0.0f; bs.eta = 1.0f; bs.delta = false; bs.w = mk(0, 0, 0);
     f3 sp = mk(0, 0, 0);
+    // (LEAN, SINGLE FILLS: without active_next the path ends here whatever the sample's weight, density and vertex are, and the caller
+    // reads neither throughput nor previous vertex of an ended path: ONE definition each, under active_next)
+    if constexpr (LEAN && (MTR_PATH_STATE & 2) != 0) {
+        MTR_FORGET(bs.w.x); MTR_FORGET(bs.w.y); MTR_FORGET(bs.w.z); MTR_FORGET(bs.pdf); MTR_FORGET(sp.x); MTR_FORGET(sp.y); MTR_FORGET(sp.z);
+    }
     p.L = mk((p.L.x + pd.Le.x) + Lr.x, (p.L.y + pd.Le.y) + Lr.y, (p.L.z + pd.Le.z) + Lr.z);    // :230
+    // (LEAN: a path that ends here leaves no ray — the caller reads none — so the ray has ONE definition, the one under active_next)
+    const f3 ray_d = p.ray.d;
+    if constexpr (LEAN && (MTR_PATH_STATE & 1) != 0) forget_ray(p.ray);
     if (valid) {
-        const HitCtx c = kept ? *kept : hit_ctx<ROUGH, tr_spheres(TR)>(sc, p.ray.d, h);
+        const HitCtx c = kept ? *kept : hit_ctx<ROUGH, tr_spheres(TR)>(sc, ray_d, h);
         sp = c.sp;
         if (active_next) {
             const f3 albedo = (ROUGH && pd.has_alb) ? pd.alb : material_albedo<ROUGH>(sc, sc.mats[c.mat], h);
@@ -2581,6 +2608,8 @@ MTR_HD bool path_bounce(Path &p, const SceneView &sc, const Film &film, const Re
     stats.closest++;
     Pending pd; Ray shadow;
     shadow.o = mk(0, 0, 0); shadow.d = mk(0, 0, 1); shadow.tmax = 0.0f;
+    constexpr bool kLeanState = stack_one_kernarg_base<Stack>::value && flat_kind(TR) == 1;      // (ONE COPY OF THE PATH STATE, above)
+    if constexpr (kLeanState && (MTR_PATH_STATE & 2) != 0) forget_ray(shadow);                   // (traced under has_shadow alone)
     // (stacks that park path state in LDS: the values come back where they are used, so that they hold no register across
     // the traversals)
     if (Stack::kPark) { p.prev_p = st.unpark_prev_p(); p.prev_pdf = st.unpark_prev_pdf(); p.rng.inc = st.unpark_inc(); }
@@ -2592,7 +2621,7 @@ MTR_HD bool path_bounce(Path &p, const SceneView &sc, const Film &film, const Re
     // (Only under the specialised shading code, kTrCornell: the four-wave kernel of the general one pays for it with 6 spilled VGPRs.)
     constexpr bool kHandOver = stack_one_kernarg_base<Stack>::value && flat_kind(TR) == 1 && (TR & kTrCornell) == kTrCornell && (MTR_BATCH & 8) != 0;
     HitCtx kept;
-    shade_hit<ROUGH, TR>(p, h, sc, film, rc, sink, pd, shadow, kHandOver ? &kept : nullptr);
+    shade_hit<ROUGH, TR, kLeanState>(p, h, sc, film, rc, sink, pd, shadow, kHandOver ? &kept : nullptr);
     st.prof_mark(1);
     bool occluded = false;
     if (pd.has_shadow) {
@@ -2603,7 +2632,7 @@ MTR_HD bool path_bounce(Path &p, const SceneView &sc, const Film &film, const Re
     st.prof_mark(0);
     if (Stack::kPark) p.rng.inc = st.unpark_inc();
     refresh(p, sink);
-    const bool an = shade_finish<ROUGH, TR>(p, h, occluded, pd, sc, film, rc, sink, kHandOver ? &kept : nullptr);
+    const bool an = shade_finish<ROUGH, TR, kLeanState>(p, h, occluded, pd, sc, film, rc, sink, kHandOver ? &kept : nullptr);
     if (Stack::kPark) { st.park_prev_p(p.prev_p); st.park_prev_pdf(p.prev_pdf); }
     st.prof_mark(1);
     return an;

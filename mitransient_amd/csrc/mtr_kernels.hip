@@ -258,6 +258,21 @@ static_assert(offsetof(FusedArgs, spp_chunk) - offsetof(FusedArgs, spp_begin) ==
               offsetof(FusedArgs, G) - offsetof(FusedArgs, spp_begin) == offsetof(LoopArgs, G) &&
               offsetof(FusedArgs, div_spp) - offsetof(FusedArgs, spp_begin) == offsetof(LoopArgs, div_spp) &&
               offsetof(FusedArgs, div_G) - offsetof(FusedArgs, spp_begin) == offsetof(LoopArgs, div_G), "LoopArgs mirrors FusedArgs");
+// ONE COPY OF THE PATH STATE (round 12; the lean kernels).  A lane that is not alive never reads its ray, throughput, distance or
+// depth again: path_begin rewrites every one of them before the lane's next bounce (prev_p, prev_pdf and the PCG32 increment are
+// parked, rewritten there too; rng_seed rewrites the generator's state).  What such a lane does read is p.L, when `carry` holds, its
+// sample index, pixel ordinal, row slot and xy.  The persistent loop says so wherever only such lanes pass: at chunk entry, on the
+// not-alive side of `if (alive)`, and on the idle back edge, which a wave takes with NO lane alive.  That last edge is the one that
+// counts: it carried the state as it is after the path start straight to the loop header, where the state as it is after the bounce
+// arrives too, and the two are live at once inside the bounce — so the allocator kept two register sets and copied one to the other
+// at every path start (17 moves per wave iteration, 17 registers).  With nothing defined on that edge the sets coalesce: config 2's
+// kernel 128 -> 125 VGPRs, 136 -> 62 register copies in the loop (profiles/r12_path_state.txt).
+__device__ __forceinline__ void forget_dead(Path &p)
+{
+    forget_ray(p.ray); MTR_FORGET(p.beta.x); MTR_FORGET(p.beta.y); MTR_FORGET(p.beta.z);
+    MTR_FORGET(p.prev_p.x); MTR_FORGET(p.prev_p.y); MTR_FORGET(p.prev_p.z); MTR_FORGET(p.prev_pdf); MTR_FORGET(p.dist); MTR_FORGET(p.depth);
+    MTR_FORGET(p.rng.state);
+}
 #ifndef MTR_FUSED_MIN_WAVES
 #define MTR_FUSED_MIN_WAVES 4          // waves per SIMD the register allocator must leave room for
 #endif
@@ -454,6 +469,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     bool alive = false;
     bool waiting = i < n_lanes;          // holds a sample index whose path has not started yet
     Path p;
+    if constexpr (kLean && (MTR_PATH_STATE & 1) != 0) forget_dead(p);
     p.L = mk(0, 0, 0);
     uint32_t q = 0, slot = 0;
     uint32_t xy = 0;                     // (packed film coordinates, below) px | py << 16 of the lane's path
@@ -502,6 +518,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
             if (__ballot(waiting) == 0ull) break;        // the whole wave is out of work
             __builtin_amdgcn_s_sleep(8);                 // every lane waits for a row another wave is about to flush
             st.prof_mark(5);
+            if constexpr (kLean && (MTR_PATH_STATE & 1) != 0) forget_dead(p);
             continue;
         }
         bool closes = false;
@@ -630,7 +647,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                 // leader lane — was measured: end-of-path bookkeeping 8.0 -> 11.0 % of the wave's time; not kept.)
                 closes = __hip_atomic_fetch_add(s_done + slot, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) + 1u == a.spp_chunk;
             }
-        }
+        } else if constexpr (kLean && (MTR_PATH_STATE & 1) != 0) forget_dead(p);
         if (!NLOS) {          // one closest-hit ray per live lane (counted with w_bounce), at most one shadow ray, at most two contributions
             w_shadow += (uint32_t)__popcll(__ballot(did_shadow != 0u));
             w_splats += (uint32_t)__popcll(__ballot((did_splats & 1u) != 0u)) + 2u * (uint32_t)__popcll(__ballot((did_splats & 2u) != 0u));
