@@ -42,6 +42,7 @@ struct mtr_ctx {
     uint32_t *d_band_count = nullptr; size_t band_cap = 0;       // mtr_render_params.n_bands: flushed pixels per band of the launch in flight
     void *d_part = nullptr; size_t part_cap = 0;         // ... and the partition workspace of unsorted input (at most 256 MiB of it kept between calls, until mtr_ctx_trim / destroy)
     void *d_samples = nullptr; size_t samples_cap = 0;   // MTR_MODE_SAMPLES: the slabs' rows (at most 256 MiB kept between calls, until mtr_ctx_trim / destroy)
+    void *d_start = nullptr; size_t start_cap = 0;       // k_fused's lean kernels: kStartSlots path-start tables (mtr_start_blocks.h), one per ticket counter of the rotation (until mtr_ctx_trim / destroy)
 };
 
 struct WfWorkspace {            // MTR_MODE_WAVEFRONT buffers, sized for one tile, reused across renders
@@ -143,7 +144,7 @@ void mtr_ctx_destroy(mtr_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (void *p : { (void *)c->d_counters, (void *)c->d_ticket, (void *)c->d_freq, c->d_runs, c->d_part, c->d_samples, (void *)c->d_band_count }) if (p) (void)hipFree(p);
+    for (void *p : { (void *)c->d_counters, (void *)c->d_ticket, (void *)c->d_freq, c->d_runs, c->d_part, c->d_samples, c->d_start, (void *)c->d_band_count }) if (p) (void)hipFree(p);
     for (hipEvent_t e : { c->ev0, c->ev1, c->ev2, c->ev3 }) if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -929,7 +930,19 @@ int mtr_render(mtr_scene *s, const mtr_render_params *p, float *t4, float *s4,
             FusedConfig cfg{};
             if (!fused_plan(s->dev, f, n_pixels, a.spp_chunk, usable_cus(c, p), a, cfg))
                 return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render: no kernel configuration fits (BVH depth / LDS)");
-            a.ticket = c->d_ticket + (c->fused_launches++ & 15u);
+            const uint32_t launch_slot = c->fused_launches++ & 15u;
+            a.ticket = c->d_ticket + launch_slot;
+            // START BLOCKS: the launch's path-start table, one per ticket counter for the same reason (fused_start_table_bytes: 0 for
+            // every kernel but the lean flat-walk ones; config 2's grid: 12 MiB per table)
+            static_assert(kStartSlots == 16u, "one path-start table per ticket counter of the rotation");
+            if (const size_t tab_bytes = fused_start_table_bytes(a, cfg)) {
+                // The slot stride follows from the ALLOCATION (start_slot_stride), not from this launch's grid: launches of different
+                // grids in flight on two streams keep disjoint tables.  A larger table re-allocates: grow_device_buffer drains this
+                // context's stream and hipFree waits for the device's other work before the old tables go.
+                if (start_slot_stride(c->start_cap) < tab_bytes)
+                    if (int r = grow_device_buffer(c, &c->d_start, &c->start_cap, start_alloc_bytes(tab_bytes))) return r;
+                a.start_tab = (unsigned char *)c->d_start + start_slot_off(start_slot_stride(c->start_cap), launch_slot);
+            }
             a.n_bands = 0u;
             if (p->n_bands) {
                 // (one banded launch in flight per context: the counts are the context's; callers that overlap launches on two
@@ -1298,6 +1311,8 @@ int mtr_ctx_trim(mtr_ctx *c)
     c->d_part = nullptr; c->part_cap = 0;
     if (c->d_samples) (void)hipFree(c->d_samples);
     c->d_samples = nullptr; c->samples_cap = 0;
+    if (c->d_start) (void)hipFree(c->d_start);
+    c->d_start = nullptr; c->start_cap = 0;
     return MTR_OK;
 }
 

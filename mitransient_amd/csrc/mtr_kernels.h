@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "mtr_core.h"
 #include "mtr_nlos.h"
+#include "mtr_start_blocks.h"
 
 namespace mtr {
 
@@ -114,6 +115,9 @@ struct FusedArgs {
     uint32_t n_bands, band_px, band_epoch;
     uint32_t *band_count, *band_done;
     NlosConst nlos;
+    // the path-start table of this launch (mtr_start_blocks.h; the lean flat-walk kernels: fused_start_blocks), start_table_bytes(grid, waves)
+    // bytes of the context's; last, so that every other member keeps its place in the kernarg segment
+    unsigned char *start_tab;
 };
 
 struct FusedConfig { int stack; bool scene_lds; bool hist_lds; bool fixed; bool rough; size_t lds_bytes; int grid; int per_cu; uint32_t traits; };
@@ -136,6 +140,9 @@ uint32_t fused_chunk(uint32_t n_pixels, uint32_t spp_chunk, uint32_t grid);
 // chooses G, LDS carve-up and grid for a render; returns false if nothing fits
 bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t spp_chunk, int n_cu,
                 FusedArgs &args, FusedConfig &cfg);
+// bytes of the path-start table the kernel launch_fused picks for (args, cfg) reads through args.start_tab; 0: that kernel has none
+// (one predicate for the caller that allocates and the launch that checks: a kernel never indexes a table nobody sized)
+size_t fused_start_table_bytes(const FusedArgs &args, const FusedConfig &cfg);
 hipError_t launch_fused(const FusedArgs &args, const FusedConfig &cfg, hipStream_t stream);
 // NLOS prepare (transientnlospath.py:295-336): one ray per film pixel -> scanned points, + the laser's axis
 hipError_t launch_nlos_prepare(const SceneDev &sc, const NlosConst &nc, q4 *targets, hipStream_t stream);
@@ -230,3 +237,5 @@ hipError_t launch_grad(const SceneDev &sc, const Emitter *ems_unit, const Camera
 // test hooks of the library, outside the C ABI of include/mitransient_amd.h: fused_chunk / fused_chunk_cap as the tests call them
 extern "C" uint32_t mtr_test_fused_chunk(uint32_t n_pixels, uint32_t spp_chunk, uint32_t grid);
 extern "C" uint32_t mtr_test_fused_chunk_cap(uint32_t chunk, uint32_t spp_chunk);
+extern "C" void mtr_test_start_blocks(uint32_t n_lanes, uint32_t grid, uint32_t wg, uint32_t wave, uint32_t entry, uint32_t base, uint32_t *out);
+extern "C" int mtr_test_start_blocks_sweep(uint32_t n_lo, uint32_t n_hi, uint32_t g_lo, uint32_t g_hi);

@@ -273,6 +273,63 @@ __device__ __forceinline__ void forget_dead(Path &p)
     MTR_FORGET(p.prev_p.x); MTR_FORGET(p.prev_p.y); MTR_FORGET(p.prev_p.z); MTR_FORGET(p.prev_pdf); MTR_FORGET(p.dist); MTR_FORGET(p.depth);
     MTR_FORGET(p.rng.state);
 }
+// START BLOCKS (round 13; the lean kernels; -DMTR_START_BLOCKS=0: the former code).  A path start — sample index to pixel and row
+// slot, the owner test, path_begin: tea4, two PCG32 seeding steps, two jitter draws, a camera ray with three divisions and a square
+// root — ran in practically every wave iteration for the 15 of 64 lanes whose paths had just ended (268 M paths over 17.4 M wave
+// iterations of config 2), 9.6 % of a wave's clock.  path_begin is a pure function of the sample index and launch constants, so a
+// wave now computes it 64 indices at a time, at full width, about once per four iterations:
+//   * A wave owns a BLOCK of 64 consecutive sample indices of the ticket (mtr_start_blocks.h): two uniform words, the block's first
+//     index and the number of entries handed out.  At ticket entry wave w holds [64 w, 64 w + 64), not computed yet (kStartFresh);
+//     later blocks come from one atomicAdd(s_next, 64) of the wave's first lane.
+//   * Lanes whose path ended in an iteration take the block's next entries in lane order (a ballot and mbcnt: a prefix count, no
+//     atomic).  A lane that finds the block used up is marked (`want`) and served at the loop top, after the refill; its `carry` is
+//     false, so it deposits its radiance at once (`carry` is an optimisation: always correct).
+//   * REFILL, at the loop top BEHIND the start section, wave-uniform: a lane wants an index and NO lane of the wave still holds an
+//     entry it could not start; the start section then takes a second turn for the lanes just served.  (In front of the start section
+//     the lanes that had taken an entry one instruction earlier still counted as holding one, the refill waited an iteration in
+//     one of four, and the marked lanes sat it out: 61.5 instead of 63.3 live lanes per iteration, +0.1 instead of -0.7 ms.)
+//     All 64 lanes, alive or not, run the unchanged path_begin for index (block + lane id) into a temporary Path and store ray and
+//     generator into their record of the wave's 64 in the path-start table (global memory, FusedArgs::start_tab; 48 bytes, so
+//     3 KB per wave that stay in the vector L1 / L2).  Store and load are the same wave's, so a wavefront-scope release orders them.
+//   * A waiting lane that owns its row reads its record at the loop top and fills in what the index gives (pixel, film coordinates,
+//     lane id) and the constants.  While a lane waits for a row its entry is of the CURRENT block — the refill waits for such lanes —
+//     so (i - block) is its record.
+// PROGRESS.  The only spin is the former one, on s_owner.  A wave hands out its block in index order and draws a new block only when
+// the old one is fully handed out AND every entry handed out has started.  Blocks are drawn in index order too (one atomic counter).
+// So when a lane holds an index of a pixel that does not own a row yet, every smaller index of the ticket lies in a block some wave
+// has drawn, and within that wave every earlier entry of the block has gone to a lane.  Take the earliest unflushed pixel q: it owns
+// its row (pixel q - G is flushed).  An index of q is held by a lane — which starts at its next loop top, the owner test passing —
+// or is a not yet handed out entry of its wave's current block: the lanes of that wave are alive (their paths end, and they take the
+// next entries in order), or hold earlier entries of the same block (of q itself, hence startable), or are marked, which happens
+// only once the block is used up.  A wave that postpones its refill does so for lanes waiting for rows, which no lane it could
+// start would release sooner: the indices it would draw are larger still.  So q completes, is flushed, and hands its row on.
+// No wave waits for another wave for anything it did not wait for before.
+#ifndef MTR_START_BLOCKS
+#define MTR_START_BLOCKS 1
+#endif
+typedef uint32_t StartRecWord __attribute__((ext_vector_type(4)));
+typedef StartRecWord __attribute__((address_space(1))) *StartRecPtr;      // a record of the table, as GLOBAL memory: global_load / global_store (a generic pointer gave flat_*, counted in lgkmcnt too)
+struct StartTabArg { uint32_t lo, hi; };
+// a pointer member of FusedArgs read from the kernarg segment where it is used (START BLOCKS: ticket, film and steady image are used once
+// per ticket or per flushed row; held by value across the loop, ticket / film / steady image / counters are ONE eight-register tuple, which
+// the allocator splits around the refill and rematerialises, leaving a stack slot nobody uses: a 36-byte private segment with no scratch
+// instruction.  With ticket and film read here the kernel has none); ON false: the by-value member, as before
+template <class T, bool ON>
+__device__ __forceinline__ T *kernarg_ptr(size_t offset, T *by_value)
+{
+    if constexpr (ON) { const StartTabArg w = kernarg_copy<StartTabArg, true>(offset); return (T *)(((uint64_t)w.hi << 32) | w.lo); }
+    else return by_value;
+}          // FusedArgs::start_tab as the kernarg segment holds it (kernarg_copy)
+// what a record does not hold: everything path_begin derives from the index alone, and the constants of a fresh path.  These are
+// path_begin's own first and last two lines (mtr_core.h), kept apart from it so that every other caller's code stays what it was; a
+// change there belongs here too — tests/test_gpu_fused_start_blocks.py compares film, steady image and counters with the oracle
+__device__ __forceinline__ void path_resume(Path &p, const Film &f, const RenderConst &rc, uint32_t pixel, uint32_t s)
+{
+    const uint32_t py = fastdiv(pixel, rc.div_crop_w), px = pixel - f.crop_w * py;
+    p.px = px + f.crop_x; p.py = py + f.crop_y; p.lane = pixel * rc.spp_total + s;
+    p.beta = mk(1, 1, 1); p.L = mk(0, 0, 0); p.prev_p = mk(0, 0, 0);
+    p.eta = 1.0f; p.dist = 0.0f; p.prev_pdf = 1.0f; p.depth = 0; p.prev_delta = 1;
+}
 #ifndef MTR_FUSED_MIN_WAVES
 #define MTR_FUSED_MIN_WAVES 4          // waves per SIMD the register allocator must leave room for
 #endif
@@ -293,6 +350,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     // same changes moved their allocation the wrong way (more spilled VGPRs, more scratch) in most of them.
     constexpr bool kLean = SCENE_LDS && HIST_LDS && !NLOS && !PHASOR && !FIXED && !ROUGH && flat_kind(TR) != 0;
     constexpr bool kPrimTable = flat_prim_table_on(kLean, flat_kind(TR) == 2);
+    constexpr bool kStartBlocks = kLean && MTR_START_BLOCKS != 0;          // START BLOCKS, above (fused_start_blocks: the host's side of it)
 #ifdef MTR_PROFILE_TAIL
     const unsigned long long t0_wall = wall_clock64();
 #endif
@@ -442,11 +500,12 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     if (tid == 0) {
         // guided: a.chunk pixels per ticket, fewer as the launch runs out (about half a share of what is left), so that the
         // workgroups finish within one pixel of each other — a launch per row band (multi-GPU pipeline) ends 8 times per render
-        const uint32_t seen = __hip_atomic_load(a.ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        uint32_t *const ticket = kernarg_ptr<uint32_t, kStartBlocks>(offsetof(FusedArgs, ticket), a.ticket);
+        const uint32_t seen = __hip_atomic_load(ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t left = seen < n_px_all ? n_px_all - seen : 0u;
         uint32_t want = left / (2u * gridDim.x);
         want = want < 1u ? 1u : (want > a.chunk ? a.chunk : want);
-        s_chunk[0] = atomicAdd(a.ticket, want); s_chunk[1] = want;
+        s_chunk[0] = atomicAdd(ticket, want); s_chunk[1] = want;
         *s_next = kBlock;
     }
     for (uint32_t k = tid; k < K; k += kBlock) s_owner[k] = k;
@@ -474,8 +533,27 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     uint32_t q = 0, slot = 0;
     uint32_t xy = 0;                     // (packed film coordinates, below) px | py << 16 of the lane's path
     bool carry = false;                  // the path that just ended leaves its radiance in p.L: this lane's next path is in the same pixel
+    // START BLOCKS: the wave's block (first index, entries handed out) and the lanes that found it used up
+    uint32_t blk_base = 0u, blk_used = 0u;
+    bool want = false;
+    if constexpr (kStartBlocks) {
+        blk_base = __builtin_amdgcn_readfirstlane((uint32_t)tid & ~(kStartBlock - 1u)); blk_used = kStartFresh;
+        want = true; waiting = false;
+    }
+    // ... a lane's record, read into the path state a dead lane has let go (forget_dead), behind the owner test.  (Requested where the
+    // lane takes its entry instead, in flight through the rest of the end-of-path section: 128 VGPRs and 0.1 ms slower, HISTORY.md.)
+    auto load_rec = [&](uint32_t entry) {
+        const StartTabArg ta = kernarg_copy<StartTabArg, kLean>(offsetof(FusedArgs, start_tab));
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint32_t wv = (uint32_t)tid / kStartBlock;
+        const StartRecPtr rec = (StartRecPtr)((((uint64_t)ta.hi << 32) | ta.lo) + start_rec_off(blockIdx.x, kBlock / kStartBlock, wv, entry));
+        const StartRecWord r0 = rec[0], r1 = rec[1], r2 = rec[2];
+        p.ray.o = mk(bitsf(r0.x), bitsf(r0.y), bitsf(r0.z)); p.ray.d = mk(bitsf(r0.w), bitsf(r1.x), bitsf(r1.y)); p.ray.tmax = bitsf(r1.z);
+        p.rng.state = (uint64_t)r1.w | ((uint64_t)r2.x << 32); p.rng.inc = (uint64_t)r2.y | ((uint64_t)r2.z << 32);
+    };
     for (;;) {
         st.prof_mark(4);                 // (experiment builds) sections: 0 traversal, 1 shading, 2 path start, 3 end-of-path bookkeeping, 4 row flush, 5 idle
+        for (;;) {          // (START BLOCKS: a second turn for the lanes the refill below has served; otherwise once)
         if (__ballot(waiting) != 0ull) {
             bool started = false;
             // (the arguments a path start needs: read from the kernarg segment here, see kernarg_copy)
@@ -498,10 +576,18 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                         // argument it lived in scalar registers across the whole persistent loop, i.e. in v_readlane'd spill slots
                         // (the loop holds more than 100 uniform values).  Scalar loads from the kernarg segment where a path starts
                         // instead: 111 -> 82 spilled SGPRs, config 2 61.1 -> 60.4 ms (same box)
+                        if constexpr (kStartBlocks) {
+                            // START BLOCKS: the lane's record of its wave's block (the refill above wrote it), and what the index gives
+                            const Film film_s = kernarg_copy<Film, kLean>(offsetof(FusedArgs, film));
+                            const RenderConst rc_s = kernarg_copy<RenderConst, kLean>(offsetof(FusedArgs, rc));
+                            load_rec(i - blk_base);
+                            path_resume(p, film_s, rc_s, pixel, s);
+                        } else {
                         const Camera cam_l = kernarg_copy<Camera, kLean>(offsetof(FusedArgs, cam));
                         const Film film_s = kernarg_copy<Film, kLean>(offsetof(FusedArgs, film));
                         const RenderConst rc_s = kernarg_copy<RenderConst, kLean>(offsetof(FusedArgs, rc));
                         path_begin(p, cam_l, film_s, rc_s, pixel, s);
+                        }
                         if (LdsStack::kPark) { st.park_inc(p.rng.inc); st.park_prev_p(p.prev_p); st.park_prev_pdf(p.prev_pdf); }
                     }
                     p.L = L_carried; carry = false;
@@ -513,6 +599,46 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
             w_paths += n_started;
             if (!kLean && !NLOS && (a.rc.flags & MTR_FLAG_CAMERA_UNWARP)) w_closest += n_started;
         }
+        if constexpr (kStartBlocks) {
+            // REFILL (wave-uniform).  Not while a lane still holds an entry of the block it could not start: its record must stay.
+            if (__ballot(want) == 0ull || __ballot(waiting) != 0ull) break;
+            {
+                const uint32_t wl = (uint32_t)tid & (kStartBlock - 1u);
+                const bool fresh = blk_used == kStartFresh;
+                if (fresh || blk_base < n_lanes) {           // (a block at or beyond the ticket's end: the ticket has run dry, for good)
+                    if (!fresh) {
+                        uint32_t b = 0u;
+                        if (wl == 0u) b = atomicAdd(s_next, kStartBlock);
+                        blk_base = __builtin_amdgcn_readfirstlane(b);
+                    }
+                    blk_used = 0u;
+                    const uint32_t fi = blk_base + wl;
+                    {        // (entries at or beyond the ticket's end do not exist: nobody takes them, whatever their records hold)
+                        const LoopArgs la = kernarg_copy<LoopArgs, kLean>(offsetof(FusedArgs, spp_begin));
+                        const Camera cam_l = kernarg_copy<Camera, kLean>(offsetof(FusedArgs, cam));
+                        const Film film_s = kernarg_copy<Film, kLean>(offsetof(FusedArgs, film));
+                        const RenderConst rc_s = kernarg_copy<RenderConst, kLean>(offsetof(FusedArgs, rc));
+                        const uint32_t fq = fastdiv(fi, la.div_spp);
+                        Path t;
+                        path_begin(t, cam_l, film_s, rc_s, pixel_of(fq), la.spp_begin + (fi - fq * la.spp_chunk));
+                        const StartTabArg ta = kernarg_copy<StartTabArg, kLean>(offsetof(FusedArgs, start_tab));
+                        const uint32_t wv = (uint32_t)tid / kStartBlock;
+                        const StartRecPtr rec = (StartRecPtr)((((uint64_t)ta.hi << 32) | ta.lo) + start_rec_off(blockIdx.x, kBlock / kStartBlock, wv, wl));
+                        rec[0] = StartRecWord{ fbits(t.ray.o.x), fbits(t.ray.o.y), fbits(t.ray.o.z), fbits(t.ray.d.x) };
+                        rec[1] = StartRecWord{ fbits(t.ray.d.y), fbits(t.ray.d.z), fbits(t.ray.tmax), (uint32_t)t.rng.state };
+                        rec[2] = StartRecWord{ (uint32_t)(t.rng.state >> 32), (uint32_t)t.rng.inc, (uint32_t)(t.rng.inc >> 32), 0u };
+                    }
+                    // the records are read by other lanes of THIS wave, through the vector L1 they were written through
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                }
+                // the marked lanes take the first entries, in lane order (a dry ticket: blk_base >= n_lanes, nobody waits)
+                const unsigned long long sm = __ballot(want);
+                const uint32_t e = blk_used + __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+                if (want) { i = blk_base + e; waiting = i < n_lanes; want = false; }
+                blk_used = min(blk_used + (uint32_t)__popcll(sm), kStartBlock);
+            }
+        } else break;
+        }
         st.prof_mark(2);
         if (__ballot(alive) == 0ull) {
             if (__ballot(waiting) == 0ull) break;        // the whole wave is out of work
@@ -522,7 +648,8 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
             continue;
         }
         bool closes = false;
-#ifdef MTR_PROFILE_OCC         // experiment build: occupancy of the persistent lanes (wave iterations, alive lanes, waiting lanes)
+        bool ended = false;                  // (START BLOCKS) the lane's path ended in this iteration: it took an entry of the block, or is marked
+#ifdef MTR_PROFILE_OCC        // experiment build: occupancy of the persistent lanes (wave iterations, alive lanes, waiting lanes)
         occ_iter += 1; occ_alive += (uint32_t)__popcll(__ballot(alive)); occ_wait += (uint32_t)__popcll(__ballot(waiting));
 #endif
         w_bounce += (uint32_t)__popcll(__ballot(alive));
@@ -623,8 +750,17 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                 // lane's next path of it has not ended.  Not for the order-independent rows (the runs depend on timing).
                 // The sample COUNT needs no atomic at all: the row is flushed when all spp_chunk paths of the pixel have ended
                 // (config 2: 68.7 -> 67.8 ms for that one atomic per path; fixed-point sums instead of f32: 67.7 -> 67.95, not kept).
+                if constexpr (kStartBlocks) {
+                    // START BLOCKS: the lanes whose path has just ended take the block's next entries in lane order; beyond its end: marked
+                    const unsigned long long em = __ballot(true);
+                    const uint32_t e = blk_used + __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
+                    i = blk_base + e; ended = true;
+                    want = e >= kStartBlock;
+                    waiting = !want && i < n_lanes;
+                } else {
                 i = atomicAdd(s_next, 1u);
                 waiting = i < n_lanes;
+                }
                 carry = !FIXED && waiting && (i - q * a.spp_chunk) < a.spp_chunk;      // the next sample is still in pixel q (i only grows)
                 const uint32_t fx = p.px - a.film.crop_x, fy = p.py - a.film.crop_y;
                 if (fx < a.film.width && fy < a.film.height && !carry) {
@@ -648,6 +784,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                 closes = __hip_atomic_fetch_add(s_done + slot, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) + 1u == a.spp_chunk;
             }
         } else if constexpr (kLean && (MTR_PATH_STATE & 1) != 0) forget_dead(p);
+        if constexpr (kStartBlocks) blk_used = min(blk_used + (uint32_t)__popcll(__ballot(ended)), kStartBlock);      // (uniform: counted outside the branch)
         if (!NLOS) {          // one closest-hit ray per live lane (counted with w_bounce), at most one shadow ray, at most two contributions
             w_shadow += (uint32_t)__popcll(__ballot(did_shadow != 0u));
             w_splats += (uint32_t)__popcll(__ballot((did_splats & 1u) != 0u)) + 2u * (uint32_t)__popcll(__ballot((did_splats & 2u) != 0u));
@@ -662,8 +799,10 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
             const uint32_t wl = tid & 63u;
             if (cx < a.film.width && cy < a.film.height) {
                 const size_t fpix = (size_t)cy * a.film.width + cx;
+                float *const film_out = kernarg_ptr<float, kStartBlocks>(offsetof(FusedArgs, film_out), a.film_out);
+                float *const steady_out = a.steady_out;      // (by value: read from the segment as well it changes no count)
                 if (PHASOR) {          // (H, W, 2F + 1): Re, Im per frequency, then the weight channel (stays 0)
-                    float *dst = a.film_out + fpix * (size_t)(T + 1u);
+                    float *dst = film_out + fpix * (size_t)(T + 1u);
                     float *h = s_hist + fs * T;
                     for (uint32_t t = wl; t < T; t += 64u) {
                         const float v = h[t];
@@ -674,7 +813,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                     // weight channel is identically 0 (develop divides by 1), so the row goes out whole — zeros included,
                     // contiguous 12 bytes per lane — and neither a cleared film nor a develop pass is needed.  Written once,
                     // never read here: non-temporal, so the stream does not displace the waves' scratch lines from L2.
-                    float *row3 = a.film_out + fpix * (size_t)T * 3u;
+                    float *row3 = film_out + fpix * (size_t)T * 3u;
                     for (uint32_t t = wl; t < T; t += 64u) {      // (four bins per lane and pass, 16-byte accesses: no faster — 68.7 vs 68.7 ms — and two more spills)
                         float r, gc, b;
                         if (FIXED) {
@@ -692,7 +831,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                         __builtin_nontemporal_store(r, o); __builtin_nontemporal_store(gc, o + 1); __builtin_nontemporal_store(b, o + 2);
                     }
                 } else if (FIXED) {
-                    float4 *row = (float4 *)(a.film_out + fpix * T * 4u);
+                    float4 *row = (float4 *)(film_out + fpix * T * 4u);
                     unsigned long long *h = s_hist64 + fs * T;
                     float *o = s_ovf + fs * T;
                     for (uint32_t t = wl; t < T; t += 64u) {
@@ -708,7 +847,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                         }
                     }
                 } else if (HIST_LDS) {
-                    float4 *row = (float4 *)(a.film_out + fpix * T * 4u);
+                    float4 *row = (float4 *)(film_out + fpix * T * 4u);
                     float *h = s_hist + fs * T;
                     // four bins per lane and pass (16-byte LDS reads, 64 contiguous bytes of film per lane); rows and planes
                     // are 16-byte aligned when T is a multiple of 4, the tail (or an odd T) goes bin by bin
@@ -750,7 +889,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                     if (FIXED) { v = splat_from_fixed(s_steady64[4 * fs + wl]) + s_steady_ovf[4 * fs + wl]; s_steady64[4 * fs + wl] = 0ull; s_steady_ovf[4 * fs + wl] = 0.0f; }
                     else { v = s_steady[4 * fs + wl]; s_steady[4 * fs + wl] = 0.0f; }
                     if (wl == 3) v = (float)a.spp_chunk;          // every sample of the pixel of this launch has ended
-                    if (v != 0.0f) a.steady_out[fpix * 4u + wl] += v;
+                    if (v != 0.0f) steady_out[fpix * 4u + wl] += v;
                 }
             }
             if (wl == 0) {
@@ -845,6 +984,16 @@ static bool fused_lean_flat_quads(bool nlos_on, uint32_t n_freq, const FusedConf
 static uint32_t fused_prim_table_bytes(const SceneDev &sc, bool nlos_on, uint32_t n_freq, const FusedConfig &cfg)
 {
     return flat_prim_table_on(true, false) && fused_lean_flat_quads(nlos_on, n_freq, cfg) ? flat_prim_bytes(sc.flat.n_boxes) : 0u;
+}
+
+// THE predicate of START BLOCKS: launch_fused_s picks a lean flat-walk kernel — !NLOS, f32 time-bin rows, plain shading, scene and
+// rows in LDS, a flat top level with or without triangle leaves (its three lean branches) — exactly where this holds.  The context
+// sizes the path-start table by it (mtr_api.hip) and launch_fused_s refuses such a launch without one.
+size_t fused_start_table_bytes(const FusedArgs &args, const FusedConfig &cfg)
+{
+    const bool lean = !args.nlos_on && !args.film.n_freq && !cfg.rough && !cfg.fixed && cfg.scene_lds && cfg.hist_lds &&
+                      (cfg.traits & kTrFlatFlags) == kTrFlatFlags;
+    return MTR_START_BLOCKS != 0 && lean && cfg.grid > 0 ? start_table_bytes((uint32_t)cfg.grid, kBlock / kStartBlock) : 0u;
 }
 
 bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t spp_chunk, int n_cu,
@@ -952,8 +1101,9 @@ bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_
 template <bool NLOS>
 static hipError_t launch_fused_s(const FusedArgs &args, const FusedConfig &cfg, hipStream_t stream)
 {
+    if (fused_start_table_bytes(args, cfg) != 0u && !args.start_tab) return hipErrorInvalidValue;      // (START BLOCKS: the kernel would index a table nobody sized)
     void (*k)(const FusedArgs) = nullptr;
-#ifdef MTR_ONLY_C2            // tools/regs_c2.sh, tools/build_variant.sh -DMTR_ONLY_C2: compile ONLY the instantiation config 2 runs (experiments: one
+#ifdef MTR_ONLY_C2           // tools/regs_c2.sh, tools/build_variant.sh -DMTR_ONLY_C2: compile ONLY the instantiation config 2 runs (experiments: one
                               // minute per variant instead of four); such a library renders config 2 and refuses everything else
     if (NLOS || args.film.n_freq || cfg.rough || cfg.fixed || !cfg.scene_lds || !cfg.hist_lds || cfg.traits != MTR_C2_TRAITS || cfg.per_cu <= 3) return hipErrorInvalidValue;
     k = k_fused<true, true, false, MTR_FUSED_MIN_WAVES, false, false, false, MTR_C2_TRAITS>;
@@ -1333,3 +1483,52 @@ hipError_t launch_develop(const Film &film, const float *t4, float *t3, const fl
 // test hooks (declared in mtr_kernels.h): the plan's host arithmetic without a device or a context
 extern "C" uint32_t mtr_test_fused_chunk(uint32_t n_pixels, uint32_t spp_chunk, uint32_t grid) { return mtr::fused_chunk(n_pixels, spp_chunk, grid); }
 extern "C" uint32_t mtr_test_fused_chunk_cap(uint32_t chunk, uint32_t spp_chunk) { return mtr::fused_chunk_cap(chunk, spp_chunk); }
+// mtr_start_blocks.h as the library compiled it: out = { blocks, entries of the last block, table bytes (lo, hi), the record offset of
+// (wg, wave, entry) (lo, hi), entries of the block at `base` }
+extern "C" void mtr_test_start_blocks(uint32_t n_lanes, uint32_t grid, uint32_t wg, uint32_t wave, uint32_t entry, uint32_t base, uint32_t *out)
+{
+    const uint32_t waves = mtr::kBlock / mtr::kStartBlock;
+    const uint64_t bytes = mtr::start_table_bytes(grid, waves), off = mtr::start_rec_off(wg, waves, wave, entry);
+    out[0] = mtr::start_blocks(n_lanes); out[1] = mtr::start_last_entries(n_lanes);
+    out[2] = (uint32_t)bytes; out[3] = (uint32_t)(bytes >> 32); out[4] = (uint32_t)off; out[5] = (uint32_t)(off >> 32);
+    out[6] = mtr::start_block_entries(n_lanes, base);
+}
+// ... swept: every ticket length in [n_lo, n_hi] (blocks, last block, the blocks' entries add up) and every grid in [g_lo, g_hi]
+// (every record of every wave inside the table, the records of a table in strictly ascending, gap-free order: no two overlap).
+// Returns 0, or the line of the first check that failed.
+extern "C" int mtr_test_start_blocks_sweep(uint32_t n_lo, uint32_t n_hi, uint32_t g_lo, uint32_t g_hi)
+{
+    using namespace mtr;
+    const uint32_t waves = kBlock / kStartBlock;
+    for (uint64_t n = n_lo; n <= n_hi; ++n) {
+        const uint32_t nl = (uint32_t)n, nb = start_blocks(nl), last = start_last_entries(nl);
+        if (nl && (last < 1u || last > kStartBlock)) return __LINE__;
+        if ((uint64_t)(nb ? nb - 1u : 0u) * kStartBlock + last != n) return __LINE__;
+        uint64_t sum = 0;
+        for (uint32_t b = 0; b < nb; ++b) {
+            const uint32_t e = start_block_entries(nl, b * kStartBlock);
+            if (e != (b + 1u == nb ? last : kStartBlock)) return __LINE__;
+            sum += e;
+        }
+        if (sum != n || start_block_entries(nl, nb * kStartBlock) != 0u) return __LINE__;
+    }
+    for (uint32_t g = g_lo; g <= g_hi && g != 0u; ++g) {
+        const size_t bytes = start_table_bytes(g, waves);
+        size_t expect = 0;
+        for (uint32_t wg = 0; wg < g; ++wg) for (uint32_t w = 0; w < waves; ++w) for (uint32_t e = 0; e < kStartBlock; ++e) {
+            const size_t off = start_rec_off(wg, waves, w, e);
+            if (off != expect || off + kStartRecBytes > bytes) return __LINE__;
+            expect = off + kStartRecBytes;
+        }
+        if (expect != bytes) return __LINE__;
+        // the context's sixteen tables: the stride comes from the ALLOCATION, so tables of launches with different grids never meet —
+        // slot s holds a table of any grid up to g, slot s + 1 one of g itself
+        const size_t cap = start_alloc_bytes(bytes), stride = start_slot_stride(cap);
+        if (stride < bytes || stride % 16u != 0u || stride * kStartSlots > cap) return __LINE__;
+        for (uint32_t s = 0; s + 1u < kStartSlots; ++s)
+            for (uint32_t g2 : { 1u, g / 2u + 1u, g })
+                if (start_slot_off(stride, s) + start_table_bytes(g2, waves) > start_slot_off(stride, s + 1u)) return __LINE__;
+        if (start_slot_off(stride, kStartSlots - 1u) + bytes > cap) return __LINE__;
+    }
+    return 0;
+}
