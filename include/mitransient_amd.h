@@ -626,6 +626,38 @@ int  mtr_film_develop(mtr_ctx *, const mtr_film_desc *,
 int  mtr_splat_add(mtr_ctx *, const mtr_splat_soa *, const mtr_film_desc *, int variant,
                    float *transient_hwt4 /*device*/, float *elapsed_ms /*host, may be NULL*/);
 
+/* Backprojection of a NLOS capture into a voxel volume (additive, ABI 24: a new entry point and a new struct; no struct that
+ * exists changes and nothing a caller of ABI 24 uses moves, so MTR_ABI_VERSION stays 24).
+ *   capture   n_sensor relay-wall points P_s (film order [y][x]), n_laser illuminated points P_l, temporal_bins bins of
+ *             bin_width_opl from start_opl.  MTR_CAPTURE_CONFOCAL (n_laser = n_sensor): pairs (s, s), capture (S, T);
+ *             MTR_CAPTURE_SINGLE (n_laser = 1): pairs (s, 0), capture (S, T); MTR_CAPTURE_EXHAUSTIVE: every (s, l), capture
+ *             (S, L, T) — the exhaustive_scan film's order [y][x][laser_x][laser_y][t] with l = laser_x * Ly + laser_y.
+ *   value     voxel centre v = volume_min + (i + 0.5) (volume_max - volume_min) / n; path length
+ *             d = |P_s - v| + |v - P_l| + sensor_offset[s] + laser_offset[l] (the sensor -> wall and laser -> wall legs of a
+ *             capture rendered with account_first_and_last_bounces, zeros otherwise); u = (d - start_opl) / bin_width_opl;
+ *             NEAREST reads bin floor(u) (the bin a rendered contribution of that length was splatted into), LINEAR
+ *             interpolates between the bin centres on either side; a tap outside [0, T) contributes 0.  volume (nz, ny, nx)
+ *             f32 is STORED: the sum over the voxel's pairs in ascending (s, l) order — a fixed order, the same bits every call.
+ * All pointers are device pointers (f32, contiguous).  Runs on the context's stream and does not synchronise it, except to grow
+ * the context's workspace when few voxels meet many pairs (mtr_ctx_trim releases it).  MTR_ERR_INVALID before any launch, the
+ * volume untouched: a zero size, n_laser != n_sensor on Confocal, n_laser != 1 on Single, bin_width_opl <= 0, a NULL pointer, an
+ * empty box (volume_max <= volume_min on an axis), an unknown capture type or interpolation. */
+enum { MTR_BACKPROJECT_NEAREST = 0, MTR_BACKPROJECT_LINEAR = 1 };
+typedef struct mtr_backproject_desc {
+    uint32_t capture_type;          /* MTR_CAPTURE_*                                  */
+    uint32_t interpolation;         /* MTR_BACKPROJECT_*                              */
+    uint32_t n_sensor, n_laser;     /* S, L                                           */
+    uint32_t temporal_bins;         /* T                                              */
+    float    start_opl, bin_width_opl;
+    float    volume_min[3], volume_max[3];
+    uint32_t nx, ny, nz;
+    const float *sensor_points;     /* (S, 3) device                                  */
+    const float *laser_points;      /* (L, 3) device                                  */
+    const float *sensor_offset;     /* (S) device                                     */
+    const float *laser_offset;      /* (L) device                                     */
+} mtr_backproject_desc;
+int  mtr_backproject(mtr_ctx *, const mtr_backproject_desc *, const float *capture_dev, float *volume_dev);
+
 /* Release the device workspaces the context keeps between calls (ABI 10: the partition workspace of mtr_splat_add on
  * unsorted input — 32 bytes per contribution; a workspace above 256 MiB is released by the call itself, a smaller one
  * stays with the context; ABI 24: the slabs' rows of MTR_MODE_SAMPLES, under the same rule).  Synchronises the context's stream. */

@@ -97,6 +97,19 @@ class mtr_nlos_desc(C.Structure):
                 ("sensor_is_confocal", C.c_uint32), ("sensor_target", _f3)]
 
 
+MTR_BACKPROJECT_NEAREST, MTR_BACKPROJECT_LINEAR = 0, 1
+
+
+class mtr_backproject_desc(C.Structure):          # (additive, ABI 24)
+    _fields_ = [("capture_type", C.c_uint32), ("interpolation", C.c_uint32),
+                ("n_sensor", C.c_uint32), ("n_laser", C.c_uint32), ("temporal_bins", C.c_uint32),
+                ("start_opl", C.c_float), ("bin_width_opl", C.c_float),
+                ("volume_min", _f3), ("volume_max", _f3),
+                ("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32),
+                ("sensor_points", C.c_void_p), ("laser_points", C.c_void_p),
+                ("sensor_offset", C.c_void_p), ("laser_offset", C.c_void_p)]
+
+
 class mtr_scene_desc(C.Structure):
     _fields_ = [("n_tris", C.c_uint32),
                 ("tri_verts", C.POINTER(C.c_float)),
@@ -166,6 +179,7 @@ EXPORTS = [
     "mtr_render_fwd", "mtr_render_fwd_tier",
     "mtr_scene_tint_layout", "mtr_scene_set_tints", "mtr_render_grad_tint", "mtr_render_fwd_tint",
     "mtr_scene_set_camera", "mtr_render_samples_plan",
+    "mtr_backproject",
 ]
 
 _lib = None
@@ -229,6 +243,7 @@ def load_library() -> C.CDLL:
     lib.mtr_render_fwd_tint.argtypes = [vp, C.POINTER(mtr_render_params), vp, vp, vp, vp, vp, vp]
     lib.mtr_scene_set_camera.argtypes = [vp, C.POINTER(mtr_camera)]      # (ABI 24)
     lib.mtr_render_samples_plan.argtypes = [vp, C.POINTER(mtr_render_params)] + [C.POINTER(C.c_uint32)] * 4
+    lib.mtr_backproject.argtypes = [vp, C.POINTER(mtr_backproject_desc), vp, vp]      # (additive, ABI 24)
     if lib.mtr_abi_version() != MTR_ABI_VERSION:
         raise MitransientAMDError("libmitransient_amd.so ABI version mismatch; rebuild")
     _lib = lib

@@ -13,6 +13,7 @@
 #include "mtr_fwd_args.h"
 #include "mtr_tint_args.h"
 #include "mtr_samples_args.h"
+#include "mtr_backproject.h"
 
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -43,6 +44,7 @@ struct mtr_ctx {
     void *d_part = nullptr; size_t part_cap = 0;         // ... and the partition workspace of unsorted input (at most 256 MiB of it kept between calls, until mtr_ctx_trim / destroy)
     void *d_samples = nullptr; size_t samples_cap = 0;   // MTR_MODE_SAMPLES: the slabs' rows (at most 256 MiB kept between calls, until mtr_ctx_trim / destroy)
     void *d_start = nullptr; size_t start_cap = 0;       // k_fused's lean kernels: kStartSlots path-start tables (mtr_start_blocks.h), one per ticket counter of the rotation (until mtr_ctx_trim / destroy)
+    void *d_bp = nullptr; size_t bp_cap = 0;             // mtr_backproject: the slabs' planes of a call with few voxels and many pairs (until mtr_ctx_trim / destroy)
 };
 
 struct WfWorkspace {            // MTR_MODE_WAVEFRONT buffers, sized for one tile, reused across renders
@@ -144,7 +146,7 @@ void mtr_ctx_destroy(mtr_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (void *p : { (void *)c->d_counters, (void *)c->d_ticket, (void *)c->d_freq, c->d_runs, c->d_part, c->d_samples, c->d_start, (void *)c->d_band_count }) if (p) (void)hipFree(p);
+    for (void *p : { (void *)c->d_counters, (void *)c->d_ticket, (void *)c->d_freq, c->d_runs, c->d_part, c->d_samples, c->d_start, c->d_bp, (void *)c->d_band_count }) if (p) (void)hipFree(p);
     for (hipEvent_t e : { c->ev0, c->ev1, c->ev2, c->ev3 }) if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -1313,6 +1315,22 @@ int mtr_ctx_trim(mtr_ctx *c)
     c->d_samples = nullptr; c->samples_cap = 0;
     if (c->d_start) (void)hipFree(c->d_start);
     c->d_start = nullptr; c->start_cap = 0;
+    if (c->d_bp) (void)hipFree(c->d_bp);
+    c->d_bp = nullptr; c->bp_cap = 0;
+    return MTR_OK;
+}
+
+int mtr_backproject(mtr_ctx *c, const mtr_backproject_desc *d, const float *capture, float *volume)
+{
+    if (!c) return fail(nullptr, MTR_ERR_INVALID, "mtr_backproject: ctx is NULL");
+    if (const char *why = bp_check(d, capture, volume)) return fail(c, MTR_ERR_INVALID, std::string("mtr_backproject: ") + why);
+    const BpArgs a = bp_args(*d, capture);
+    BpPlan pl;
+    if (!bp_plan(a.nx, a.ny, a.nz, a.n_pairs, c->n_cu, pl)) return fail(c, MTR_ERR_INVALID, "mtr_backproject: the volume has too many voxels for one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (pl.n_slabs > 1u)
+        if (int r = grow_device_buffer(c, &c->d_bp, &c->bp_cap, (size_t)pl.n_slabs * a.nx * a.ny * a.nz * sizeof(float))) return r;
+    HIP_TRY(c, launch_backproject(a, pl, (float *)c->d_bp, volume, c->stream));
     return MTR_OK;
 }
 
