@@ -16,10 +16,12 @@
 #include "mtr_backproject.h"
 
 #include <hip/hip_runtime.h>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <initializer_list>
 #include <string>
 #include <vector>
 #include <algorithm>
@@ -991,6 +993,67 @@ int mtr_render_plan(mtr_scene *s, const mtr_render_params *p, uint32_t *mode_out
     return MTR_OK;
 }
 
+// ---- what the derivative entry points (render_grad, render_fwd) share -------------------------
+// the tint slot table of the scene's materials (tint_slot_table, mtr_scene_host.h: 2 n_mats + 2 entries) and the number of slots
+static int scene_tint_slots(mtr_scene *s, std::vector<int32_t> &slots, uint32_t *n_tints)
+{
+    mtr_ctx *c = s->ctx;
+    const uint32_t n_m = s->dev.n_mats;
+    std::vector<mtr_material> mats(n_m);
+    slots.assign(2u * (size_t)n_m + 2u, -1);
+    if (n_m) HIP_TRY(c, hipMemcpy(mats.data(), s->dev.mats, n_m * sizeof(mtr_material), hipMemcpyDeviceToHost));
+    *n_tints = tint_slot_table(mats.data(), n_m, slots.data());
+    return MTR_OK;
+}
+
+// the first n_e emitters of the scene with unit radiance — what a derivative kernel traces: a contribution without its radiance
+// factor — and the true radiances beside them: rad holds 3 n_rad + 3 words (n_rad >= n_e; the NLOS tier's one "emitter" is the
+// laser, which the caller fills in), the first 3 n_e of them set here
+static int unit_emitters(mtr_scene *s, uint32_t n_e, uint32_t n_rad, std::vector<Emitter> &ems, std::vector<float> &rad)
+{
+    mtr_ctx *c = s->ctx;
+    ems.resize(n_e);
+    rad.assign(3u * (size_t)n_rad + 3u, 0.0f);
+    if (n_e) HIP_TRY(c, hipMemcpy(ems.data(), s->dev.ems, n_e * sizeof(Emitter), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ems.size(); ++i)
+        for (int k = 0; k < 3; ++k) { rad[3u * i + k] = ems[i].radiance[k]; ems[i].radiance[k] = 1.0f; }
+    return MTR_OK;
+}
+
+// One device allocation handed out in 256-byte-aligned pieces: alloc() takes the sizes of the pieces, take() hands them out in
+// that order (NULL for a piece past what alloc() was told: a caller's launch then fails on its own checks instead of writing
+// outside the block).  release() waits for the context's stream, frees the block and returns what the wait said; the destructor
+// does the same for a caller that returns early.
+struct Workspace {
+    mtr_ctx *c;
+    unsigned char *base = nullptr;
+    size_t used = 0, cap = 0;
+    explicit Workspace(mtr_ctx *ctx) : c(ctx) {}
+    Workspace(const Workspace &) = delete;
+    Workspace &operator=(const Workspace &) = delete;
+    static size_t piece(size_t bytes) { return (bytes + 255u) & ~(size_t)255u; }
+    hipError_t alloc(std::initializer_list<size_t> pieces)
+    {
+        for (size_t b : pieces) cap += piece(b);
+        return hipMalloc((void **)&base, cap);
+    }
+    void *take(size_t bytes)
+    {
+        assert(used + piece(bytes) <= cap && "Workspace::take beyond what alloc() was told");
+        if (used + piece(bytes) > cap) return nullptr;
+        void *p = base + used; used += piece(bytes); return p;
+    }
+    hipError_t release()
+    {
+        if (!base) return hipSuccess;
+        const hipError_t e_sync = hipStreamSynchronize(c->stream);
+        (void)hipFree(base);
+        base = nullptr;
+        return e_sync;
+    }
+    ~Workspace() { (void)release(); }
+};
+
 // mtr_render_grad (grad_texels == nullptr), mtr_render_grad_tex and mtr_render_grad_tint (grad_tints != nullptr)
 static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_s, const float *g_t,
                        float *grad_materials, float *grad_emitters, float *grad_texels, float *grad_tints = nullptr)
@@ -1023,10 +1086,7 @@ static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_
     std::vector<int32_t> slots;
     uint32_t n_tints = 0u;
     if (grad_tints) {
-        std::vector<mtr_material> mats(n_m);
-        slots.assign(2u * (size_t)n_m + 2u, -1);
-        if (n_m) HIP_TRY(c, hipMemcpy(mats.data(), s->dev.mats, n_m * sizeof(mtr_material), hipMemcpyDeviceToHost));
-        n_tints = tint_slot_table(mats.data(), n_m, slots.data());
+        if (int r = scene_tint_slots(s, slots, &n_tints)) return r;
         if (n_tints == 0u) grad_tints = nullptr;
     }
     if (grad_tints && grad_texels) {
@@ -1048,34 +1108,31 @@ static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_
     }
     // the traced emitter table carries unit radiance (a contribution without its radiance factor); the true radiance goes alongside
     // (the NLOS tier: the walk runs with unit irradiance, and the laser's true irradiance is the one entry of `rad`)
-    std::vector<Emitter> ems(nlos ? 0u : n_e);
-    std::vector<float> rad(3u * (size_t)n_e + 3u, 0.0f);
+    std::vector<Emitter> ems;
+    std::vector<float> rad;
+    if (int r = unit_emitters(s, nlos ? 0u : n_e, n_e, ems, rad)) return r;
     NlosConst nlos_unit{};
     if (nlos) {
         nlos_unit = s->nlos.k;
         rad[0] = nlos_unit.l_irr.x; rad[1] = nlos_unit.l_irr.y; rad[2] = nlos_unit.l_irr.z;
         nlos_unit.l_irr = mk(1, 1, 1);
     }
-    if (!ems.empty()) HIP_TRY(c, hipMemcpy(ems.data(), s->dev.ems, n_e * sizeof(Emitter), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < ems.size(); ++i)
-        for (int k = 0; k < 3; ++k) { rad[3u * i + k] = ems[i].radiance[k]; ems[i].radiance[k] = 1.0f; }
-    const size_t partial_b = ((size_t)grid * (slab_n + 3u * slab_tx) * sizeof(double) + 255u) & ~(size_t)255u;
-    const size_t ems_b = ((size_t)ems.size() * sizeof(Emitter) + 255u) & ~(size_t)255u;
+    const size_t ems_b = ems.size() * sizeof(Emitter), rad_b = rad.size() * sizeof(float);
+    const size_t partial_b = (size_t)grid * (slab_n + 3u * slab_tx) * sizeof(double);
     const size_t acc_b = tier == MTR_GRAD_TEX_GLOBAL ? (size_t)n_tx * 3u * sizeof(double) : 0u;      // the global tier's f64 sums
     const size_t slots_b = grad_tints ? slots.size() * sizeof(int32_t) : 0u;                         // the tint slot table
-    const size_t ws_b = ems_b + ((rad.size() * sizeof(float) + 255u) & ~(size_t)255u) + partial_b + acc_b + slots_b;
-    unsigned char *ws = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&ws, ws_b));
-    Emitter *d_ems = (Emitter *)ws;
-    float *d_rad = (float *)(ws + ems_b);
-    double *d_partial = (double *)(ws + ems_b + ((rad.size() * sizeof(float) + 255u) & ~(size_t)255u));
-    double *d_acc = acc_b ? (double *)((unsigned char *)d_partial + partial_b) : nullptr;
-    int32_t *d_slots = slots_b ? (int32_t *)((unsigned char *)d_partial + partial_b + acc_b) : nullptr;
+    Workspace ws(c);
+    HIP_TRY(c, ws.alloc({ ems_b, rad_b, partial_b, acc_b, slots_b }));
+    Emitter *d_ems = (Emitter *)ws.take(ems_b);
+    float *d_rad = (float *)ws.take(rad_b);
+    double *d_partial = (double *)ws.take(partial_b);
+    double *d_acc = acc_b ? (double *)ws.take(acc_b) : nullptr;
+    int32_t *d_slots = slots_b ? (int32_t *)ws.take(slots_b) : nullptr;
     hipError_t e = hipSuccess;
     if (d_acc) e = hipMemsetAsync(d_acc, 0, acc_b, c->stream);
     if (d_slots && e == hipSuccess) e = hipMemcpy(d_slots, slots.data(), slots_b, hipMemcpyHostToDevice);
-    if (!ems.empty() && e == hipSuccess) e = hipMemcpy(d_ems, ems.data(), ems.size() * sizeof(Emitter), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_rad, rad.data(), rad.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (!ems.empty() && e == hipSuccess) e = hipMemcpy(d_ems, ems.data(), ems_b, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rad, rad.data(), rad_b, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const RenderConst rc = make_render_const(*p, f, s->dev.n_ems);
         GradConst gc;
@@ -1085,11 +1142,10 @@ static int render_grad(mtr_scene *s, const mtr_render_params *p, const float *g_
             e = launch_grad_tint(s->dev, d_ems, s->cam, f, rc, gc, p->pixel_begin, n_pixels, p->spp_begin, chunk, d_partial, grid, lds,
                                  scene_lds, grad_materials, grad_emitters, n_tints, d_slots, grad_tints, c->stream);
         else
-        e = launch_grad(s->dev, d_ems, s->cam, f, rc, gc, p->pixel_begin, n_pixels, p->spp_begin, chunk, d_partial, grid, lds,
-                        scene_lds, grad_materials, grad_emitters, c->stream, tier, n_tx, d_acc, grad_texels, nlos ? &nlos_unit : nullptr);
+            e = launch_grad(s->dev, d_ems, s->cam, f, rc, gc, p->pixel_begin, n_pixels, p->spp_begin, chunk, d_partial, grid, lds,
+                            scene_lds, grad_materials, grad_emitters, c->stream, tier, n_tx, d_acc, grad_texels, nlos ? &nlos_unit : nullptr);
     }
-    const hipError_t e_sync = hipStreamSynchronize(c->stream);
-    (void)hipFree(ws);
+    const hipError_t e_sync = ws.release();
     HIP_TRY(c, e);
     HIP_TRY(c, e_sync);
     return MTR_OK;
@@ -1151,33 +1207,29 @@ static int render_fwd(mtr_scene *s, const mtr_render_params *p, const float *tan
     HIP_TRY(c, hipSetDevice(c->device));
     std::vector<int32_t> slots;
     if (tan_tints) {
-        const uint32_t n_m = s->dev.n_mats;
-        std::vector<mtr_material> mats(n_m);
-        slots.assign(2u * (size_t)n_m + 2u, -1);
-        if (n_m) HIP_TRY(c, hipMemcpy(mats.data(), s->dev.mats, n_m * sizeof(mtr_material), hipMemcpyDeviceToHost));
-        if (tint_slot_table(mats.data(), n_m, slots.data()) == 0u) tan_tints = nullptr;
+        uint32_t n_tints = 0u;
+        if (int r = scene_tint_slots(s, slots, &n_tints)) return r;
+        if (n_tints == 0u) tan_tints = nullptr;
     }
     FwdPlan pl{};
     if (!fwd_plan(s->dev, f, n_pixels, p->spp_total, c->n_cu, pl))
         return fail(c, MTR_ERR_UNSUPPORTED, "mtr_render_fwd: the traversal stack and the staged scene exceed LDS");
     // the traced emitter table carries unit radiance; the true radiance goes alongside (as mtr_render_grad)
     const uint32_t n_e = s->dev.n_ems;
-    std::vector<Emitter> ems(n_e);
-    std::vector<float> rad(3u * (size_t)n_e + 3u, 0.0f);
-    if (n_e) HIP_TRY(c, hipMemcpy(ems.data(), s->dev.ems, n_e * sizeof(Emitter), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < ems.size(); ++i)
-        for (int k = 0; k < 3; ++k) { rad[3u * i + k] = ems[i].radiance[k]; ems[i].radiance[k] = 1.0f; }
-    const size_t ems_b = ((size_t)n_e * sizeof(Emitter) + 255u) & ~(size_t)255u;
-    const size_t rad_b = (rad.size() * sizeof(float) + 255u) & ~(size_t)255u;
-    unsigned char *ws = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&ws, ems_b + rad_b + (tan_tints ? slots.size() * sizeof(int32_t) : 0u)));
-    Emitter *d_ems = (Emitter *)ws;
-    float *d_rad = (float *)(ws + ems_b);
-    int32_t *d_slots = (int32_t *)(ws + ems_b + rad_b);
+    std::vector<Emitter> ems;
+    std::vector<float> rad;
+    if (int r = unit_emitters(s, n_e, n_e, ems, rad)) return r;
+    const size_t ems_b = ems.size() * sizeof(Emitter), rad_b = rad.size() * sizeof(float);
+    const size_t slots_b = tan_tints ? slots.size() * sizeof(int32_t) : 0u;
+    Workspace ws(c);
+    HIP_TRY(c, ws.alloc({ ems_b, rad_b, slots_b }));
+    Emitter *d_ems = (Emitter *)ws.take(ems_b);
+    float *d_rad = (float *)ws.take(rad_b);
+    int32_t *d_slots = (int32_t *)ws.take(slots_b);
     hipError_t e = hipSuccess;
-    if (tan_tints) e = hipMemcpy(d_slots, slots.data(), slots.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (n_e && e == hipSuccess) e = hipMemcpy(d_ems, ems.data(), n_e * sizeof(Emitter), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_rad, rad.data(), rad.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (tan_tints) e = hipMemcpy(d_slots, slots.data(), slots_b, hipMemcpyHostToDevice);
+    if (n_e && e == hipSuccess) e = hipMemcpy(d_ems, ems.data(), ems_b, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_rad, rad.data(), rad_b, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const RenderConst rc = make_render_const(*p, f, n_e);
         FwdConst fc;
@@ -1187,10 +1239,9 @@ static int render_fwd(mtr_scene *s, const mtr_render_params *p, const float *tan
             e = launch_fwd_tint(s->dev, d_ems, s->cam, f, rc, fc, p->pixel_begin, p->pixel_end, p->spp_total, pl, d_slots, tan_tints,
                                 steady_hw3, transient_hwt3, c->stream);
         else
-        e = launch_fwd(s->dev, d_ems, s->cam, f, rc, fc, p->pixel_begin, p->pixel_end, p->spp_total, pl, steady_hw3, transient_hwt3, c->stream);
+            e = launch_fwd(s->dev, d_ems, s->cam, f, rc, fc, p->pixel_begin, p->pixel_end, p->spp_total, pl, steady_hw3, transient_hwt3, c->stream);
     }
-    const hipError_t e_sync = hipStreamSynchronize(c->stream);
-    (void)hipFree(ws);
+    const hipError_t e_sync = ws.release();
     HIP_TRY(c, e);
     HIP_TRY(c, e_sync);
     return MTR_OK;

@@ -562,6 +562,7 @@ void build_bvh(const float *verts, uint32_t n, const BvhPrims *prims, BvhBuild &
     // (fused_plan / wf_plan), so no scene above 546 triangles is ever walked in LDS — the choice is made on exactly that bound.
     // (The quantised HBM trees are still built for small scenes — a handful of nodes — because k_nlos_prepare and the
     // HBM instantiations requested explicitly walk them.)
+    // (this file builds without the HIP headers: the literal is scene_fits_lds()'s bound, mtr_kernels.h)
     const bool never_in_lds = (size_t)n * (sizeof(TriShade) + sizeof(TriPair) / 2) > 64u * 1024u;
     // (before the spatial splits four triangles per leaf were best for the large scenes — config 5 at 256 spp, 1 / 2 / 3 / 4: 335 / 288 /
     // 283 / 275 ms; with them 2 / 3 / 4: k_wf_trace 110.0 / 116.1 / 113.9 ms)

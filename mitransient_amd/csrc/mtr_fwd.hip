@@ -5,7 +5,7 @@
 //
 //   k_fwd_paths<SCENE_LDS, EXT, ROWS>   one lane per (pixel, sample), lane identity = RNG identity; the lane's path is walked ONCE
 //                  through the general shading code with its log-derivative (fwd_walk), over the scene staged in LDS (when the
-//                  tables fit 64 KB) or walked in HBM — staging and stack as k_grad_paths.
+//                  tables fit: scene_fits_lds) or walked in HBM — stage_scene (mtr_kernels.h); the stack as k_grad_paths.
 //   rows tier      a workgroup owns RUNS of G consecutive pixels (fwd_plan): run r = pixels [begin + r G, begin + (r + 1) G), its
 //                  lanes i = slot * spp + s over trips of 256 — several pixels at once when spp < 256, several trips per pixel when
 //                  spp > 256.  Every pixel in flight has an f32 LDS row of T x 3 words + 3 steady words; tangents arrive by
@@ -34,30 +34,7 @@ __global__ void __launch_bounds__(kBlock) k_fwd_paths(const FwdArgs a)
     float *s_rows = (float *)smem; off += ROWS ? al16(a.G * row_words * 4u) : 0u;
     int32_t *s_stack = (int32_t *)(smem + off); off += a.stack_rows * kBlock * 4u;
     if (ROWS) for (uint32_t i = tid; i < a.G * row_words; i += kBlock) s_rows[i] = 0.0f;
-    const SceneDev &sc = a.sc;
-    SceneView sv;
-    sv.n_emitters = sc.n_ems; sv.n_slots = sc.n_slots;
-    sv.samp_tris = sc.samp_tris; sv.samp_vn = sc.samp_vn; sv.face_pmf = sc.face_pmf; sv.face_cdf = sc.face_cdf; sv.vnormals = sc.vnormals;
-    sv.texels = sc.texels; sv.tex_info = sc.tex_info; sv.uvs = sc.uvs;
-    sv.flat_off = 0u;                                   // (the flat top-level walk is not instantiated here)
-    if (SCENE_LDS) {
-        WNode *n = (WNode *)(smem + off); off += al16(sc.n_wnodes * sizeof(WNode));
-        TriPair *tg = (TriPair *)(smem + off); off += al16(sc.n_slots / 2 * sizeof(TriPair));
-        TriShade *ts = (TriShade *)(smem + off); off += al16(sc.n_slots * sizeof(TriShade));
-        mtr_material *mm = (mtr_material *)(smem + off); off += al16(sc.n_mats * sizeof(mtr_material));
-        Emitter *ee = (Emitter *)(smem + off); off += al16(sc.n_ems * sizeof(Emitter));
-        cp16(n, sc.wnodes, al16(sc.n_wnodes * sizeof(WNode)), tid);
-        cp16(tg, sc.tpairs, al16(sc.n_slots / 2 * sizeof(TriPair)), tid);
-        cp16(ts, sc.tshade, al16(sc.n_slots * sizeof(TriShade)), tid);
-        cp16(mm, sc.mats, al16(sc.n_mats * sizeof(mtr_material)), tid);
-        cp16(ee, a.ems_unit, al16(sc.n_ems * sizeof(Emitter)), tid);
-        sv.nodes = nullptr; sv.wnodes = n; sv.wnodes4 = nullptr; sv.wnodes8q = nullptr; sv.tpairs = tg; sv.tshade = ts; sv.mats = mm; sv.ems = ee;
-        sv.node_pairs = true;
-    } else {
-        sv.nodes = sc.nodes; sv.tpairs = sc.tpairs; sv.tshade = sc.tshade; sv.mats = sc.mats; sv.ems = a.ems_unit;
-        sv.wnodes = nullptr; sv.wnodes4 = sc.wnodes4; sv.wnodes8q = sc.wnodes8q;
-        sv.node_pairs = false;
-    }
+    const SceneView sv = stage_scene<SCENE_LDS>(a.sc, a.ems_unit, smem, off, tid);
     __syncthreads();
     WStack st; st.base = s_stack + tid; st.sp = 0;
     if constexpr (ROWS) {
@@ -115,17 +92,14 @@ __global__ void __launch_bounds__(kBlock) k_fwd_zero(const FwdArgs a)
     }
 }
 
-template <bool SL, bool EXT, bool ROWS>
-hipError_t launch_paths(const FwdArgs &a, int grid, size_t lds, hipStream_t stream)
+template <bool ROWS>
+hipError_t launch_paths(const FwdArgs &a, bool sl, bool ext, int grid, size_t lds, hipStream_t stream)
 {
-    auto k = k_fwd_paths<SL, EXT, ROWS>;
-    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, stream, a);
-    return hipGetLastError();
+    return sl ? (ext ? launch_with_lds(k_fwd_paths<true, true, ROWS>, a, grid, lds, stream)
+                     : launch_with_lds(k_fwd_paths<true, false, ROWS>, a, grid, lds, stream))
+              : (ext ? launch_with_lds(k_fwd_paths<false, true, ROWS>, a, grid, lds, stream)
+                     : launch_with_lds(k_fwd_paths<false, false, ROWS>, a, grid, lds, stream));
 }
-
-constexpr uint32_t kLdsCu = 160u * 1024u;
 
 } // namespace
 
@@ -139,7 +113,7 @@ hipError_t launch_fwd_zero(const FwdArgs &a, hipStream_t stream)
 uint32_t fwd_tier(const SceneDev &sc, const Film &film)
 {
     const uint32_t scene_b = lds_scene_bytes(sc);
-    const bool scene_lds = sc.wnodes != nullptr && scene_b <= 64u * 1024u;
+    const bool scene_lds = scene_fits_lds(sc);
     const uint64_t fixed = (uint64_t)wf_stack_rows(sc, scene_lds) * kBlock * 4u + (scene_lds ? scene_b : 0u);
     const uint64_t row_b = ((3ull * film.bins + 3ull) * 4ull + 15ull) & ~15ull;
     return fixed + row_b <= kLdsCu ? MTR_FWD_ROWS : MTR_FWD_GLOBAL;
@@ -151,7 +125,7 @@ uint32_t fwd_tier(const SceneDev &sc, const Film &film)
 bool fwd_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t spp, int n_cu, FwdPlan &pl)
 {
     const uint32_t scene_b = lds_scene_bytes(sc);
-    pl.scene_lds = sc.wnodes != nullptr && scene_b <= 64u * 1024u;
+    pl.scene_lds = scene_fits_lds(sc);
     pl.stack_rows = wf_stack_rows(sc, pl.scene_lds);
     const uint64_t fixed = (uint64_t)pl.stack_rows * kBlock * 4u + (pl.scene_lds ? scene_b : 0u);
     if (fixed > kLdsCu) return false;
@@ -185,25 +159,29 @@ bool fwd_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t 
     return true;
 }
 
-hipError_t launch_fwd(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
+FwdArgs make_fwd_args(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
                       const FwdConst &fc, uint32_t pixel_begin, uint32_t pixel_end, uint32_t spp, const FwdPlan &pl,
-                      float *steady, float *transient, hipStream_t stream)
+                      float *steady, float *transient)
 {
-    if (pixel_begin >= pixel_end || spp == 0u) return hipSuccess;
     FwdArgs a{};
     a.sc = sc; a.ems_unit = ems_unit; a.cam = cam; a.film = film; a.rc = rc; a.fc = fc;
     a.pixel_begin = pixel_begin; a.pixel_end = pixel_end; a.spp = spp; a.div_spp = fastdiv_make(spp);
     a.G = pl.G; a.n_runs = pl.n_runs; a.stack_rows = pl.stack_rows;
     a.steady = steady; a.transient = transient;
-    const bool ext = sc.has_rough != 0u, sl = pl.scene_lds;
-    const int grid = (int)pl.grid;
-    if (pl.tier == MTR_FWD_ROWS)
-        return sl ? (ext ? launch_paths<true, true, true>(a, grid, pl.lds, stream) : launch_paths<true, false, true>(a, grid, pl.lds, stream))
-                  : (ext ? launch_paths<false, true, true>(a, grid, pl.lds, stream) : launch_paths<false, false, true>(a, grid, pl.lds, stream));
+    return a;
+}
+
+hipError_t launch_fwd(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
+                      const FwdConst &fc, uint32_t pixel_begin, uint32_t pixel_end, uint32_t spp, const FwdPlan &pl,
+                      float *steady, float *transient, hipStream_t stream)
+{
+    if (pixel_begin >= pixel_end || spp == 0u) return hipSuccess;
+    const FwdArgs a = make_fwd_args(sc, ems_unit, cam, film, rc, fc, pixel_begin, pixel_end, spp, pl, steady, transient);
+    const bool ext = sc.has_rough != 0u;
+    if (pl.tier == MTR_FWD_ROWS) return launch_paths<true>(a, pl.scene_lds, ext, (int)pl.grid, pl.lds, stream);
     hipError_t e = launch_fwd_zero(a, stream);
     if (e != hipSuccess) return e;
-    return sl ? (ext ? launch_paths<true, true, false>(a, grid, pl.lds, stream) : launch_paths<true, false, false>(a, grid, pl.lds, stream))
-              : (ext ? launch_paths<false, true, false>(a, grid, pl.lds, stream) : launch_paths<false, false, false>(a, grid, pl.lds, stream));
+    return launch_paths<false>(a, pl.scene_lds, ext, (int)pl.grid, pl.lds, stream);
 }
 
 } // namespace mtr

@@ -58,7 +58,7 @@ struct GlobalSink {
     }
 };
 
-// most workgroups of k_fwd_paths that a compute unit is asked to hold: what its registers allow (132 - 163 VGPRs: three waves per
+// most workgroups of k_fwd_paths that a compute unit is asked to hold: what its registers allow (138 - 165 VGPRs: three waves per
 // SIMD, a workgroup being one wave on each)
 constexpr int kFwdPerCu = 3;
 
@@ -78,6 +78,10 @@ bool fwd_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t 
 hipError_t launch_fwd(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
                       const FwdConst &fc, uint32_t pixel_begin, uint32_t pixel_end, uint32_t spp, const FwdPlan &pl,
                       float *steady, float *transient, hipStream_t stream);
+// the argument block of such a launch (launch_fwd, launch_fwd_tint)
+FwdArgs make_fwd_args(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
+                      const FwdConst &fc, uint32_t pixel_begin, uint32_t pixel_end, uint32_t spp, const FwdPlan &pl,
+                      float *steady, float *transient);
 
 // global tier: k_fwd_zero over the launch's pixels (clears their rows and steady words)
 hipError_t launch_fwd_zero(const FwdArgs &a, hipStream_t stream);

@@ -1,6 +1,8 @@
 // mtr_grad_nlos.hip — mtr_render_grad on the NLOS tier (ABI 17): k_grad_paths_nlos, the k_grad_paths of transient_nlos_path
 // (mtr_grad.h: grad_nlos_lane over mtr_nlos.h's nlos_bounce; semantics in DESIGN.md §2).  A translation unit of its own: the kernels
 // of mtr_grad.hip keep their instructions.  k_grad_reduce (mtr_grad.hip) sums the rows it stores.
+// The kernel stages its scene itself, not through stage_scene (mtr_kernels.h): with the helper its instructions move
+// (profiles/deriv_harness_asm_diff.txt), and no timing script reaches every form of the NLOS gradient kernels.
 #include "mtr_grad_args.h"
 
 namespace mtr {
@@ -60,23 +62,13 @@ __global__ void __launch_bounds__(kBlock, kGradNlosPerCu) k_grad_paths_nlos(cons
     for (uint32_t i = tid; i < slab_n; i += kBlock) row[i] = s_slab[i];
 }
 
-template <bool EXT>
-hipError_t launch_paths_nlos(const GradNlosArgs &a, int grid, size_t lds, hipStream_t stream)
-{
-    auto k = k_grad_paths_nlos<EXT>;
-    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, stream, a);
-    return hipGetLastError();
-}
-
 } // namespace
 
 hipError_t launch_grad_paths_nlos(const GradArgs &a, const NlosConst &nlos_unit, bool ext, int grid, size_t lds, hipStream_t stream)
 {
     GradNlosArgs n{};
     n.g = a; n.nlos = nlos_unit;
-    return ext ? launch_paths_nlos<true>(n, grid, lds, stream) : launch_paths_nlos<false>(n, grid, lds, stream);
+    return ext ? launch_with_lds(k_grad_paths_nlos<true>, n, grid, lds, stream) : launch_with_lds(k_grad_paths_nlos<false>, n, grid, lds, stream);
 }
 
 } // namespace mtr

@@ -1,7 +1,8 @@
 // mtr_grad_nlos_tex.hip — mtr_render_grad_tex on the NLOS tier (ABI 20): k_grad_paths_nlos_tex, k_grad_paths_nlos (mtr_grad_nlos.hip)
 // with the texel hook of mtr_grad.h (grad_nlos_lane over nlos_bounce with NlosGradTexHook; semantics in DESIGN.md §2) in the two
 // tiers of mtr_grad.hip.  A translation unit of its own: the kernels of mtr_grad.hip and mtr_grad_nlos.hip keep their instructions.
-// k_grad_reduce_tex (slab tier) or k_grad_reduce and k_grad_tex_store (global tier) of mtr_grad.hip follow it.
+// k_grad_reduce of mtr_grad.hip follows it (slab tier: the texel words its third segment), and k_grad_tex_store on the global tier.
+// The staging is k_grad_paths_nlos' own (see mtr_grad_nlos.hip).
 #include "mtr_grad_args.h"
 
 namespace mtr {
@@ -65,16 +66,6 @@ __global__ void __launch_bounds__(kBlock, kGradNlosPerCu) k_grad_paths_nlos_tex(
     for (uint32_t i = tid; i < slab_n; i += kBlock) row[i] = s_slab[i];
 }
 
-template <int TEX>
-hipError_t launch_paths_nlos_tex(const GradNlosArgs &a, int grid, size_t lds, hipStream_t stream)
-{
-    auto k = k_grad_paths_nlos_tex<TEX>;
-    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, stream, a);
-    return hipGetLastError();
-}
-
 } // namespace
 
 hipError_t launch_grad_paths_nlos_tex(const GradArgs &a, const NlosConst &nlos_unit, uint32_t tier, int grid, size_t lds, hipStream_t stream)
@@ -82,7 +73,8 @@ hipError_t launch_grad_paths_nlos_tex(const GradArgs &a, const NlosConst &nlos_u
     if (tier != MTR_GRAD_TEX_SLAB && tier != MTR_GRAD_TEX_GLOBAL) return hipErrorInvalidValue;
     GradNlosArgs n{};
     n.g = a; n.nlos = nlos_unit;
-    return tier == MTR_GRAD_TEX_SLAB ? launch_paths_nlos_tex<kTexSlab>(n, grid, lds, stream) : launch_paths_nlos_tex<kTexGlobal>(n, grid, lds, stream);
+    return tier == MTR_GRAD_TEX_SLAB ? launch_with_lds(k_grad_paths_nlos_tex<kTexSlab>, n, grid, lds, stream)
+                                     : launch_with_lds(k_grad_paths_nlos_tex<kTexGlobal>, n, grid, lds, stream);
 }
 
 } // namespace mtr

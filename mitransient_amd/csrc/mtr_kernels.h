@@ -89,6 +89,55 @@ __host__ __device__ inline uint32_t lds_scene_bytes(const SceneDev &sc)
     return al16(sc.n_wnodes * sizeof(WNode)) + al16(sc.n_slots / 2 * sizeof(TriPair)) + al16(sc.n_slots * sizeof(TriShade)) +
            al16(sc.n_mats * sizeof(mtr_material)) + al16(sc.n_ems * sizeof(Emitter));
 }
+// THE LDS RULES, shared by every kernel and its planner: a compute unit has 160 KiB, and a scene is staged when it has an 8-wide tree
+// and its tables take at most 64 KiB (mtr_bvh.cpp's never_in_lds follows the same bound)
+constexpr uint32_t kLdsCu = 160u * 1024u;
+__host__ __device__ inline bool scene_fits_lds(const SceneDev &sc) { return sc.wnodes != nullptr && lds_scene_bytes(sc) <= 64u * 1024u; }
+
+// The scene of a workgroup: staged in LDS at smem + off (lds_scene_bytes, in that order) or walked in HBM.  `ems` is the emitter
+// table the kernel traces (the scene's, or a unit-radiance copy).  flat_off: where SceneDev::flat sits in the kernel's argument
+// block, for the kernels that instantiate the flat top-level walk.  The caller synchronises before the first walk.
+// (`off` by value and the statements in this order: k_grad_paths, k_fwd_paths and the tint kernels compile to the instructions they
+// had with the block written out — profiles/deriv_harness_asm_diff.txt.)
+template <bool SCENE_LDS>
+__device__ __forceinline__ SceneView stage_scene(const SceneDev &sc, const Emitter *ems, unsigned char *smem, uint32_t off, int tid,
+                                                 uint32_t flat_off = 0u)
+{
+    SceneView sv;
+    sv.n_emitters = sc.n_ems; sv.n_slots = sc.n_slots;
+    sv.samp_tris = sc.samp_tris; sv.samp_vn = sc.samp_vn; sv.face_pmf = sc.face_pmf; sv.face_cdf = sc.face_cdf; sv.vnormals = sc.vnormals;
+    sv.texels = sc.texels; sv.tex_info = sc.tex_info; sv.uvs = sc.uvs;
+    sv.flat_off = flat_off;
+    if (SCENE_LDS) {
+        WNode *n = (WNode *)(smem + off); off += al16(sc.n_wnodes * sizeof(WNode));
+        TriPair *tg = (TriPair *)(smem + off); off += al16(sc.n_slots / 2 * sizeof(TriPair));
+        TriShade *ts = (TriShade *)(smem + off); off += al16(sc.n_slots * sizeof(TriShade));
+        mtr_material *mm = (mtr_material *)(smem + off); off += al16(sc.n_mats * sizeof(mtr_material));
+        Emitter *ee = (Emitter *)(smem + off);
+        cp16(n, sc.wnodes, al16(sc.n_wnodes * sizeof(WNode)), tid);
+        cp16(tg, sc.tpairs, al16(sc.n_slots / 2 * sizeof(TriPair)), tid);
+        cp16(ts, sc.tshade, al16(sc.n_slots * sizeof(TriShade)), tid);
+        cp16(mm, sc.mats, al16(sc.n_mats * sizeof(mtr_material)), tid);
+        cp16(ee, ems, al16(sc.n_ems * sizeof(Emitter)), tid);
+        sv.nodes = nullptr; sv.wnodes = n; sv.wnodes4 = nullptr; sv.wnodes8q = nullptr; sv.tpairs = tg; sv.tshade = ts; sv.mats = mm; sv.ems = ee;
+        sv.node_pairs = true;
+    } else {
+        sv.nodes = sc.nodes; sv.tpairs = sc.tpairs; sv.tshade = sc.tshade; sv.mats = sc.mats; sv.ems = ems;
+        sv.wnodes = nullptr; sv.wnodes4 = sc.wnodes4; sv.wnodes8q = sc.wnodes8q;
+        sv.node_pairs = false;
+    }
+    return sv;
+}
+
+// a kernel launch with `lds` bytes of dynamic LDS (above the 64 KiB a kernel gets unasked)
+template <class K, class A>
+hipError_t launch_with_lds(K kernel, const A &args, int grid, size_t lds, hipStream_t stream)
+{
+    hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, stream, args);
+    return hipGetLastError();
+}
 
 struct SplatLog { uint32_t *rec; unsigned long long cap; unsigned long long *count; };
 
@@ -216,7 +265,7 @@ hipError_t launch_develop(const Film &film, const float *t4, float *t3, const fl
 // the workgroup's f64 LDS slab when all of them take at most kGradTexSlabBytes (slab_texels of grad_grid = n_texels: the grid keeps
 // its occupancy rule over the larger slab), f64 global atomics into tex_acc otherwise.  8 KiB: a workgroup's share of the 160 KiB
 // when eight are resident is 20 KiB, of which the traversal stack takes 4-16 KiB — a larger texel slab would cost resident
-// workgroups on every scene staged in LDS; the rows of `partial` and k_grad_reduce_tex's pass grow with it as well.
+// workgroups on every scene staged in LDS; the rows of `partial` and k_grad_reduce's pass grow with it as well.
 struct GradConst;
 constexpr uint32_t kGradTexSlabBytes = 8u * 1024u;
 uint32_t grad_tex_tier(const SceneDev &sc, uint32_t n_texels, bool nlos = false);     // nlos: the laser's words in the slab

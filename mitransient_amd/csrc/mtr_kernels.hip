@@ -999,13 +999,12 @@ size_t fused_start_table_bytes(const FusedArgs &args, const FusedConfig &cfg)
 bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t spp_chunk, int n_cu,
                 FusedArgs &args, FusedConfig &cfg)
 {
-    const uint32_t kLdsMax = 160u * 1024u;
     int stack = sc.bvh_depth <= 8 ? 8 : sc.bvh_depth <= 16 ? 16 : sc.bvh_depth <= 32 ? 32 : 64;
     if (sc.bvh_depth > 64) return false;
     // (k_fused keeps a path's film coordinates packed in one register, 16 bits each)
     if ((uint64_t)film.crop_x + film.crop_w > 65536ull || (uint64_t)film.crop_y + film.crop_h > 65536ull) return false;
     uint32_t scene_b = scene_lds_bytes(sc);
-    cfg.scene_lds = sc.wnodes != nullptr && scene_b <= 64u * 1024u;
+    cfg.scene_lds = scene_fits_lds(sc);
     // the kernel walks a WIDE tree (8-wide in LDS, quantised 4-wide in HBM): one stacked group per level (+ the row the
     // branch-free push writes before it knows whether it counts)
     const uint32_t rows = wf_stack_rows(sc, cfg.scene_lds);
@@ -1030,7 +1029,7 @@ bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_
     cfg.hist_lds = true;
     uint32_t G;
     if (g_fit >= 1) G = g_want < g_fit ? g_want : g_fit;
-    else if (fixed_b + row_bytes + 64 <= kLdsMax) G = 1;                  // one long row still fits the CU
+    else if (fixed_b + row_bytes + 64 <= kLdsCu) G = 1;                  // one long row still fits the CU
     else { G = g_want; cfg.hist_lds = false; }                          // row > LDS: f32 atomics to HBM
     // phasor_hdr_film: the (Re, Im) rows are LDS rows or nothing (k_fused<PHASOR> has no global-atomic form) — a frequency table too long
     // for LDS beside the staged scene is the wavefront organisation's (resolve_mode)
@@ -1054,7 +1053,7 @@ bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_
     // that fits the most workgroups a CU can hold, and among those the largest (rounds 1 - 5 took as many slots as the row budget held).
     const int reg_cap = (cfg.rough || cfg.fixed || args.nlos_on) ? 3 : (int)MTR_FUSED_MIN_WAVES;
     auto lds_of = [&](uint32_t g) { return (size_t)fixed_b + align16(g * 32) + (cfg.fixed ? align16(g * 16) : 0u) + 2 * align16(g * 4) + (cfg.hist_lds ? (size_t)g * row_bytes : 0) + 16; };
-    auto per_cu_of = [&](uint32_t g) { const int p = (int)(kLdsMax / lds_of(g)); return p > reg_cap ? reg_cap : p; };
+    auto per_cu_of = [&](uint32_t g) { const int p = (int)(kLdsCu / lds_of(g)); return p > reg_cap ? reg_cap : p; };
     if (cfg.hist_lds) {
         uint32_t best = G;
         for (uint32_t g = G; g-- > 1u;) if (per_cu_of(g) > per_cu_of(best)) best = g;
@@ -1067,7 +1066,7 @@ bool fused_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_
     args.div_G = fastdiv_make(G); args.div_spp = fastdiv_make(spp_chunk);
     cfg.stack = stack;
     cfg.lds_bytes = lds_of(G);
-    if (cfg.lds_bytes > kLdsMax) return false;
+    if (cfg.lds_bytes > kLdsCu) return false;
     // persistent grid: as many workgroups as can be resident, each with at least g_want pixels
     int per_cu = per_cu_of(G);
     if (per_cu < 1) per_cu = 1;

@@ -5,7 +5,7 @@
 // looking along a line) or a film of a few pixels with millions of samples therefore runs on a handful of workgroups.  Here the
 // work item is (pixel, slab), a slab a contiguous range of the call's samples of that pixel (samples_plan):
 //
-//   k_samples_paths   a workgroup stages the scene as k_grad_paths does (LDS when it fits, HBM walk otherwise), keeps ONE row of
+//   k_samples_paths   a workgroup stages the scene with stage_scene (mtr_kernels.h: LDS when it fits, HBM walk otherwise), keeps ONE row of
 //                     3 T f32 time bins + steady RGB + sample count in LDS, walks the slab's lanes through path_bounce — the
 //                     general shading code, lane identity = RNG identity as every organisation — with an LDS-row sink, and
 //                     stores the row once to its own slot of `partial` (pixels, slabs, 3 T + 4).  No global atomics on the film.
@@ -47,30 +47,7 @@ __global__ void __launch_bounds__(kBlock) k_samples_paths(const SamplesArgs a)
     unsigned long long *s_cnt = (unsigned long long *)(smem + off); off += 48u;      // paths, closest, shadow, splats, bounces (DevCounters order)
     int32_t *s_stack = (int32_t *)(smem + off); off += a.stack_rows * kBlock * 4u;
     if (tid < 5) s_cnt[tid] = 0ull;
-    const SceneDev &sc = a.sc;
-    SceneView sv;
-    sv.n_emitters = sc.n_ems; sv.n_slots = sc.n_slots;
-    sv.samp_tris = sc.samp_tris; sv.samp_vn = sc.samp_vn; sv.face_pmf = sc.face_pmf; sv.face_cdf = sc.face_cdf; sv.vnormals = sc.vnormals;
-    sv.texels = sc.texels; sv.tex_info = sc.tex_info; sv.uvs = sc.uvs;
-    sv.flat_off = 0u;                                   // (the flat top-level walk is not instantiated here)
-    if (SCENE_LDS) {
-        WNode *n = (WNode *)(smem + off); off += al16(sc.n_wnodes * sizeof(WNode));
-        TriPair *tg = (TriPair *)(smem + off); off += al16(sc.n_slots / 2 * sizeof(TriPair));
-        TriShade *ts = (TriShade *)(smem + off); off += al16(sc.n_slots * sizeof(TriShade));
-        mtr_material *mm = (mtr_material *)(smem + off); off += al16(sc.n_mats * sizeof(mtr_material));
-        Emitter *ee = (Emitter *)(smem + off); off += al16(sc.n_ems * sizeof(Emitter));
-        cp16(n, sc.wnodes, al16(sc.n_wnodes * sizeof(WNode)), tid);
-        cp16(tg, sc.tpairs, al16(sc.n_slots / 2 * sizeof(TriPair)), tid);
-        cp16(ts, sc.tshade, al16(sc.n_slots * sizeof(TriShade)), tid);
-        cp16(mm, sc.mats, al16(sc.n_mats * sizeof(mtr_material)), tid);
-        cp16(ee, sc.ems, al16(sc.n_ems * sizeof(Emitter)), tid);
-        sv.nodes = nullptr; sv.wnodes = n; sv.wnodes4 = nullptr; sv.wnodes8q = nullptr; sv.tpairs = tg; sv.tshade = ts; sv.mats = mm; sv.ems = ee;
-        sv.node_pairs = true;
-    } else {
-        sv.nodes = sc.nodes; sv.tpairs = sc.tpairs; sv.tshade = sc.tshade; sv.mats = sc.mats; sv.ems = sc.ems;
-        sv.wnodes = nullptr; sv.wnodes4 = sc.wnodes4; sv.wnodes8q = sc.wnodes8q;
-        sv.node_pairs = false;
-    }
+    const SceneView sv = stage_scene<SCENE_LDS>(a.sc, a.sc.ems, smem, off, tid);      // (the first item's barrier covers it)
     WStack st; st.base = s_stack + tid; st.sp = 0;
     const bool unwarp = (a.rc.flags & MTR_FLAG_CAMERA_UNWARP) != 0u;
     const uint32_t n_items = a.n_pixels * a.n_slabs;
@@ -157,16 +134,6 @@ __global__ void __launch_bounds__(kBlock) k_samples_reduce(const SamplesArgs a)
     else *dst += acc;
 }
 
-template <bool SL, bool EXT>
-hipError_t launch_paths(const SamplesArgs &a, const SamplesPlan &pl, hipStream_t stream)
-{
-    auto k = k_samples_paths<SL, EXT>;
-    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(pl.grid), dim3(kBlock), pl.lds_bytes, stream, a);
-    return hipGetLastError();
-}
-
 } // namespace
 
 bool samples_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t spp_chunk, int n_cu, SamplesPlan &pl)
@@ -175,15 +142,15 @@ bool samples_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint3
     if (n_pixels == 0u || spp_chunk == 0u || n_cu <= 0) return false;
     const size_t row_b = al16(samples_row_words(film) * 4u) + 48u;               // the row and the workgroup's counters
     const uint32_t scene_b = lds_scene_bytes(sc);
-    bool scene_lds = sc.wnodes != nullptr && scene_b <= 64u * 1024u;
+    bool scene_lds = scene_fits_lds(sc);
     size_t lds = row_b + (size_t)wf_stack_rows(sc, scene_lds) * kBlock * 4u + (scene_lds ? scene_b : 0u);
-    if (scene_lds && lds > kSamplesLdsMax && sc.wnodes4 != nullptr) {             // a long row beside the scene: walk the scene in HBM
+    if (scene_lds && lds > kLdsCu && sc.wnodes4 != nullptr) {             // a long row beside the scene: walk the scene in HBM
         scene_lds = false;
         lds = row_b + (size_t)wf_stack_rows(sc, false) * kBlock * 4u;
     }
-    if (lds > kSamplesLdsMax) return false;
+    if (lds > kLdsCu) return false;
     // (at most four per compute unit: the path kernel holds 145 - 171 VGPRs, two or three waves per SIMD)
-    uint32_t per_cu = (uint32_t)(kSamplesLdsMax / lds);
+    uint32_t per_cu = (uint32_t)(kLdsCu / lds);
     if (per_cu > 4u) per_cu = 4u;
     const uint64_t cap = (uint64_t)n_cu * per_cu;                                 // workgroups the device keeps resident
     // slabs per pixel: enough items to fill the device, a slab no shorter than one sample per thread of a workgroup
@@ -207,8 +174,11 @@ hipError_t launch_samples(SamplesArgs a, const SamplesPlan &pl, hipStream_t stre
 {
     a.slab_len = pl.slab_len; a.n_slabs = pl.n_slabs; a.stack_rows = pl.stack_rows;
     const bool ext = a.sc.has_rough != 0u;
-    hipError_t e = pl.scene_lds ? (ext ? launch_paths<true, true>(a, pl, stream) : launch_paths<true, false>(a, pl, stream))
-                                : (ext ? launch_paths<false, true>(a, pl, stream) : launch_paths<false, false>(a, pl, stream));
+    const int grid = (int)pl.grid;
+    hipError_t e = pl.scene_lds ? (ext ? launch_with_lds(k_samples_paths<true, true>, a, grid, pl.lds_bytes, stream)
+                                       : launch_with_lds(k_samples_paths<true, false>, a, grid, pl.lds_bytes, stream))
+                                : (ext ? launch_with_lds(k_samples_paths<false, true>, a, grid, pl.lds_bytes, stream)
+                                       : launch_with_lds(k_samples_paths<false, false>, a, grid, pl.lds_bytes, stream));
     if (e != hipSuccess) return e;
     const uint64_t words = (uint64_t)a.n_pixels * ((uint64_t)a.film.tbins * 4u + 4u);
     hipLaunchKernelGGL(k_samples_reduce, dim3((uint32_t)((words + kBlock - 1u) / kBlock)), dim3(kBlock), 0, stream, a);

@@ -6,8 +6,6 @@
 
 namespace mtr {
 
-constexpr size_t kSamplesLdsMax = 160u * 1024u;      // row + scene + stack of a workgroup: the LDS of a compute unit
-
 // words of a workgroup's row and of a slot of `partial`: [T][3] time bins, steady R G B, sample count
 __host__ __device__ inline uint32_t samples_row_words(const Film &f) { return 3u * f.tbins + 4u; }
 
@@ -34,7 +32,7 @@ struct SamplesPlan {
     size_t partial_bytes;
 };
 
-// false: the row, the traversal stack (and the scene) exceed kSamplesLdsMax
+// false: the row, the traversal stack (and the scene) exceed kLdsCu, the LDS of a compute unit
 bool samples_plan(const SceneDev &sc, const Film &film, uint32_t n_pixels, uint32_t spp_chunk, int n_cu, SamplesPlan &pl);
 // k_samples_paths over the plan's items, then k_samples_reduce (a.partial: pl.partial_bytes of device memory)
 hipError_t launch_samples(SamplesArgs a, const SamplesPlan &pl, hipStream_t stream);

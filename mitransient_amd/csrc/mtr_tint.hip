@@ -5,9 +5,10 @@
 // arithmetic in the tint hooks of mtr_grad.h / mtr_fwd.h).  A translation unit of its own, so that the kernels of mtr_grad.hip and
 // mtr_fwd.hip keep their instructions.
 //
-//   k_grad_paths_tint<SCENE_LDS, EXT>       k_grad_paths with the tint hook: the workgroup's f64 LDS slab holds 3 more words per
-//                  tint slot behind the emitters' (LDS atomics), stored once to the workgroup's row of `partial`.
-//   k_grad_reduce_tint                      k_grad_reduce over the longer rows: no global atomics, bitwise reproducible.
+//   k_grad_paths_tint<SCENE_LDS, EXT>       k_grad_paths with the tint hook: the workgroup's f64 LDS slab holds 3
+//                  more words per tint slot behind the emitters' (LDS atomics), stored once to the workgroup's row of `partial`;
+//                  k_grad_reduce (mtr_grad.hip) sums the longer rows, the tints its third segment: no global atomics, bitwise
+//                  reproducible.
 //   k_fwd_paths_tint<SCENE_LDS, EXT, ROWS>  k_fwd_paths with the tint hook: the same rows and global tiers, the same fwd_plan; only
 //                  the lane arithmetic differs.
 #include "mtr_kernels.h"
@@ -27,10 +28,7 @@ struct TintSlab {
     {
         const int32_t s = slots[2u * m + which];
         if (s < 0) return;
-        double *p = t + 3u * (uint32_t)s;
-        if (g.x != 0.0f) atomicAdd(p, (double)g.x);
-        if (g.y != 0.0f) atomicAdd(p + 1, (double)g.y);
-        if (g.z != 0.0f) atomicAdd(p + 2, (double)g.z);
+        add3_nonzero(t + 3u * (uint32_t)s, g);
     }
     __device__ __forceinline__ void lobes(uint32_t, int, int) const {}
 };
@@ -44,36 +42,6 @@ struct TintTan {
         return s < 0 ? nullptr : tan + 3u * (uint32_t)s;
     }
 };
-
-// the scene of a workgroup, staged in LDS at smem + off or walked in HBM (as k_grad_paths / k_fwd_paths); the caller synchronises
-template <bool SCENE_LDS>
-__device__ __forceinline__ SceneView stage_scene(const SceneDev &sc, const Emitter *ems_unit, unsigned char *smem, uint32_t off, int tid)
-{
-    SceneView sv;
-    sv.n_emitters = sc.n_ems; sv.n_slots = sc.n_slots;
-    sv.samp_tris = sc.samp_tris; sv.samp_vn = sc.samp_vn; sv.face_pmf = sc.face_pmf; sv.face_cdf = sc.face_cdf; sv.vnormals = sc.vnormals;
-    sv.texels = sc.texels; sv.tex_info = sc.tex_info; sv.uvs = sc.uvs;
-    sv.flat_off = 0u;
-    if (SCENE_LDS) {
-        WNode *n = (WNode *)(smem + off); off += al16(sc.n_wnodes * sizeof(WNode));
-        TriPair *tg = (TriPair *)(smem + off); off += al16(sc.n_slots / 2 * sizeof(TriPair));
-        TriShade *ts = (TriShade *)(smem + off); off += al16(sc.n_slots * sizeof(TriShade));
-        mtr_material *mm = (mtr_material *)(smem + off); off += al16(sc.n_mats * sizeof(mtr_material));
-        Emitter *ee = (Emitter *)(smem + off); off += al16(sc.n_ems * sizeof(Emitter));
-        cp16(n, sc.wnodes, al16(sc.n_wnodes * sizeof(WNode)), tid);
-        cp16(tg, sc.tpairs, al16(sc.n_slots / 2 * sizeof(TriPair)), tid);
-        cp16(ts, sc.tshade, al16(sc.n_slots * sizeof(TriShade)), tid);
-        cp16(mm, sc.mats, al16(sc.n_mats * sizeof(mtr_material)), tid);
-        cp16(ee, ems_unit, al16(sc.n_ems * sizeof(Emitter)), tid);
-        sv.nodes = nullptr; sv.wnodes = n; sv.wnodes4 = nullptr; sv.wnodes8q = nullptr; sv.tpairs = tg; sv.tshade = ts; sv.mats = mm; sv.ems = ee;
-        sv.node_pairs = true;
-    } else {
-        sv.nodes = sc.nodes; sv.tpairs = sc.tpairs; sv.tshade = sc.tshade; sv.mats = sc.mats; sv.ems = ems_unit;
-        sv.wnodes = nullptr; sv.wnodes4 = sc.wnodes4; sv.wnodes8q = sc.wnodes8q;
-        sv.node_pairs = false;
-    }
-    return sv;
-}
 
 template <bool SCENE_LDS, bool EXT>
 __global__ void __launch_bounds__(kBlock) k_grad_paths_tint(const GradTintArgs args)
@@ -101,19 +69,6 @@ __global__ void __launch_bounds__(kBlock) k_grad_paths_tint(const GradTintArgs a
     __syncthreads();
     double *row = a.partial + (size_t)blockIdx.x * slab_n;
     for (uint32_t i = tid; i < slab_n; i += kBlock) row[i] = s_slab[i];
-}
-
-__global__ void __launch_bounds__(kBlock) k_grad_reduce_tint(const GradTintArgs args)
-{
-    const GradArgs &a = args.g;
-    const uint32_t n_m = 3u * a.n_mats, n_me = n_m + 3u * a.n_ems, slab_n = n_me + 3u * args.n_tints;
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= slab_n) return;
-    double acc = 0.0;
-    for (uint32_t r = 0; r < a.n_rows; ++r) acc += a.partial[(size_t)r * slab_n + i];
-    if (i < n_m) a.grad_mats[i] = (float)acc;
-    else if (i < n_me) a.grad_ems[i - n_m] = (float)acc;
-    else args.grad_tints[i - n_me] = (float)acc;
 }
 
 template <bool SCENE_LDS, bool EXT, bool ROWS>
@@ -171,15 +126,6 @@ __global__ void __launch_bounds__(kBlock) k_fwd_paths_tint(const FwdTintArgs arg
     }
 }
 
-template <class K, class A>
-hipError_t launch_with_lds(K k, const A &a, int grid, size_t lds, hipStream_t stream)
-{
-    hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), lds, stream, a);
-    return hipGetLastError();
-}
-
 template <bool ROWS>
 hipError_t launch_fwd_paths(const FwdTintArgs &a, bool sl, bool ext, int grid, size_t lds, hipStream_t stream)
 {
@@ -197,13 +143,7 @@ hipError_t launch_grad_tint(const SceneDev &sc, const Emitter *ems_unit, const C
                             uint32_t n_tints, const int32_t *tint_slots, float *grad_tints, hipStream_t stream)
 {
     GradTintArgs t{};
-    GradArgs &a = t.g;
-    a.sc = sc; a.ems_unit = ems_unit; a.cam = cam; a.film = film; a.rc = rc; a.gc = gc;
-    a.pixel_begin = pixel_begin; a.spp_begin = spp_begin; a.spp_chunk = spp_chunk;
-    a.n_lanes = (uint64_t)n_pixels * spp_chunk;
-    a.n_mats = sc.n_mats; a.n_ems = sc.n_ems;
-    a.stack_rows = wf_stack_rows(sc, scene_lds);
-    a.partial = partial; a.grad_mats = grad_mats; a.grad_ems = grad_ems; a.n_rows = grid;
+    t.g = make_grad_args(sc, ems_unit, cam, film, rc, gc, pixel_begin, n_pixels, spp_begin, spp_chunk, partial, grid, scene_lds, grad_mats, grad_ems);
     t.n_tints = n_tints; t.tint_slots = tint_slots; t.grad_tints = grad_tints;
     const bool ext = sc.has_rough != 0u;
     hipError_t e = scene_lds ? (ext ? launch_with_lds(k_grad_paths_tint<true, true>, t, (int)grid, lds, stream)
@@ -211,9 +151,7 @@ hipError_t launch_grad_tint(const SceneDev &sc, const Emitter *ems_unit, const C
                              : (ext ? launch_with_lds(k_grad_paths_tint<false, true>, t, (int)grid, lds, stream)
                                     : launch_with_lds(k_grad_paths_tint<false, false>, t, (int)grid, lds, stream));
     if (e != hipSuccess) return e;
-    const uint32_t slab_n = 3u * (sc.n_mats + sc.n_ems + n_tints);
-    hipLaunchKernelGGL(k_grad_reduce_tint, dim3((slab_n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, t);
-    return hipGetLastError();
+    return launch_grad_reduce(t.g, n_tints, grad_tints, false, stream);
 }
 
 hipError_t launch_fwd_tint(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
@@ -222,15 +160,11 @@ hipError_t launch_fwd_tint(const SceneDev &sc, const Emitter *ems_unit, const Ca
 {
     if (pixel_begin >= pixel_end || spp == 0u) return hipSuccess;
     FwdTintArgs t{};
-    FwdArgs &a = t.f;
-    a.sc = sc; a.ems_unit = ems_unit; a.cam = cam; a.film = film; a.rc = rc; a.fc = fc;
-    a.pixel_begin = pixel_begin; a.pixel_end = pixel_end; a.spp = spp; a.div_spp = fastdiv_make(spp);
-    a.G = pl.G; a.n_runs = pl.n_runs; a.stack_rows = pl.stack_rows;
-    a.steady = steady; a.transient = transient;
+    t.f = make_fwd_args(sc, ems_unit, cam, film, rc, fc, pixel_begin, pixel_end, spp, pl, steady, transient);
     t.tint_slots = tint_slots; t.tan_tints = tan_tints;
     const bool ext = sc.has_rough != 0u;
     if (pl.tier == MTR_FWD_ROWS) return launch_fwd_paths<true>(t, pl.scene_lds, ext, (int)pl.grid, pl.lds, stream);
-    hipError_t e = launch_fwd_zero(a, stream);
+    hipError_t e = launch_fwd_zero(t.f, stream);
     if (e != hipSuccess) return e;
     return launch_fwd_paths<false>(t, pl.scene_lds, ext, (int)pl.grid, pl.lds, stream);
 }

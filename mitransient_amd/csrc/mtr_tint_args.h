@@ -10,7 +10,7 @@ struct GradTintArgs {
     GradArgs g;                   // (n_texels, tex_acc, grad_texels: not used)
     uint32_t n_tints;             // tint slots: 3 more doubles each behind the emitters' words of the slab
     const int32_t *tint_slots;    // device [n_mats * 2]: tint_slot_table (mtr_scene_host.h)
-    float *grad_tints;            // (n_tints, 3) f32: k_grad_reduce_tint's output
+    float *grad_tints;            // (n_tints, 3) f32: the third segment of k_grad_reduce's output
 };
 
 struct FwdTintArgs {
@@ -20,7 +20,7 @@ struct FwdTintArgs {
 };
 
 // k_grad_paths_tint over the lanes of the launch (the arguments of launch_grad; grid and lds from grad_grid with n_tints more slab
-// entries), then k_grad_reduce_tint: grad_mats, grad_ems and grad_tints
+// entries), then k_grad_reduce with the tints as its third segment: grad_mats, grad_ems and grad_tints
 hipError_t launch_grad_tint(const SceneDev &sc, const Emitter *ems_unit, const Camera &cam, const Film &film, const RenderConst &rc,
                             const GradConst &gc, uint32_t pixel_begin, uint32_t n_pixels, uint32_t spp_begin, uint32_t spp_chunk,
                             double *partial, uint32_t grid, size_t lds, bool scene_lds, float *grad_mats, float *grad_ems,

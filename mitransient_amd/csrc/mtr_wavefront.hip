@@ -1351,7 +1351,7 @@ bool wf_plan(const SceneDev &sc, WfConfig &cfg)
     if (sc.bvh_depth > 64) return false;
     cfg.stack = sc.bvh_depth <= 8 ? 8 : sc.bvh_depth <= 16 ? 16 : sc.bvh_depth <= 32 ? 32 : 64;
     const uint32_t scene_b = lds_scene_bytes(sc);
-    cfg.scene_lds = sc.wnodes != nullptr && scene_b <= 64u * 1024u;
+    cfg.scene_lds = scene_fits_lds(sc);
     cfg.lds_bytes = 64 + (size_t)wf_stack_rows(sc, cfg.scene_lds) * kBlock * 4 + (cfg.scene_lds ? scene_b : 0) + 16;
     return true;
 }
@@ -1382,7 +1382,7 @@ hipError_t launch_wf(const WfArgs &a, const WfConfig &cfg, WfKernel which, int g
         // of workgroups behind the first
         int dev = 0, n_cu = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu > 0) {
-            int per_cu = (int)((160u * 1024u) / lds);
+            int per_cu = (int)(kLdsCu / lds);
             if (per_cu > 8) per_cu = 8;
             if (per_cu < 1) per_cu = 1;
             if (grid > n_cu * per_cu) grid = n_cu * per_cu;

@@ -5,7 +5,9 @@ _SAMPLES of one build.  Per case: one warm-up render, then `--reps` timed ones, 
 time of a render is mtr_render's own (device events around the launches, mtr_kernel_times.total_ms) with the host's wall clock
 around the synchronised call beside it.  The median is reported; a mode that cannot run a size is recorded with its error.
 
-    python tools/time_samples.py [--reps 3] [--out profiles/samples_mode_times.txt] [--log2-spp 20 22] [--films 1 4]
+    python tools/time_samples.py [--reps 3] [--out profiles/samples_mode_times.txt] [--log2-spp 20 22] [--films 1 4] [--rough]
+
+--rough: the small box a `roughconductor`, so that every mode runs its kernels with the extended shading code.
 """
 import argparse
 import json
@@ -20,12 +22,14 @@ sys.path.insert(0, ROOT)
 MODES = ["fused", "wavefront", "samples"]
 
 
-def scene_for(side, mode, bins):
+def scene_for(side, mode, bins, rough=False):
     import mitransient_amd as mitr
     import mitransient_amd.mi as mi
     mi.set_variant("llvm_ad_rgb")
     d = mitr.cornell_box()
     d["integrator"]["amd_mode"] = mode
+    if rough:
+        d["small-box"]["bsdf"] = dict(type="roughconductor", distribution="ggx", alpha=0.2)
     d["sensor"]["film"].update(width=side, height=side, temporal_bins=bins, start_opl=3.5, bin_width_opl=6.0 / bins)
     return mi.load_dict(d)
 
@@ -49,6 +53,7 @@ def main():
     ap.add_argument("--log2-spp", type=int, nargs="+", default=[20, 22])
     ap.add_argument("--films", type=int, nargs="+", default=[1, 4])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "samples_mode_times.txt"))
+    ap.add_argument("--rough", action="store_true", help="a roughconductor small box: the extended shading code")
     ap.add_argument("--slow-ms", type=float, default=30000.0, help="a mode whose warm-up took longer is timed once more only")
     a = ap.parse_args()
     import torch
@@ -60,7 +65,7 @@ def main():
             scenes, times, walls, sums, errors = {}, {}, {}, {}, {}
             for m in MODES:
                 try:
-                    scenes[m] = scene_for(side, m, a.bins)
+                    scenes[m] = scene_for(side, m, a.bins, a.rough)
                     dev, wall, total = render_once(scenes[m], spp)                  # warm-up (code objects, workspaces)
                     times[m], walls[m], sums[m] = [], [], total
                     if dev > a.slow_ms:
