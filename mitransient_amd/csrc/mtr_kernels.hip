@@ -303,9 +303,22 @@ __device__ __forceinline__ void forget_dead(Path &p)
 // next entries in order), or hold earlier entries of the same block (of q itself, hence startable), or are marked, which happens
 // only once the block is used up.  A wave that postpones its refill does so for lanes waiting for rows, which no lane it could
 // start would release sooner: the indices it would draw are larger still.  So q completes, is flushed, and hands its row on.
-// No wave waits for another wave for anything it did not wait for before.
+// No wave waits for another wave for anything it did not wait for before.  (CARRY START, below: a lane that starts its entry where it
+// takes it holds no entry it has not started, so it never postpones a refill, and it starts no later than it did at the loop top.)
+// CARRY START (round 14; -DMTR_START_CARRY=1; 0: round 13's loop, instruction for instruction).  The loop-top start section
+// ran in 98 % of the wave iterations, mostly for lanes whose next sample lies in the pixel they have just finished (`carry`: at 1024 spp
+// a lane runs about four paths of a pixel in a row, and blocks lie inside one pixel).  For such a lane the section recomputes what it
+// holds: q, slot and xy are the ended path's, the owner test cannot fail — the pixel cannot close while this lane's next path of it has
+// not ended — and p.L goes on accumulating.  So the lane starts in the end-of-path block, where it takes entry e < kStartBlock of the
+// wave's COMPUTED block (a block not computed yet gives `want`, never `carry`): its record, the constants of path_resume, the lane id
+// advanced by the difference of the two sample indices, the parks.  The loop-top section is left to lanes of another pixel and to
+// lanes served by a refill: 52 % of the iterations.  Config 2 42.24 -> 41.58 ms (profiles/r14_carry_start.txt).
+// (Measured and taken out again: the remaining starts' index arithmetic as four wave-uniform words per block, HISTORY.md.)
 #ifndef MTR_START_BLOCKS
 #define MTR_START_BLOCKS 1
+#endif
+#ifndef MTR_START_CARRY
+#define MTR_START_CARRY 0
 #endif
 typedef uint32_t StartRecWord __attribute__((ext_vector_type(4)));
 typedef StartRecWord __attribute__((address_space(1))) *StartRecPtr;      // a record of the table, as GLOBAL memory: global_load / global_store (a generic pointer gave flat_*, counted in lgkmcnt too)
@@ -351,6 +364,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     constexpr bool kLean = SCENE_LDS && HIST_LDS && !NLOS && !PHASOR && !FIXED && !ROUGH && flat_kind(TR) != 0;
     constexpr bool kPrimTable = flat_prim_table_on(kLean, flat_kind(TR) == 2);
     constexpr bool kStartBlocks = kLean && MTR_START_BLOCKS != 0;          // START BLOCKS, above (fused_start_blocks: the host's side of it)
+    constexpr bool kCarryStart = kStartBlocks && (MTR_START_CARRY & 1) != 0;      // CARRY START, above
 #ifdef MTR_PROFILE_TAIL
     const unsigned long long t0_wall = wall_clock64();
 #endif
@@ -451,8 +465,9 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     // 32 BITS PER CHUNK (kLean).  The counters are live across everything in the loop; as five 64-bit sums they are ten scalar registers,
     // two of them spilled and restored in every wave iteration.  Four 32-bit ones instead — closest-hit rays are bounces, plus one per
     // path under camera_unwarp — drained into the workgroup's 64-bit sums at the end of every chunk (drain_counters).  No wrap: a wave
-    // iteration adds at most 64 paths, 64 bounces, 64 shadow rays and 128 contributions — paths and shadow rays never outnumber the
-    // bounces, contributions are at most twice as many — and a wave that has counted 2^30 bounces since its last drain drains at
+    // iteration adds at most 128 paths (64 at the loop top, 64 where paths end: CARRY START), 64 bounces, 64 shadow rays and 128
+    // contributions — shadow rays never outnumber the bounces, paths exceed them by at most the 64 that are counted before their first
+    // bounce, contributions are at most twice as many — and a wave that has counted 2^30 bounces since its last drain drains at
     // once: THAT is what rules a wrap out.  fused_chunk_cap only keeps that branch cold for any path length a render is likely to have.
     typedef typename std::conditional<kLean, uint32_t, unsigned long long>::type WaveCount;
     WaveCount w_closest = 0, w_shadow = 0, w_bounce = 0, w_paths = 0, w_splats = 0;       // (w_closest: not kLean)
@@ -467,6 +482,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     };
 #ifdef MTR_PROFILE_OCC
     unsigned long long occ_iter = 0, occ_alive = 0, occ_wait = 0;
+    [[maybe_unused]] bool occ_ran = false, occ_need = false;
 #endif
     uint32_t n_closest = 0, n_shadow = 0, n_splats = 0;          // NLOS only
 
@@ -554,6 +570,9 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     for (;;) {
         st.prof_mark(4);                 // (experiment builds) sections: 0 traversal, 1 shading, 2 path start, 3 end-of-path bookkeeping, 4 row flush, 5 idle
         for (;;) {          // (START BLOCKS: a second turn for the lanes the refill below has served; otherwise once)
+#if defined(MTR_PROFILE_OCC) && MTR_PROFILE_OCC == 2      // experiment build: did the start section run in this iteration, and for a lane that is no same-pixel restart?
+        occ_ran |= __ballot(waiting) != 0ull; occ_need |= __ballot(waiting && !carry) != 0ull;
+#endif
         if (__ballot(waiting) != 0ull) {
             bool started = false;
             // (the arguments a path start needs: read from the kernarg segment here, see kernarg_copy)
@@ -650,7 +669,13 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
         bool closes = false;
         bool ended = false;                  // (START BLOCKS) the lane's path ended in this iteration: it took an entry of the block, or is marked
 #ifdef MTR_PROFILE_OCC        // experiment build: occupancy of the persistent lanes (wave iterations, alive lanes, waiting lanes)
-        occ_iter += 1; occ_alive += (uint32_t)__popcll(__ballot(alive)); occ_wait += (uint32_t)__popcll(__ballot(waiting));
+        occ_iter += 1;
+#if MTR_PROFILE_OCC == 2      // (tools/occ.py --starts: iterations in which the start section ran / ran for more than same-pixel restarts)
+        occ_alive += occ_ran ? 1u : 0u; occ_wait += occ_need ? 1u : 0u; occ_ran = false; occ_need = false;
+#elif MTR_PROFILE_OCC == 3      // (tools/occ.py --mixed: counted where the paths end, below)
+#else
+        occ_alive += (uint32_t)__popcll(__ballot(alive)); occ_wait += (uint32_t)__popcll(__ballot(waiting));
+#endif
 #endif
         w_bounce += (uint32_t)__popcll(__ballot(alive));
         uint32_t did_shadow = 0u, did_splats = 0u;                 // this iteration's per-lane counts (0..1, 0..2)
@@ -750,6 +775,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                 // lane's next path of it has not ended.  Not for the order-independent rows (the runs depend on timing).
                 // The sample COUNT needs no atomic at all: the row is flushed when all spp_chunk paths of the pixel have ended
                 // (config 2: 68.7 -> 67.8 ms for that one atomic per path; fixed-point sums instead of f32: 67.7 -> 67.95, not kept).
+                [[maybe_unused]] const uint32_t i_ended = i;          // (CARRY START: the index of the path that has just ended)
                 if constexpr (kStartBlocks) {
                     // START BLOCKS: the lanes whose path has just ended take the block's next entries in lane order; beyond its end: marked
                     const unsigned long long em = __ballot(true);
@@ -782,9 +808,31 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
                 // (One atomic per wave for the next samples and one per (wave, slot) for the count — ballots, readlanes and a
                 // leader lane — was measured: end-of-path bookkeeping 8.0 -> 11.0 % of the wave's time; not kept.)
                 closes = __hip_atomic_fetch_add(s_done + slot, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) + 1u == a.spp_chunk;
+                if constexpr (kCarryStart) {
+                    // CARRY START: the lane's next path is of the pixel it has just finished a path of, and starts here.  q, slot, xy
+                    // and p.px, p.py stay; the owner test cannot fail (the pixel cannot close before this path ends: `carry`, above);
+                    // p.L goes on accumulating.  What is left of a path start is the record of entry e < kStartBlock of the wave's
+                    // computed block (kStartFresh gives `want`, never `carry`) and the constants of path_resume.  p.lane is
+                    // pixel * spp_total + spp_begin + (i - q * spp_chunk): pixel and q are the ended path's, so it grows by the
+                    // difference of the two indices.
+                    if (carry) {
+                        load_rec(i - blk_base);
+                        p.lane += i - i_ended;
+                        p.beta = mk(1, 1, 1); p.prev_p = mk(0, 0, 0);
+                        p.eta = 1.0f; p.dist = 0.0f; p.prev_pdf = 1.0f; p.depth = 0; p.prev_delta = 1;
+                        if (LdsStack::kPark) { st.park_inc(p.rng.inc); st.park_prev_p(p.prev_p); st.park_prev_pdf(p.prev_pdf); }
+                        alive = true; waiting = false; carry = false;
+                    } else if constexpr ((MTR_PATH_STATE & 1) != 0) forget_dead(p);
+                }
             }
         } else if constexpr (kLean && (MTR_PATH_STATE & 1) != 0) forget_dead(p);
         if constexpr (kStartBlocks) blk_used = min(blk_used + (uint32_t)__popcll(__ballot(ended)), kStartBlock);      // (uniform: counted outside the branch)
+        if constexpr (kCarryStart) w_paths += (uint32_t)__popcll(__ballot(ended && alive));      // (CARRY START: the paths started where they ended)
+#if defined(MTR_PROFILE_OCC) && MTR_PROFILE_OCC == 3      // experiment build: iterations in which a lane restarted where its path ended, and in which another
+        // lane of the wave, ending beside it, took an entry of ANOTHER pixel (`waiting`, not marked: it goes to the loop top and its owner test)
+        occ_alive += __ballot(ended && alive) != 0ull ? 1u : 0u;
+        occ_wait += __ballot(ended && alive) != 0ull && __ballot(ended && waiting) != 0ull ? 1u : 0u;
+#endif
         if (!NLOS) {          // one closest-hit ray per live lane (counted with w_bounce), at most one shadow ray, at most two contributions
             w_shadow += (uint32_t)__popcll(__ballot(did_shadow != 0u));
             w_splats += (uint32_t)__popcll(__ballot((did_splats & 1u) != 0u)) + 2u * (uint32_t)__popcll(__ballot((did_splats & 2u) != 0u));

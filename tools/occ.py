@@ -1,10 +1,32 @@
 import sys; import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 # -DMTR_PROFILE_OCC build: how full are k_fused's persistent waves?  (wave iterations with a live lane, live lanes, lanes
 # holding a sample whose row slot is not free yet)
+# --starts, -DMTR_PROFILE_OCC=2 build: in how many of those iterations did the loop-top start section run, and in how many for a lane
+# that is no same-pixel restart (`carry` false: another pixel, or served by a refill)?  With CARRY START the two are the same number.
+# --mixed, -DMTR_PROFILE_OCC=3 build: in how many iterations did a lane restart where its path ended (CARRY START), and in how many of
+# those did another lane of the wave, ending beside it, take an entry of another pixel?
+# --film W H BINS SPP [--one-cu]: the Cornell box of tests/test_gpu_fused_carry_start.py at that shape instead of config 2
+# (--one-cu: amd_reserve_cus, tickets of many pixels on a small film)
 import bench, torch
-scene = bench.build_scene(512,512,1024)
+if '--film' in sys.argv:
+    import mitransient_amd as mitr
+    import mitransient_amd.mi as mi
+    w, h, bins, spp = (int(x) for x in sys.argv[sys.argv.index('--film') + 1:][:4])
+    mi.set_variant("llvm_ad_rgb")
+    d = mitr.cornell_box()
+    d["sensor"]["film"].update(width=w, height=h, temporal_bins=bins, start_opl=0.0, bin_width_opl=12.0 / bins)
+    d["integrator"].update(amd_mode="fused", max_depth=6)
+    if '--one-cu' in sys.argv: d["integrator"].update(amd_reserve_cus=100000)
+    scene = mi.load_dict(d)
+else:
+    scene, spp = bench.build_scene(512,512,1024), 1024
 integ = scene.integrator(); integ.collect_stats=True
-s,t = integ.render(scene, spp=1024)
+s,t = integ.render(scene, spp=spp)
 c = integ.last_counters
 it, alive, wait = c['splats_overflow'], c['reserved'][0], c['reserved'][1]
-print('wave iterations %d  alive lanes/iteration %.1f  waiting lanes/iteration %.1f  (bounces %d, ideal iterations %d)' % (it, alive/it, wait/it, c['bounces'], c['bounces']//64))
+if '--starts' in sys.argv:
+    print('wave iterations %d  start section ran in %d (%.3f)  for more than same-pixel restarts in %d (%.3f)' % (it, alive, alive/it, wait, wait/it))
+elif '--mixed' in sys.argv:
+    print('wave iterations %d  with a restart where a path ended %d (%.3f)  with a lane beside it that moved on to another pixel %d (%.3f)' % (it, alive, alive/it, wait, wait/it))
+else:
+    print('wave iterations %d  alive lanes/iteration %.1f  waiting lanes/iteration %.1f  (bounces %d, ideal iterations %d)' % (it, alive/it, wait/it, c['bounces'], c['bounces']//64))
