@@ -307,6 +307,13 @@ enum { MTR_FLAG_CAMERA_UNWARP = 1u,        /* common.py:25, transientpath.py:133
                                               sample_tea_64(idx, seed)) — 64-bit state and stream words, each the two TEA
                                               outputs glued together (v0 + (v1 << 32)) — instead of the two halves of one
                                               sample_tea_32(seed, idx) [upstream-unverified].  Wins over PLUS_LANE if both are set. */ };
+/* SHADOW HULL MARGIN (round 15; bits 16..31 of `flags`, zero in every earlier caller: no ABI change).  In a room of rectangles with one
+   rectangular light the fused kernel spares a shadow ray the rectangle tests it provably cannot pass (mtr_scene_shadow_hull says whether
+   the scene is one); a lane is spared only when its ray origin lies a guard distance inside the walls' planes and in front of the light.
+   The field v multiplies those distances by v + 1 (0: as derived; larger: only more careful, the same picture bit for bit);
+   MTR_SHADOW_HULL_OFF switches the feature off for the call. */
+#define MTR_SHADOW_HULL_SHIFT 16u
+#define MTR_SHADOW_HULL_OFF   0xffffu
 
 /* which kernel organisation executes the path */
 enum { MTR_MODE_AUTO = 0,
@@ -433,6 +440,11 @@ int  mtr_scene_bvh_info(const mtr_scene *, uint32_t *n_nodes, uint32_t *max_dept
 #define MTR_TRAIT_NO_LOBES        32u   /* extended shading (interpolated normals, bitmaps) without any microfacet lobe / plastic / thin dielectric */
 #define MTR_TRAIT_GREY            64u   /* every colour (materials, emitters, the NLOS laser) has three equal channels, no bitmaps: r == g == b in every contribution */
 int  mtr_scene_traits(const mtr_scene *, uint32_t *traits);
+/* SHADOW HULL (round 15; a new entry point, nothing a caller of ABI 24 uses moves): is the scene a room of rectangles with one
+ * rectangular light in the sense of MTR_SHADOW_HULL_SHIFT above?  *n_hull_rectangles receives the number of rectangles a safe shadow
+ * ray is spared (the walls: every top-level rectangle but the light), 0 when the scene is no such room.  Reported here and not as a
+ * bit of mtr_scene_traits: that word selects kernels and is compared for equality. */
+int  mtr_scene_shadow_hull(const mtr_scene *, uint32_t *n_hull_rectangles);
 /* (ABI 15) mi.traverse(scene) parameters changed (params.update()): new constant colours for the scene's tables, without
  * rebuilding anything else — material_a (host, n_materials x 3) replaces every mtr_material.a, emitter_radiance (host,
  * n_emitters x 3) every mtr_emitter.radiance; the traits that depend on colours are decided again.  Synchronises the context's

@@ -24,6 +24,7 @@ MTR_FLAG_DISCARD_DIRECT_LIGHT = 2
 MTR_FLAG_FILM_ZERO = 4
 MTR_FLAG_PCG_INITSEQ_PLUS_LANE = 8
 MTR_FLAG_PCG_TEA64 = 128
+MTR_SHADOW_HULL_SHIFT, MTR_SHADOW_HULL_OFF = 16, 0xFFFF      # bits 16..31 of the flags: the shadow-hull margin less one, or off
 MTR_FLAG_KEEP_COUNTERS = 16
 MTR_FLAG_DETERMINISTIC = 32
 MTR_FLAG_DEVELOPED_ROWS = 64
@@ -172,7 +173,7 @@ class mtr_kernel_times(C.Structure):
 # Every symbol include/mitransient_amd.h declares (checked by tests/test_abi.py).
 EXPORTS = [
     "mtr_abi_version", "mtr_ctx_create", "mtr_ctx_destroy", "mtr_ctx_set_stream", "mtr_last_error",
-    "mtr_scene_create", "mtr_scene_destroy", "mtr_scene_set_film", "mtr_scene_set_nlos", "mtr_scene_bvh_info", "mtr_scene_traits",
+    "mtr_scene_create", "mtr_scene_destroy", "mtr_scene_set_film", "mtr_scene_set_nlos", "mtr_scene_bvh_info", "mtr_scene_traits", "mtr_scene_shadow_hull",
     "mtr_ctx_trim", "mtr_film_clear", "mtr_render", "mtr_render_plan", "mtr_counters_reset", "mtr_counters_read", "mtr_film_develop", "mtr_splat_add", "mtr_debug_set_splat_log",
     "mtr_render_grad", "mtr_scene_set_colors",
     "mtr_render_grad_tex", "mtr_render_grad_tex_tier", "mtr_scene_set_texture", "mtr_scene_texture_layout",
@@ -218,6 +219,7 @@ def load_library() -> C.CDLL:
     lib.mtr_scene_set_nlos.argtypes = [vp, C.POINTER(mtr_nlos_desc)]
     lib.mtr_scene_bvh_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.mtr_scene_traits.argtypes = [vp, C.POINTER(C.c_uint32)]
+    lib.mtr_scene_shadow_hull.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.mtr_counters_read.argtypes = [vp, C.POINTER(mtr_counters)]
     lib.mtr_counters_reset.argtypes = [vp]
     lib.mtr_ctx_trim.argtypes = [vp]

@@ -92,6 +92,7 @@ struct mtr_scene {
     uint32_t n_texels = 0;                   // texels of all textures (mtr_render_grad_tex's grad_texels)
     std::vector<void *> allocs;
     SplatLog log{ nullptr, 0, nullptr };
+    ShadowHull hull{};                       // SHADOW HULL (mtr_shadow_hull.h): classify_scene's block; a render applies its margin (FusedArgs::hull)
 };
 
 static thread_local std::string g_err;
@@ -233,7 +234,7 @@ int mtr_scene_create(mtr_ctx *c, const mtr_scene_desc *d, mtr_scene **out)
     s->dev.n_mats = d->n_materials; s->dev.n_ems = d->n_emitters;
     // what the kernels are chosen by: decided over the host tables (mtr_scene_host.cpp classify_scene)
     s->polar_ok = hs.polar_ok; s->grey_scene = hs.grey_scene; s->has_sphere = hs.has_sphere;
-    s->dev.has_rough = hs.needs_ext ? 1u : 0u; s->dev.traits = hs.traits; s->dev.flat = hs.flat;
+    s->dev.has_rough = hs.needs_ext ? 1u : 0u; s->dev.traits = hs.traits; s->dev.flat = hs.flat; s->hull = hs.hull;
     s->dev.bvh_depth = hs.bvh_depth; s->n_leaves = hs.n_leaves;
     s->dev.wide_levels = hs.wide_levels; s->dev.wide4_levels = hs.wide4_levels; s->dev.wide8q_levels = hs.wide8q_levels;
     s->tri_verts.assign(d->tri_verts, d->tri_verts + 9 * (size_t)d->n_tris);
@@ -462,6 +463,13 @@ int mtr_scene_traits(const mtr_scene *s, uint32_t *traits)
                   MTR_TRAIT_FLAT_TOP == kTrFlatTop && MTR_TRAIT_FLAT_LEAVES == kTrFlatLeaves && MTR_TRAIT_NO_LOBES == kTrNoLobes &&
                   MTR_TRAIT_GREY == kTrGrey, "public trait bits");
     *traits = s->dev.traits;
+    return MTR_OK;
+}
+
+int mtr_scene_shadow_hull(const mtr_scene *s, uint32_t *n_hull_rectangles)
+{
+    if (!s || !n_hull_rectangles) return MTR_ERR_INVALID;
+    *n_hull_rectangles = s->hull.count;
     return MTR_OK;
 }
 
@@ -892,6 +900,10 @@ int mtr_render(mtr_scene *s, const mtr_render_params *p, float *t4, float *s4,
     a.film_out = t4; a.steady_out = s4;
     a.counters = c->d_counters;
     a.log = s->log;
+    {   // SHADOW HULL MARGIN (bits 16..31 of the flags): v + 1 times the derived guard distances, MTR_SHADOW_HULL_OFF: no block
+        const uint32_t v = p->flags >> MTR_SHADOW_HULL_SHIFT;
+        a.hull = shadow_hull_with_margin(s->hull, v == MTR_SHADOW_HULL_OFF ? 0.0f : (float)(v + 1u));
+    }
     a.nlos_on = s->nlos.on ? 1u : 0u;
     if (s->nlos.on) {
         a.nlos = s->nlos.k;

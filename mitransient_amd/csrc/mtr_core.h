@@ -30,6 +30,7 @@
 #include <math.h>
 #include "../../include/mitransient_amd.h"
 #include "mtr_flat_prims.h"
+#include "mtr_shadow_hull.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -474,6 +475,7 @@ struct SceneView {
     // and the corner texture coordinates by slot: (u0, v0, u1, v1) (u2, v2, -, -)
     const q4 *texels; const q4 *tex_info; const q4 *uvs;
     uint32_t flat_off;        // kTrFlatTop kernels: byte offset of the scene's FlatTop inside the kernel's argument (kernarg_copy)
+    uint32_t hull_off;        // k_fused's flat walk with one rectangular emitter: ... and of the ShadowHull block (set and read there alone)
 };
 
 // [mitsuba3: DiscreteDistribution::sample_reuse_pmf] on a normalised f32 table
@@ -1239,6 +1241,9 @@ __device__ __forceinline__ void kernarg_pin(const T &v)
 // (a traversal stack type may name the form of kernarg_copy its kernel reads the flat top level with: Stack::kOneKernargBase)
 template <class S, class = void> struct stack_one_kernarg_base { static constexpr bool value = false; };
 template <class S> struct stack_one_kernarg_base<S, decltype((void)S::kOneKernargBase)> { static constexpr bool value = S::kOneKernargBase; };
+// (... and that its kernel's argument holds a ShadowHull block at SceneView::hull_off: Stack::kShadowHull — k_fused alone)
+template <class S, class = void> struct stack_shadow_hull { static constexpr bool value = false; };
+template <class S> struct stack_shadow_hull<S, decltype((void)S::kShadowHull)> { static constexpr bool value = S::kShadowHull; };
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // One pair of children of the root against a ray: the slab tests of flat_walk_device's rectangle stage.  `p0`, `p1`: the children exist.
@@ -1247,11 +1252,12 @@ template <class S> struct stack_one_kernarg_base<S, decltype((void)S::kOneKernar
 // BATCH (k_fused's lean kernels, BATCHED REQUESTS): the step's six plane pairs are read into locals FIRST and only then used.  Written read by
 // read beside its fma, the compiler keeps that order — a ds_read_b64, an s_waitcnt, four instructions, six times over in the first
 // step; requested together they are awaited once per step (config 2's loop: 98 -> 87 s_waitcnt).  A pin on the six adds nothing.
-template <bool ANY_HIT, uint32_t J, bool BATCH = false>
-__device__ __forceinline__ void flat_slab_pair(const f3 id, const f3 noid, const float tb, const uint32_t sel0, const uint32_t sel1, const uint32_t sel2,
-                                               const char *root, const bool p0, const bool p1, uint32_t &qm, uint32_t &key1, uint32_t &key2)
+// (flat_slab_pair_at: the pair whose planes begin at `pb`, children j2 and j2 + 1 — flat_slab_pair with J a constant, as every stage but
+// SHADOW HULL's emitter tier has it)
+template <bool ANY_HIT, bool BATCH = false>
+__device__ __forceinline__ void flat_slab_pair_at(const f3 id, const f3 noid, const float tb, const uint32_t sel0, const uint32_t sel1, const uint32_t sel2,
+                                                  const char *pb, const uint32_t j2, const bool p0, const bool p1, uint32_t &qm, uint32_t &key1, uint32_t &key2)
 {
-    const char *pb = root + 48u * J;
     f2 nx, fx, ny, fy, nz, fz;
     if constexpr (BATCH) {
         const f2 pnx = *(const f2 *)(pb + sel0), pfx = *(const f2 *)(pb + (sel0 ^ 8u));
@@ -1271,13 +1277,19 @@ __device__ __forceinline__ void flat_slab_pair(const f3 id, const f3 noid, const
     const float tf1 = fminf(fminf(fx.y, fy.y), fminf(fz.y, tb));
     const bool h0 = (tn0 <= tf0) && p0;
     const bool h1 = (tn1 <= tf1) && p1;
-    qm |= (h0 ? 1u : 0u) << (2u * J);
-    qm |= (h1 ? 2u : 0u) << (2u * J);
+    qm |= (h0 ? 1u : 0u) << j2;
+    qm |= (h1 ? 2u : 0u) << j2;
     if (!ANY_HIT) {
-        const uint32_t ka = h0 ? ((fbits(tn0) & ~7u) | (2u * J)) : 0xffffffffu, kb = h1 ? ((fbits(tn1) & ~7u) | (2u * J + 1u)) : 0xffffffffu;
+        const uint32_t ka = h0 ? ((fbits(tn0) & ~7u) | j2) : 0xffffffffu, kb = h1 ? ((fbits(tn1) & ~7u) | (j2 + 1u)) : 0xffffffffu;
         key2 = min(key2, max(key1, ka)); key1 = min(key1, ka);
         key2 = min(key2, max(key1, kb)); key1 = min(key1, kb);
     }
+}
+template <bool ANY_HIT, uint32_t J, bool BATCH = false>
+__device__ __forceinline__ void flat_slab_pair(const f3 id, const f3 noid, const float tb, const uint32_t sel0, const uint32_t sel1, const uint32_t sel2,
+                                               const char *root, const bool p0, const bool p1, uint32_t &qm, uint32_t &key1, uint32_t &key2)
+{
+    flat_slab_pair_at<ANY_HIT, BATCH>(id, noid, tb, sel0, sel1, sel2, root + 48u * J, 2u * J, p0, p1, qm, key1, key2);
 }
 // CHILD-ORDERED PRIMITIVE TABLE (round 11; mtr_flat_prims.h; MTR_BATCH & 4).  flat_walk_device knows WHICH primitive it wants as a
 // number in a register — the child index k of the slab stage, the face bit of box_select — and used to turn it into a record in
@@ -1313,9 +1325,20 @@ __device__ __forceinline__ RecByValue flat_prim_fetch(const char *root, const ui
 // (The ray comes BY VALUE and is never stored in the Trav, which carries the hit alone: o, d and what trav_init derives from them
 // are plain values from the first box to the last rectangle.  Round 8: they were a 32-byte object in private memory before, written
 // once and read back four times per walk — see trav_quad_test for the cause.)
-template <bool ANY_HIT, bool ONE_PAIR, bool TOP_LEAVES, class Stack>
+// SHADOW HULL (round 15; HULL: path_bounce's shadow walk in the kernels of one rectangular emitter, no other caller; mtr_shadow_hull.h
+// holds the proof).  A ray that shade_hit aimed at the emitter E (shadow_ray_to) cannot be told a hit by a HULL RECTANGLE — a wall:
+// E and the whole scene on one side of its plane — when its computed origin lies delta_k inside every such plane (risky_h false), nor
+// by E itself when the origin lies delta_E in front of E (risky_e false).  The block with the sign-folded rows comes from the host
+// (classify_scene; count 0: the scene is no such room) and is read HERE, behind the face stage, and held nowhere else.  Three tiers, by ballot:
+//   some live lane risky_h     the stage as it always was, for every live lane;
+//   else some lane risky_e     E's slab pair with the sibling masked and the test loop, for the risky_e lanes alone — the same id, noid
+//                              and tb: what the full stage decides about E, and about nothing else, since nothing else can hit;
+//   else                       no rectangle stage.
+// Each tier returns what the full stage returns, bit for bit: a shadow walk reports whether SOME primitive was hit, never which.
+template <bool ANY_HIT, bool ONE_PAIR, bool TOP_LEAVES, bool HULL = false, class Stack>
 __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o, const f3 d, const float tmax, Stack &st)
 {
+    static_assert(!HULL || (ANY_HIT && !TOP_LEAVES), "SHADOW HULL: shadow rays over a top level of rectangles and boxes");
     typedef WNode N;
     Trav tr;                  // the hit so far, its tie-breaking index and the leaf under test; never the ray
     const RayByValue ray{ o, d, tmax };
@@ -1327,6 +1350,7 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
     constexpr bool kOneBase = stack_one_kernarg_base<Stack>::value;
     constexpr bool kTable = flat_prim_table_on(kOneBase, TOP_LEAVES);      // CHILD-ORDERED PRIMITIVE TABLE, above
     const FlatHdr fh =kernarg_copy<FlatHdr, kOneBase>(sc.flat_off);
+    constexpr int kProfKind = ANY_HIT ? 8 : 0;      // (the sections build tells the stages of a shadow walk from those of a closest-hit walk)
     bool live = true;
     // ---- boxes: face selection per box, uniform over the wave
     uint32_t fm = 0u;
@@ -1342,7 +1366,7 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
         const f3 id = mk(safe_rcp(dl.x), safe_rcp(dl.y), safe_rcp(dl.z));
         fm |= box_select(box_mag_bound(A, B, C, S, omax), ol, dl, id, tmax) << (6u * b);
     }
-    st.prof_flat(0);
+    st.prof_flat(kProfKind + 0);
     // ---- the selected faces, in lock step (box = k / 6, face = k % 6; the face's leaf = child `face` of the box node)
     while (__ballot(live && fm != 0u) != 0ull) {
         if (live && fm != 0u) {
@@ -1361,11 +1385,50 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
             }
         }
     }
-    st.prof_flat(5);
+    st.prof_flat(kProfKind + 5);
     // ---- rectangles
     // (a segment-box pre-test for shadow rays — the box of [o, o + d tmax] against the rectangles' boxes, 12 comparisons per pair
     // instead of the slab tests — was measured in round 6: 53.4 -> 53.9 ms; some lane of nearly every wave grazes the light's box)
-    if (__ballot(live) != 0ull) {
+    // SHADOW HULL, above: which tier this wave's shadow walk takes (0 whenever the scene's block is empty, and in every other walk)
+    uint32_t tier = 0u, e_child = 0u;
+    bool risky_e = false;
+    if constexpr (HULL) {
+        if (__ballot(live) != 0ull) {
+            struct Head { uint32_t count, e_child; float e_delta, pad; float e_row[4]; float delta[kHullRows]; };
+            struct Rows4 { float row[4][4]; };
+            struct Rows2 { float row[2][4]; };
+            static_assert(sizeof(Head) == offsetof(ShadowHull, row) && kHullRows == 8u, "the block in four reads");
+            // (three dependent round trips for the Cornell box's five walls.  Head and six rows requested together and awaited once was
+            // measured: 4 more spilled SGPRs and 40.53 against 40.44 ms — HISTORY.md's index, round 15)
+            const Head hh = kernarg_copy<Head, kOneBase>(sc.hull_off);
+            if (hh.count != 0u) {
+                const Rows4 ra = kernarg_copy<Rows4, kOneBase>(sc.hull_off + sizeof(Head));
+                bool risky_h = false;
+                for (uint32_t k = 0; k < 4u; ++k) risky_h |= !(hull_side(ra.row[k], o.x, o.y, o.z) >= hh.delta[k]);
+                if (hh.count > 4u) {
+                    const Rows2 rb = kernarg_copy<Rows2, kOneBase>(sc.hull_off + sizeof(Head) + sizeof(Rows4));
+                    for (uint32_t k = 0; k < 2u; ++k) risky_h |= !(hull_side(rb.row[k], o.x, o.y, o.z) >= hh.delta[4u + k]);
+                }
+                if (hh.count > 6u) {
+                    const Rows2 rc = kernarg_copy<Rows2, kOneBase>(sc.hull_off + sizeof(Head) + sizeof(Rows4) + sizeof(Rows2));
+                    for (uint32_t k = 0; k < 2u; ++k) risky_h |= !(hull_side(rc.row[k], o.x, o.y, o.z) >= hh.delta[6u + k]);
+                }
+                risky_e = !(hull_side(hh.e_row, o.x, o.y, o.z) >= hh.e_delta);
+                e_child = hh.e_child;
+                const bool any_h = __ballot(live && risky_h) != 0ull, any_e = __ballot(live && risky_e) != 0ull;
+                tier = any_h ? 0u : (any_e ? 1u : 2u);
+#if defined(MTR_PROFILE_OCC) && MTR_PROFILE_OCC == 4
+                if (any_h) st.occ_hull(3);
+                if (any_e) st.occ_hull(4);
+#endif
+            }
+        }
+#if defined(MTR_PROFILE_OCC) && MTR_PROFILE_OCC == 4
+        st.occ_hull(0);
+        if (tier != 2u && __ballot(live) != 0ull) st.occ_hull(1);
+#endif
+    }
+    if ((!HULL || tier != 2u) && __ballot(live) != 0ull) {
         // reciprocal direction and entry-plane offsets as trav_init derives them, here where they are first needed: nothing of
         // them is held across the box stage
         const f3 id = mk(safe_rcp(d.x), safe_rcp(d.y), safe_rcp(d.z));
@@ -1383,7 +1446,11 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
 #define MTR_FLAT_SLAB_PAIR(J) flat_slab_pair<ANY_HIT, J, kOneBase && (MTR_BATCH & 1) != 0>(id, noid, tb, sel0, sel1, sel2, root, \
             TOP_LEAVES ? ((fh.prim_mask >> (2u * J)) & 1u) != 0u : 2u * J < fh.n_quads, \
             TOP_LEAVES ? ((fh.prim_mask >> (2u * J + 1u)) & 1u) != 0u : 2u * J + 1u < fh.n_quads, qm, key1, key2)
-        if (TOP_LEAVES) {
+        if (HULL && tier == 1u) {          // E's pair alone, its sibling masked; for the lanes that are not E-safe
+            flat_slab_pair_at<ANY_HIT, kOneBase && (MTR_BATCH & 1) != 0>(id, noid, tb, sel0, sel1, sel2, root + 48u * (e_child >> 1), e_child & ~1u,
+                                                                         (e_child & 1u) == 0u, (e_child & 1u) != 0u, qm, key1, key2);
+            if (!risky_e) qm = 0u;
+        } else if (TOP_LEAVES) {
             MTR_FLAT_SLAB_PAIR(0u);
             if (fh.prim_mask > 3u) MTR_FLAT_SLAB_PAIR(1u);
             if (fh.prim_mask > 15u) MTR_FLAT_SLAB_PAIR(2u);
@@ -1394,8 +1461,11 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
         }
 #undef MTR_FLAT_SLAB_PAIR
         if (!live) qm = 0u;
-        st.prof_flat(2);
+        st.prof_flat(kProfKind + 2);
         for (uint32_t it = 0; __ballot(qm != 0u) != 0ull; ++it) {
+#if defined(MTR_PROFILE_OCC) && MTR_PROFILE_OCC == 4
+            if (HULL && it == 0u) st.occ_hull(2);
+#endif
             if (qm != 0u) {
                 const uint32_t k = (!ANY_HIT && it == 0u) ? (key1 & 7u) : (uint32_t)__builtin_ctz(qm);
                 qm &= ~(1u << k);
@@ -1413,7 +1483,7 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
             }
         }
     }
-    st.prof_flat(4);
+    st.prof_flat(kProfKind + 4);
     return tr.h;
 }
 #endif
@@ -1423,11 +1493,12 @@ __device__ __forceinline__ Hit flat_walk_device(const SceneView &sc, const f3 o,
 // FLAT: the scene has a flat top level (kTrFlatTop, FlatTop; 2: one that may hold triangle leaves, kTrFlatLeaves) — the device does not walk its
 // tree at all (flat_walk_device); a host build walks the tree, whose result is the same by construction
 // SPH: the tree may hold sphere leaves (trav_leaf_test)
-template <bool ANY_HIT, bool ONE_PAIR = false, int FLAT = 0, bool SPH = !ONE_PAIR && FLAT == 0, class Stack>
+// HULL: SHADOW HULL (flat_walk_device) — the caller vouches that the ray was built by shadow_ray_to towards the scene's one rectangular emitter
+template <bool ANY_HIT, bool ONE_PAIR = false, int FLAT = 0, bool SPH = !ONE_PAIR && FLAT == 0, bool HULL = false, class Stack>
 MTR_HD Hit traverse(const SceneView &sc, f3 o, f3 d, float tmax, Stack &st)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
-    if (FLAT) return flat_walk_device<ANY_HIT, ONE_PAIR, FLAT == 2>(sc, o, d, tmax, st);
+    if (FLAT) return flat_walk_device<ANY_HIT, ONE_PAIR, FLAT == 2, HULL && FLAT == 1>(sc, o, d, tmax, st);
 #endif
     Trav tr;
     trav_init(tr, sc, o, d, tmax, st);
@@ -2289,6 +2360,26 @@ MTR_HD f3 offset_point(f3 sp, f3 sn, f3 dir)
     if (sign_neg(dot(sn, dir))) mag = -mag;
     return fma3(sn, mag, sp);
 }
+// The point (u1, u2) of a rectangular emitter, and the shadow ray from a surface point to an emitter point [spawn_ray_to].
+// SHADOW HULL (mtr_shadow_hull.h) rests on exactly this arithmetic — ep from E's centre and half-edges by two fmas per coordinate,
+// the origin offset along the geometric normal, d = (ep - so) / |ep - so|, tmax = |ep - so| (1 - kShadowEps): the rectangle tests a
+// shadow walk of flat_walk_device skips are proven misses for rays built HERE.  Change one and the proof, its constants and
+// tests/host_shadow_hull.cpp change with it.
+MTR_HD f3 rect_emitter_point(const Emitter &E, float u1, float u2)
+{
+    const float a = fmaf(u1, 2.0f, -1.0f), b = fmaf(u2, 2.0f, -1.0f);
+    return mk(fmaf(E.du[0], a, fmaf(E.dv[0], b, E.center[0])),
+              fmaf(E.du[1], a, fmaf(E.dv[1], b, E.center[1])),
+              fmaf(E.du[2], a, fmaf(E.dv[2], b, E.center[2])));
+}
+MTR_HD Ray shadow_ray_to(f3 sp, f3 gn, f3 ep)
+{
+    const f3 so = offset_point(sp, gn, ep - sp);
+    const f3 sd = ep - so;
+    const float sdist = sqrtf(dot(sd, sd));
+    Ray r; r.o = so; r.d = sd / sdist; r.tmax = sdist * (1.0f - kShadowEps);
+    return r;
+}
 
 // ---- an `area` emitter on an analytic sphere [mitsuba3: Sphere::sample_direction / pdf_direction / sample_position, upstream-unverified]
 // Is the reference point outside?  |c - ref|^2 > (r (1 -+ RayEpsilon))^2, + under flip_normals (E.n[0] < 0)
@@ -2459,10 +2550,7 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
         else if (!kOneRect && E.kind == kEmMesh) {
             mesh_sample_position(sc.samp_tris, sc.face_cdf, sc.face_pmf, E.first_tri, E.n_tris, u1, u2, ep, en, ROUGH ? sc.samp_vn : nullptr);
         } else {
-            float a = fmaf(u1, 2.0f, -1.0f), b = fmaf(u2, 2.0f, -1.0f);
-            ep = mk(fmaf(E.du[0], a, fmaf(E.dv[0], b, E.center[0])),
-                    fmaf(E.du[1], a, fmaf(E.dv[1], b, E.center[1])),
-                    fmaf(E.du[2], a, fmaf(E.dv[2], b, E.center[2])));
+            ep = rect_emitter_point(E, u1, u2);
             en = ld3(E.n);
         }
         f3 dd = ep - c.sp;
@@ -2490,10 +2578,7 @@ MTR_HD void shade_hit(Path &p, const Hit &h, const SceneView &sc, const Film &fi
                 f3 wi_e = c.wi;
                 if (!kDiff && (mat.flags & MTR_MAT_TWOSIDED) && wi_e.z < 0.0f) { wi_e.z = -wi_e.z; wo.z = -wo.z; }
                 // shadow ray: spawn_ray_to(ds.p) + ray_test
-                f3 so = offset_point(c.sp, c.gn, ep - c.sp);
-                f3 sd = ep - so;
-                float sdist = sqrtf(dot(sd, sd));
-                shadow.o = so; shadow.d = sd / sdist; shadow.tmax = sdist * (1.0f - kShadowEps);
+                shadow = shadow_ray_to(c.sp, c.gn, ep);         // (SHADOW HULL: see there)
                 pd.has_shadow = 1u;
                 if constexpr (LEAN && (MTR_PATH_STATE & 2) != 0) { pd.Lr = mk(0, 0, 0); pd.opl = 0.0f; }
                 if (lobes_on<ROUGH, TR>() && bsdf_is_rough(mat.type)) {
@@ -2626,7 +2711,9 @@ MTR_HD bool path_bounce(Path &p, const SceneView &sc, const Film &film, const Re
     bool occluded = false;
     if (pd.has_shadow) {
         stats.shadow++;
-        Hit sh = traverse<true, (TR & kTrLeafPair) != 0u, flat_kind(TR), tr_spheres(TR)>(sc, shadow.o, shadow.d, shadow.tmax, st);
+        // (SHADOW HULL: this is the walk of a ray shade_hit built with shadow_ray_to; with one rectangular emitter it ends on that emitter)
+        constexpr bool kHull = stack_shadow_hull<Stack>::value && flat_kind(TR) == 1 && (TR & kTrOneRectEmitter) != 0u;
+        Hit sh = traverse<true, (TR & kTrLeafPair) != 0u, flat_kind(TR), tr_spheres(TR), kHull>(sc, shadow.o, shadow.d, shadow.tmax, st);
         occluded = sh.prim >= 0;
     }
     st.prof_mark(0);

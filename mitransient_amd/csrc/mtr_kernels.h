@@ -167,6 +167,9 @@ struct FusedArgs {
     // the path-start table of this launch (mtr_start_blocks.h; the lean flat-walk kernels: fused_start_blocks), start_table_bytes(grid, waves)
     // bytes of the context's; last, so that every other member keeps its place in the kernarg segment
     unsigned char *start_tab;
+    // SHADOW HULL (mtr_core.h flat_walk_device, mtr_shadow_hull.h): the scene's block with this render's margin applied; count 0 switches
+    // the shadow walk's tiers off.  Read by the flat-walk kernels of one rectangular emitter alone, at SceneView::hull_off.
+    ShadowHull hull;
 };
 
 struct FusedConfig { int stack; bool scene_lds; bool hist_lds; bool fixed; bool rough; size_t lds_bytes; int grid; int per_cu; uint32_t traits; };

@@ -24,6 +24,7 @@ namespace mtr {
 template <bool ONE_BASE = false>      // ONE_BASE: the kernel reads its argument through kernarg_copy<T, true> (mtr_core.h), the flat walk included
 struct LdsStackT {
     static constexpr bool kOneKernargBase = ONE_BASE;
+    static constexpr bool kShadowHull = true;      // SHADOW HULL (mtr_core.h): k_fused's argument holds the block, SceneView::hull_off says where
     int32_t *base;     // &stack[tid]; entry k lives at base[k * kBlock]  (one bank column per lane)
     int sp;            // the column has FusedArgs::stack_rows rows: one per stacked group + the row push_if writes before it counts
     __device__ __forceinline__ void reset() { sp = 0; }
@@ -60,9 +61,10 @@ struct LdsStackT {
 #if MTR_PROFILE_CYCLES == 3     // ... no sections: the price of ONE round trip, bracketed in `refresh` (tools/cycles_rt.py)
     __device__ __forceinline__ void prof_mark(int) {}
     __device__ __forceinline__ void prof_flat(int) {}
-#elif MTR_PROFILE_CYCLES == 2   // ... the flat walk's stages in sections 0 (box selection), 5 (box faces), 2 (rectangle slabs), 4 (rectangle tests); everything else but shading in 3
+#elif MTR_PROFILE_CYCLES == 2 || MTR_PROFILE_CYCLES == 4   // ... the flat walk's stages in sections 0 (box selection), 5 (box faces), 2 (rectangle slabs), 4 (rectangle tests); everything else but shading in 3
+    // (a shadow walk names its stages 8 + section.  2: both kinds of walk together; 4: the SHADOW walk's stages alone, the closest-hit walk's in 3 — tools/cycles_flat.py --shadow)
     __device__ __forceinline__ void prof_mark(int sec) { unsigned long long t = __builtin_readcyclecounter(); cyc[sec == 1 ? 1 : 3] += t - t0; t0 = t; }
-    __device__ __forceinline__ void prof_flat(int sec) { unsigned long long t = __builtin_readcyclecounter(); cyc[sec] += t - t0; t0 = t; }
+    __device__ __forceinline__ void prof_flat(int sec) { unsigned long long t = __builtin_readcyclecounter(); cyc[MTR_PROFILE_CYCLES == 2 ? (sec & 7) : (sec >= 8 ? sec - 8 : 3)] += t - t0; t0 = t; }
 #else
     __device__ __forceinline__ void prof_mark(int sec) { unsigned long long t = __builtin_readcyclecounter(); cyc[sec] += t - t0; t0 = t; }
     __device__ __forceinline__ void prof_flat(int) {}
@@ -70,6 +72,10 @@ struct LdsStackT {
 #else
     __device__ __forceinline__ void prof_mark(int) {}
     __device__ __forceinline__ void prof_flat(int) {}
+#endif
+#if defined(MTR_PROFILE_OCC) && MTR_PROFILE_OCC == 4      // experiment build (tools/occ.py --hull): shadow walks of the wave | that entered the rectangle slab stage |
+    unsigned int hull_n[5];                                // that ran a rectangle test pass | with a hull-risky live lane | with an E-risky live lane (SHADOW HULL)
+    __device__ __forceinline__ void occ_hull(int k) { const unsigned long long m = __ballot(1); if ((int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) hull_n[k] += 1u; }      // (the first active lane counts for its wave; every lane's counts are summed at the end)
 #endif
 #ifdef MTR_PROFILE_SIMT        // experiment build: lane-steps vs wave-steps of node / triangle tests
     unsigned int ls[2], ws[2], wmax, wcalls;
@@ -379,6 +385,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     sv.samp_tris = a.sc.samp_tris; sv.samp_vn = a.sc.samp_vn; sv.face_pmf = a.sc.face_pmf; sv.face_cdf = a.sc.face_cdf; sv.vnormals = a.sc.vnormals;
     sv.texels = a.sc.texels; sv.tex_info = a.sc.tex_info; sv.uvs = a.sc.uvs;
     sv.flat_off = (uint32_t)(offsetof(FusedArgs, sc) + offsetof(SceneDev, flat));
+    sv.hull_off = (uint32_t)offsetof(FusedArgs, hull);
     if (SCENE_LDS) {
         // a scene staged in LDS is walked through its 8-wide tree (fused_plan); the BVH2 packets stay in HBM, unused
         const uint32_t tree_bytes = a.sc.n_wnodes * (uint32_t)sizeof(WNode);
@@ -454,6 +461,9 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
 #endif
 #ifdef MTR_PROFILE_SIMT
     st.ls[0] = st.ls[1] = st.ws[0] = st.ws[1] = 0; st.wmax = 0; st.wcalls = 0;
+#endif
+#if defined(MTR_PROFILE_OCC) && MTR_PROFILE_OCC == 4
+    for (int k = 0; k < 5; ++k) st.hull_n[k] = 0u;
 #endif
 #ifdef MTR_PROFILE_CYCLES
     for (int k = 0; k < 6; ++k) st.cyc[k] = 0;
@@ -673,6 +683,7 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
 #if MTR_PROFILE_OCC == 2      // (tools/occ.py --starts: iterations in which the start section ran / ran for more than same-pixel restarts)
         occ_alive += occ_ran ? 1u : 0u; occ_wait += occ_need ? 1u : 0u; occ_ran = false; occ_need = false;
 #elif MTR_PROFILE_OCC == 3      // (tools/occ.py --mixed: counted where the paths end, below)
+#elif MTR_PROFILE_OCC == 4      // (tools/occ.py --hull: counted in the shadow walk, mtr_core.h flat_walk_device)
 #else
         occ_alive += (uint32_t)__popcll(__ballot(alive)); occ_wait += (uint32_t)__popcll(__ballot(waiting));
 #endif
@@ -970,9 +981,16 @@ __global__ void __launch_bounds__(kBlock, MINW) k_fused(const FusedArgs a)
     if (kLean) __syncthreads();
     if (tid < 5 && a.counters) atomicAdd(&a.counters->paths + tid, s_cnt[tid]);
 #ifdef MTR_PROFILE_OCC
+#if MTR_PROFILE_OCC == 4      // (three packed pairs of 32-bit counts: config 2 has 2e7 wave iterations)
+    if (a.counters) {
+        atomicAdd(&a.counters->r0, ((unsigned long long)st.hull_n[0] << 32) | st.hull_n[1]); atomicAdd(&a.counters->r1, ((unsigned long long)st.hull_n[2] << 32) | st.hull_n[3]);
+        atomicAdd(&a.counters->splats_overflow, ((unsigned long long)st.hull_n[4] << 32) | ((tid & 63) == 0 ? (occ_iter & 0xffffffffull) : 0ull));
+    }
+#else
     if ((tid & 63) == 0 && a.counters) {
         atomicAdd(&a.counters->splats_overflow, occ_iter); atomicAdd(&a.counters->r0, occ_alive); atomicAdd(&a.counters->r1, occ_wait);
     }
+#endif
 #endif
 #ifdef MTR_PROFILE_TAIL       // experiment build: when does the first / the last workgroup finish (100 MHz wall clock)
     if (tid == 0 && a.counters) {

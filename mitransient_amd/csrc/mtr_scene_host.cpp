@@ -79,7 +79,7 @@ static f3 coordinate_system_s(f3 n)
 static void sh_frame_from(f3 n, f3 dp_du, f3 &s, f3 &t) { sh_frame_of(n, dp_du, s, t); }
 // rows of a rectangle's to_object from (c, du, dv): the inverse of [du dv n^ | c], n^ = normalize(du x dv); f64 -> f32
 // (numerics contract: the same operations, in the same order, as the test oracle's restatement)
-static void rect_to_object(const float c[3], const float du[3], const float dv[3], float rx[4], float ry[4], float rz[4])
+void rect_to_object(const float c[3], const float du[3], const float dv[3], float rx[4], float ry[4], float rz[4])
 {
     const double a[3] = { du[0], du[1], du[2] }, b[3] = { dv[0], dv[1], dv[2] }, o[3] = { c[0], c[1], c[2] };
     double n[3] = { a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0] };
@@ -516,6 +516,44 @@ void classify_scene(const mtr_scene_desc &d, HostScene &hs)
             if (prim_mask >> root.n_quads) hs.traits |= kTrFlatLeaves;
         }
     }
+    classify_shadow_hull(d, hs);
+}
+
+// SHADOW HULL (mtr_shadow_hull.h; mtr_core.h flat_walk_device): a flat top level of rectangles and boxes, ONE rectangular emitter that
+// is one of those rectangles, every other rectangle a wall with the emitter and the whole scene on one side.  Anything else: count 0.
+void classify_shadow_hull(const mtr_scene_desc &d, HostScene &hs)
+{
+    static_assert((float)kHullShadowEps == kShadowEps, "mtr_shadow_hull.h derives delta_E from shade_hit's kShadowEps");
+    hs.hull = ShadowHull{};
+    if ((hs.traits & (kTrFlatTop | kTrFlatLeaves | kTrOneRectEmitter)) != (kTrFlatTop | kTrOneRectEmitter) || hs.ems.size() != 1u) return;
+    const WNode &root = hs.wnodes[0];
+    const Emitter &E = hs.ems[0];
+    float rows[kWide][4];
+    HullInput in{};
+    std::vector<float> verts(d.tri_verts, d.tri_verts + 9u * (size_t)d.n_tris);      // every triangle of the scene: the boxes' faces, the rectangles' carriers
+    uint32_t n_e = 0u;
+    for (uint32_t k = 0; k < root.n_quads && k < kWide; ++k) {
+        const uint32_t first = ((~(uint32_t)root.ref[k]) & ~kLeafQuadBit) >> 2;
+        if (first >= hs.tshade.size()) return;
+        const q4 Z = hs.tpairs[first >> 1].g[0];
+        rows[k][0] = Z.x; rows[k][1] = Z.y; rows[k][2] = Z.z; rows[k][3] = Z.w;
+        const TriShade &t = hs.tshade[first];
+        const f3 du = mk(t.h[2].y, t.h[2].z, t.h[2].w), dv = mk(t.h[3].x, t.h[3].y, t.h[3].z), c = mk(t.h[3].w, t.h[4].x, t.h[4].y);
+        for (int i = 0; i < 4; ++i) {
+            const float a = (i & 1) ? 1.0f : -1.0f, b = (i & 2) ? 1.0f : -1.0f;
+            verts.push_back(c.x + a * du.x + b * dv.x); verts.push_back(c.y + a * du.y + b * dv.y); verts.push_back(c.z + a * du.z + b * dv.z);
+        }
+        if ((fbits(t.h[4].z) >> 16) == 1u) {          // the rectangle that carries emitter 0 — and is the rectangle shade_hit samples, word for word
+            if (c.x != E.center[0] || c.y != E.center[1] || c.z != E.center[2] || du.x != E.du[0] || du.y != E.du[1] || du.z != E.du[2] ||
+                dv.x != E.dv[0] || dv.y != E.dv[1] || dv.z != E.dv[2]) return;
+            in.e_child = k; ++n_e;
+        }
+    }
+    if (n_e != 1u) return;
+    in.n_quads = root.n_quads; in.rows = rows;
+    for (int k = 0; k < 3; ++k) { in.ec[k] = E.center[k]; in.edu[k] = E.du[k]; in.edv[k] = E.dv[k]; in.en[k] = E.n[k]; }
+    in.verts = verts.data(); in.n_verts = verts.size() / 3u;
+    if (!shadow_hull_classify(in, hs.hull)) hs.hull.count = 0u;
 }
 
 const char *derive_nlos(const mtr_scene_desc &d, HostNlos &o)

@@ -39,6 +39,7 @@ struct HostScene {
     bool grey_scene = false;                   // kTrGrey without the NLOS laser (traits_with_laser decides with it)
     bool has_sphere = false;                   // an analytic sphere among the shapes: none of the traits tr_spheres (mtr_core.h) names
     FlatTop flat{};                            // traits & kTrFlatTop: the top level as scalar kernel arguments
+    ShadowHull hull{};                         // SHADOW HULL (mtr_shadow_hull.h): which rectangles a shadow ray is spared; count 0: none
 };
 
 inline bool bsdf_is_lobe(uint32_t type) { return bsdf_is_rough(type) || type == MTR_BSDF_THINDIELECTRIC; }     // what only the extended shading code evaluates
@@ -51,8 +52,13 @@ inline bool scene_is_grey(bool has_sphere, const mtr_material *mats, uint32_t n_
 {
     return !has_sphere && colours_are_grey(mats, n_mats, ems, n_ems, textured);
 }
+// world -> object rows of an analytic rectangle (centre c, half-edges du, dv): x and y along the edges, z the unit normal — the
+// rows of its intersection record (TriPair::g[1], g[2], g[0])
+void rect_to_object(const float c[3], const float du[3], const float dv[3], float rx[4], float ry[4], float rz[4]);
 // fills traits, needs_ext, polar_ok, grey_scene and flat from the tables (derive_scene ends with it)
 void classify_scene(const mtr_scene_desc &d, HostScene &s);
+// ... its last step: fills hull from the traits, the flat top level and the emitter
+void classify_shadow_hull(const mtr_scene_desc &d, HostScene &s);
 // kTrGrey of the NLOS tier: the scene's colours and the laser's irradiance
 uint32_t traits_with_laser(uint32_t traits, bool grey_scene, const float laser_irradiance[3]);
 

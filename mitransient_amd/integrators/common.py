@@ -11,6 +11,7 @@ with the Dr.Jit trace replaced by launches of the HIP library: ``sample_rays`` +
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Tuple
 
 from .. import _cabi, variant
@@ -86,6 +87,13 @@ class TransientADIntegrator:
         # compute units left WITHOUT a workgroup of the persistent fused kernel (extension; mtr_render_params.reserve_cus): room for
         # the kernels of other streams — RCCL's film reduction of the previous row band — while a band renders.  0 on one GPU.
         self.reserve_cus = int(props.get("amd_reserve_cus", 0))
+        # shadow rays of the fused kernel skip the rectangles they provably cannot hit (extension; MTR_SHADOW_HULL_SHIFT): the guard
+        # distances of that proof times this margin.  1: as derived; larger (whole numbers up to 65535): only more careful, the same
+        # picture bit for bit; 0: off
+        m = props.get("amd_shadow_hull_margin", 1)
+        if not (m == 0 or 1 <= m <= 65535):
+            raise Exception("\"amd_shadow_hull_margin\" must be 0 (off) or a value in [1, 65535]")
+        self.shadow_hull_margin = 0 if m == 0 else int(math.ceil(m))
         self.mode = _cabi.MTR_MODE_AUTO            # kernel organisation (extension; not a reference key)
         m = props.get("amd_mode", None)
         if m is not None:
@@ -195,6 +203,8 @@ class TransientADIntegrator:
             f |= _cabi.MTR_FLAG_DETERMINISTIC
         if variant.is_polarized():
             f |= _cabi.MTR_FLAG_POLARIZED         # Mueller throughput, Stokes film (wavefront organisation)
+        m = int(self.shadow_hull_margin)
+        f |= (_cabi.MTR_SHADOW_HULL_OFF if m == 0 else m - 1) << _cabi.MTR_SHADOW_HULL_SHIFT
         return f
 
     def render_params(self, film, seed_value, spp_total, spp_begin=0, spp_end=None,

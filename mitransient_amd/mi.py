@@ -509,6 +509,15 @@ class Scene:
         ctx.check(ctx.lib.mtr_scene_traits(self.gpu_handle(ctx, sensor), C.byref(t)), "mtr_scene_traits")
         return int(t.value)
 
+    def gpu_shadow_hull(self, sensor=0):
+        """rectangles a safe shadow ray of the fused kernel is spared (mtr_scene_shadow_hull: the walls of a room of rectangles with one
+        rectangular light); 0: the scene is no such room"""
+        from .runtime import get_context
+        ctx = get_context()
+        n = C.c_uint32(0)
+        ctx.check(ctx.lib.mtr_scene_shadow_hull(self.gpu_handle(ctx, sensor), C.byref(n)), "mtr_scene_shadow_hull")
+        return int(n.value)
+
     def __del__(self):
         try:
             lib = _cabi.load_library()
