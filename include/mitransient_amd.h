@@ -670,6 +670,42 @@ typedef struct mtr_backproject_desc {
 } mtr_backproject_desc;
 int  mtr_backproject(mtr_ctx *, const mtr_backproject_desc *, const float *capture_dev, float *volume_dev);
 
+/* Phasor-field reconstruction: the phasors of a NLOS capture propagated back into a complex voxel volume (additive, ABI 24: a new
+ * entry point and a new struct; MTR_ABI_VERSION stays 24).
+ *   capture   mtr_backproject's geometry: n_sensor points P_s, n_laser points P_l, the two offset arrays, pairs in ascending (s, l)
+ *             order for MTR_CAPTURE_CONFOCAL / _SINGLE / _EXHAUSTIVE.  phasors (n_pairs, n_freq, 2) f32 — the developed tensor of a
+ *             phasor_hdr_film viewed as rows: P[p, k] = sum of value * exp(-i 2 pi f_k (opl - start_opl)).
+ *   value     d = |P_s - v| + |v - P_l| + sensor_offset[s] + laser_offset[l] for the voxel centre v, tau = d - start_opl;
+ *             V(v) = sum over p of [tau_min <= tau <= tau_max] sum over k of (w_k P[p, k]) exp(+i 2 pi f_k tau), pairs ascending
+ *             and k ascending inside a pair, one complex f32 accumulator per voxel.  volume (nz, ny, nx, 2) f32 is STORED; the same
+ *             call gives the same bits.  A NaN or infinite tau fails the window test: with the bounds -FLT_MAX .. FLT_MAX a voxel
+ *             so far away that d overflows contributes exactly 0.
+ *   exp       freq_step == 0: every exp(+i 2 pi f_k tau) is the conjugate of the film's own term (its range reduction and
+ *             polynomials).  freq_step > 0 is the caller's promise that frequencies[k] = frequencies[0] + k freq_step: the term is
+ *             evaluated so at every 16th k and rotated by exp(+i 2 pi freq_step tau) in between.
+ *   weights   NULL means ones; otherwise w_k P is formed first.
+ * All pointers are device pointers (f32, contiguous; phasors and volume 8-byte aligned, or MTR_ERR_INVALID).  Runs on the
+ * context's stream and does not synchronise it, except to grow the context's workspace (weights given, or few voxels meeting many pairs; mtr_ctx_trim releases it).  MTR_ERR_INVALID before any
+ * launch, the volume untouched: a zero size (n_freq included), a NULL pointer other than weights, n_laser != n_sensor on Confocal,
+ * n_laser != 1 on Single, an empty box, a start_opl that is not finite, tau_min > tau_max or either a NaN, freq_step < 0 or a NaN,
+ * an unknown capture type. */
+typedef struct mtr_phasor_backproject_desc {
+    uint32_t capture_type;          /* MTR_CAPTURE_*                                  */
+    uint32_t n_sensor, n_laser;     /* S, L                                           */
+    uint32_t n_freq;                /* F                                              */
+    float    start_opl, freq_step;
+    float    tau_min, tau_max;      /* the window, in path length from start_opl      */
+    float    volume_min[3], volume_max[3];
+    uint32_t nx, ny, nz;
+    const float *sensor_points;     /* (S, 3) device                                  */
+    const float *laser_points;      /* (L, 3) device                                  */
+    const float *sensor_offset;     /* (S) device                                     */
+    const float *laser_offset;      /* (L) device                                     */
+    const float *frequencies;       /* (F) device                                     */
+    const float *weights;           /* (F) device, or NULL                            */
+} mtr_phasor_backproject_desc;
+int  mtr_phasor_backproject(mtr_ctx *, const mtr_phasor_backproject_desc *, const float *phasors_dev, float *volume_dev);
+
 /* Release the device workspaces the context keeps between calls (ABI 10: the partition workspace of mtr_splat_add on
  * unsorted input — 32 bytes per contribution; a workspace above 256 MiB is released by the call itself, a smaller one
  * stays with the context; ABI 24: the slabs' rows of MTR_MODE_SAMPLES, under the same rule).  Synchronises the context's stream. */

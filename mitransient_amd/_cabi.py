@@ -111,6 +111,16 @@ class mtr_backproject_desc(C.Structure):          # (additive, ABI 24)
                 ("sensor_offset", C.c_void_p), ("laser_offset", C.c_void_p)]
 
 
+class mtr_phasor_backproject_desc(C.Structure):          # (additive, ABI 24)
+    _fields_ = [("capture_type", C.c_uint32), ("n_sensor", C.c_uint32), ("n_laser", C.c_uint32), ("n_freq", C.c_uint32),
+                ("start_opl", C.c_float), ("freq_step", C.c_float), ("tau_min", C.c_float), ("tau_max", C.c_float),
+                ("volume_min", _f3), ("volume_max", _f3),
+                ("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32),
+                ("sensor_points", C.c_void_p), ("laser_points", C.c_void_p),
+                ("sensor_offset", C.c_void_p), ("laser_offset", C.c_void_p),
+                ("frequencies", C.c_void_p), ("weights", C.c_void_p)]
+
+
 class mtr_scene_desc(C.Structure):
     _fields_ = [("n_tris", C.c_uint32),
                 ("tri_verts", C.POINTER(C.c_float)),
@@ -180,7 +190,7 @@ EXPORTS = [
     "mtr_render_fwd", "mtr_render_fwd_tier",
     "mtr_scene_tint_layout", "mtr_scene_set_tints", "mtr_render_grad_tint", "mtr_render_fwd_tint",
     "mtr_scene_set_camera", "mtr_render_samples_plan",
-    "mtr_backproject",
+    "mtr_backproject", "mtr_phasor_backproject",
 ]
 
 _lib = None
@@ -246,6 +256,7 @@ def load_library() -> C.CDLL:
     lib.mtr_scene_set_camera.argtypes = [vp, C.POINTER(mtr_camera)]      # (ABI 24)
     lib.mtr_render_samples_plan.argtypes = [vp, C.POINTER(mtr_render_params)] + [C.POINTER(C.c_uint32)] * 4
     lib.mtr_backproject.argtypes = [vp, C.POINTER(mtr_backproject_desc), vp, vp]      # (additive, ABI 24)
+    lib.mtr_phasor_backproject.argtypes = [vp, C.POINTER(mtr_phasor_backproject_desc), vp, vp]      # (additive, ABI 24)
     if lib.mtr_abi_version() != MTR_ABI_VERSION:
         raise MitransientAMDError("libmitransient_amd.so ABI version mismatch; rebuild")
     _lib = lib
