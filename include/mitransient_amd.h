@@ -670,6 +670,21 @@ typedef struct mtr_backproject_desc {
 } mtr_backproject_desc;
 int  mtr_backproject(mtr_ctx *, const mtr_backproject_desc *, const float *capture_dev, float *volume_dev);
 
+/* The transpose of mtr_backproject: a voxel volume scattered into a NLOS capture — the three-bounce forward model of a hidden
+ * volume, and the gradient of a backprojection (additive, ABI 24: a new entry point on mtr_backproject's struct;
+ * MTR_ABI_VERSION stays 24).
+ *   value     with mtr_backproject's path length d and lookup of (voxel v, row p): NEAREST adds volume[v] to
+ *             capture[p, floor(u)], LINEAR adds (1 - w) volume[v] and w volume[v] to the two bins it interpolates between, each
+ *             only inside [0, T).  The weight of (v, p, bin) is bit-identical to the one mtr_backproject reads with: with the
+ *             same description the two calls are exact transposes, up to the order of their f32 sums.
+ *   capture   (rows, T) f32 in mtr_backproject's row order is STORED: every cell is written, a cell nothing reaches is 0.
+ *             Voxels that are exactly 0 are skipped (a NaN is not).  The sum of a cell is taken with float atomics in LDS,
+ *             whose order is not fixed: the same call gives the same capture to rounding, NOT to bits.
+ * All pointers are device pointers (f32, contiguous).  Runs on the context's stream and does not synchronise it, except to grow
+ * the context's workspace when few rows meet many voxels (mtr_ctx_trim releases it).  MTR_ERR_INVALID before any launch, the
+ * capture untouched: whatever mtr_backproject refuses, more than 2^31 - 1 voxels, rows or (row, 16384-bin window) pairs. */
+int  mtr_forward_project(mtr_ctx *, const mtr_backproject_desc *, const float *volume_dev, float *capture_dev);
+
 /* Phasor-field reconstruction: the phasors of a NLOS capture propagated back into a complex voxel volume (additive, ABI 24: a new
  * entry point and a new struct; MTR_ABI_VERSION stays 24).
  *   capture   mtr_backproject's geometry: n_sensor points P_s, n_laser points P_l, the two offset arrays, pairs in ascending (s, l)

@@ -69,6 +69,38 @@ MTR_HD float bp_tap_linear(const float *row, uint32_t T, float start_opl, float 
     return (1.0f - w) * h0 + w * h1;
 }
 
+// The same lookups and the same path length for the transpose (mtr_forward_project.h), which adds where bp_tap_* read: the
+// operations of bp_tap_nearest / bp_tap_linear / bp_voxel in their order, restated rather than shared so that k_backproject
+// keeps its instructions.  nearest: the bin, or false outside the window.  linear: the lower tap b0 (b0 + 1 is the other;
+// either may lie outside [0, T)) and the weight w of the upper one, or false when both lie outside.
+MTR_HD bool bp_bin_nearest(uint32_t T, float start_opl, float bin_width, float d, uint32_t &b)
+{
+    const float u = (d - start_opl) / bin_width;
+    if (!(u >= 0.0f && u < (float)T)) return false;
+    b = (uint32_t)floorf(u);
+    return b < T;
+}
+
+MTR_HD bool bp_bins_linear(uint32_t T, float start_opl, float bin_width, float d, int64_t &b0, float &w)
+{
+    const float u = (d - start_opl) / bin_width - 0.5f;
+    if (!(u >= -1.0f && u < (float)T)) return false;
+    const float b0f = floorf(u);
+    w = u - b0f;
+    b0 = (int64_t)b0f;
+    return true;
+}
+
+// the path length of voxel centre (vx, vy, vz) for one pair (P_s, so), (P_l, lo); Confocal never reads pl
+template <uint32_t CAPTURE>
+MTR_HD float bp_path(const float *ps, const float *pl, float so, float lo, float vx, float vy, float vz)
+{
+    const float r1 = bp_norm(ps[0] - vx, ps[1] - vy, ps[2] - vz);
+    float r2 = r1;                                          // Confocal: P_l = P_s, and (-x)^2 = x^2 — the same bits
+    if (CAPTURE != MTR_CAPTURE_CONFOCAL) r2 = bp_norm(vx - pl[0], vy - pl[1], vz - pl[2]);
+    return ((r1 + r2) + so) + lo;
+}
+
 // the sum of voxel (ix, iy, iz) over the pairs [p0, p1) of the capture's rows, ascending
 template <uint32_t CAPTURE, bool LINEAR>
 MTR_HD float bp_voxel(const BpArgs &a, uint32_t ix, uint32_t iy, uint32_t iz, uint64_t p0, uint64_t p1)
@@ -90,7 +122,7 @@ MTR_HD float bp_voxel(const BpArgs &a, uint32_t ix, uint32_t iy, uint32_t iz, ui
             r2 = bp_norm(vx - pl[0], vy - pl[1], vz - pl[2]);
             lo = a.laser_offset[(size_t)l];
         }
-        const float d = ((r1 + r2) + a.sensor_offset[(size_t)s]) + lo;
+        const float d = ((r1 + r2) + a.sensor_offset[(size_t)s]) + lo;      // (bp_path restates this for the transpose)
         const float *row = a.capture + (size_t)p * a.T;
         acc += LINEAR ? bp_tap_linear(row, a.T, a.start_opl, a.bin_width, d) : bp_tap_nearest(row, a.T, a.start_opl, a.bin_width, d);
         if (CAPTURE == MTR_CAPTURE_EXHAUSTIVE) { if (++l == a.L) { l = 0u; ++s; } }

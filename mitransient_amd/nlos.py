@@ -2,7 +2,9 @@
 all three resolve to one world-space point and share ``_aim``.
 
 ``capture_geometry`` / ``backproject`` / ``laplacian_filter`` turn a rendered capture back into a volume of the hidden
-scene: the sum runs in HIP (``mtr_backproject``, csrc/mtr_backproject.hip), torch is plumbing.  ``phasor_backproject`` does the
+scene: the sum runs in HIP (``mtr_backproject``, csrc/mtr_backproject.hip), torch is plumbing.  ``forward_project`` is its
+transpose (``mtr_forward_project``, csrc/mtr_forward_project.hip): the two are each other's autograd backward, and
+``reconstruct_cgls`` iterates them to fit a volume to a capture.  ``phasor_backproject`` does the
 same for the phasors a ``phasor_hdr_film`` develops (``mtr_phasor_backproject``, csrc/mtr_phasor_backproject.hip)."""
 from __future__ import annotations
 
@@ -198,32 +200,112 @@ def _checked_box(who, volume_min, volume_max, resolution):
     return vmin, vmax, res
 
 
-def _checked_call(transient, g, volume_min, volume_max, resolution, interpolation, channel, filter):
+def _checked_call(transient, g, volume_min, volume_max, resolution, interpolation, channel, filter, who="backproject"):
     """Everything ``backproject`` can refuse without a GPU; returns (S, L, T, has a channel axis, vmin, vmax, (nx, ny, nz))"""
     if interpolation not in _INTERPOLATIONS:
-        raise ValueError(f"backproject: interpolation must be 'nearest' or 'linear', not {interpolation!r}")
+        raise ValueError(f"{who}: interpolation must be 'nearest' or 'linear', not {interpolation!r}")
     if filter not in (None, "laplacian"):
-        raise ValueError(f"backproject: filter must be None or 'laplacian', not {filter!r}")
-    H, W, S, L = _checked_geometry("backproject", g)
+        raise ValueError(f"{who}: filter must be None or 'laplacian', not {filter!r}")
+    H, W, S, L = _checked_geometry(who, g)
     T = int(g.temporal_bins)
     if T <= 0:
-        raise ValueError("backproject: a capture of zero size")
+        raise ValueError(f"{who}: a capture of zero size")
     if not g.bin_width_opl > 0.0:
-        raise ValueError(f"backproject: bin_width_opl must be positive, got {g.bin_width_opl}")
+        raise ValueError(f"{who}: bin_width_opl must be positive, got {g.bin_width_opl}")
     shape = tuple(int(v) for v in transient.shape)
-    t_axis = _checked_rows("backproject", shape, g, H, W, L, ("(H, W, T) or (H, W, T, C)", "(H, W, Lx, Ly, T) or (H, W, Lx, Ly, T, C)"))
+    t_axis = _checked_rows(who, shape, g, H, W, L, ("(H, W, T) or (H, W, T, C)", "(H, W, Lx, Ly, T) or (H, W, Lx, Ly, T, C)"))
     if shape[t_axis] != T:
-        raise ValueError(f"backproject: the capture has {shape[t_axis]} time bins, the geometry {T}")
+        raise ValueError(f"{who}: the capture has {shape[t_axis]} time bins, the geometry {T}")
     has_c = len(shape) == t_axis + 2
     if channel is not None:
         if not has_c:
-            raise ValueError("backproject: channel= needs a capture with a channel axis")
+            raise ValueError(f"{who}: channel= needs a capture with a channel axis")
         if not 0 <= int(channel) < shape[-1]:
-            raise ValueError(f"backproject: channel {channel} is outside the capture's {shape[-1]} channels")
+            raise ValueError(f"{who}: channel {channel} is outside the capture's {shape[-1]} channels")
     if has_c and shape[-1] == 0:
-        raise ValueError("backproject: a capture without channels")
-    vmin, vmax, res = _checked_box("backproject", volume_min, volume_max, resolution)
+        raise ValueError(f"{who}: a capture without channels")
+    vmin, vmax, res = _checked_box(who, volume_min, volume_max, resolution)
     return S, L, T, has_c, vmin, vmax, res
+
+
+class _Projection:
+    """One geometry and one volume box on the device: what ``mtr_backproject`` and ``mtr_forward_project`` share in a call and
+    in the autograd graph of a call.  ``run(entry, src)`` launches either on a contiguous f32 CUDA tensor."""
+
+    def __init__(self, ctx, g, S, L, T, vmin, vmax, res, interpolation, capture_shape):
+        import torch
+        self.ctx, self.dev = ctx, torch.device("cuda", ctx.device_index)
+
+        def dev_f32(a):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.dev)
+        # (the four arrays live as long as this object: a graph that holds it can run its backward later)
+        self.arrays = (dev_f32(g.sensor_points.reshape(-1, 3)), dev_f32(g.laser_points), dev_f32(g.sensor_offset.reshape(-1)),
+                       dev_f32(g.laser_offset))
+        d = self.desc = _cabi.mtr_backproject_desc()
+        d.capture_type, d.interpolation = g.capture_type, _INTERPOLATIONS[interpolation]
+        d.n_sensor, d.n_laser, d.temporal_bins = S, L, T
+        d.start_opl, d.bin_width_opl = np.float32(g.start_opl), np.float32(g.bin_width_opl)
+        for k in range(3):
+            d.volume_min[k], d.volume_max[k] = np.float32(vmin[k]), np.float32(vmax[k])
+        d.nx, d.ny, d.nz = res
+        d.sensor_points, d.laser_points, d.sensor_offset, d.laser_offset = (t.data_ptr() for t in self.arrays)
+        self.shapes = {"mtr_backproject": (res[2], res[1], res[0]), "mtr_forward_project": tuple(capture_shape)}
+
+    def run(self, entry, src):
+        import torch
+        src = src.to(device=self.dev, dtype=torch.float32).contiguous()
+        other = "mtr_forward_project" if entry == "mtr_backproject" else "mtr_backproject"
+        if tuple(src.shape) != self.shapes[other]:
+            raise ValueError(f"{entry}: the input has shape {tuple(src.shape)}, {self.shapes[other]} is expected")
+        out = torch.empty(self.shapes[entry], dtype=torch.float32, device=self.dev)
+        with torch.cuda.device(self.dev):
+            self.ctx.bind_current_stream()
+            self.ctx.check(getattr(self.ctx.lib, entry)(self.ctx.handle, C.byref(self.desc), C.c_void_p(src.data_ptr()),
+                                                        C.c_void_p(out.data_ptr())), entry)
+        # (src is released to torch's caching allocator, which hands it out again in stream order)
+        return out
+
+
+_functions = None
+
+
+def _autograd_pair():
+    """(Backproject, ForwardProject): the two kernels as torch.autograd.Functions, each the other's backward — the operators are
+    transposes of one another (csrc/mtr_forward_project.h)"""
+    global _functions
+    if _functions is None:
+        import torch
+
+        class Backproject(torch.autograd.Function):
+            @staticmethod
+            def forward(fctx, capture, projection):
+                fctx.projection = projection
+                return projection.run("mtr_backproject", capture)
+
+            @staticmethod
+            def backward(fctx, grad_volume):
+                return ForwardProject.apply(grad_volume, fctx.projection), None
+
+        class ForwardProject(torch.autograd.Function):
+            @staticmethod
+            def forward(fctx, volume, projection):
+                fctx.projection = projection
+                return projection.run("mtr_forward_project", volume)
+
+            @staticmethod
+            def backward(fctx, grad_capture):
+                return Backproject.apply(grad_capture, fctx.projection), None
+
+        _functions = (Backproject, ForwardProject)
+    return _functions
+
+
+def _as_tensor(value):
+    """(a torch tensor of what a call was handed, whether a graph is wanted through it)"""
+    import torch
+    t = value if isinstance(value, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(value))
+    wanted = bool(t.requires_grad and torch.is_grad_enabled() and (t.is_floating_point() or t.is_complex()))
+    return (t if wanted else t.detach()), wanted
 
 
 def backproject(transient, geometry, volume_min, volume_max, resolution, interpolation="nearest", channel=None, filter=None):
@@ -238,10 +320,15 @@ def backproject(transient, geometry, volume_min, volume_max, resolution, interpo
     ``filter="laplacian"`` applies :func:`laplacian_filter`.  Returns a CUDA torch tensor (nz, ny, nx); the sum has a fixed
     order, the same call gives the same bits.
 
+    Autograd: a torch tensor that requires grad (``transient.torch()`` of a render whose ``params`` hold such tensors
+    included), with grad enabled, gives a volume with a ``grad_fn`` — the backward pass is :func:`forward_project`, the
+    transpose, so a loss on the volume reaches the capture and through ``mi.render`` the scene parameters; the channel
+    selection and the filter are torch ops and differentiate by themselves.  Any other input takes the same path as ever,
+    gives the same bits and carries no graph.
+
     A capture rendered in the frequency domain (``phasor_hdr_film``) is reconstructed by :func:`phasor_backproject`.
-    Out of scope: autograd through ``backproject`` (the result carries no graph), LCT / f-k migration, non-rectangular relay
-    walls in ``capture_geometry`` (a hand-built ``CaptureGeometry`` takes any points).
-    Shape and geometry mismatches raise ``ValueError`` before the GPU is touched."""
+    Out of scope: LCT / f-k migration, non-rectangular relay walls in ``capture_geometry`` (a hand-built ``CaptureGeometry``
+    takes any points).  Shape and geometry mismatches raise ``ValueError`` before the GPU is touched."""
     from .tensor import TensorXf
     if isinstance(transient, TensorXf):
         transient = transient.torch()
@@ -253,32 +340,121 @@ def backproject(transient, geometry, volume_min, volume_max, resolution, interpo
     from .runtime import get_context
     ctx = get_context()
     import torch
-    dev = torch.device("cuda", ctx.device_index)
-    t = transient if isinstance(transient, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(transient))
-    t = t.detach().to(device=dev, dtype=torch.float32)
+    t, wanted = _as_tensor(transient)
+    t = t.to(device=torch.device("cuda", ctx.device_index), dtype=torch.float32)
     if has_c:
         t = t[..., int(channel)] if channel is not None else (t[..., 0] if t.shape[-1] == 1 else t.mean(dim=-1))
     t = t.contiguous()
-
-    def dev_f32(a):
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-    sp, lp = dev_f32(g.sensor_points.reshape(-1, 3)), dev_f32(g.laser_points)
-    so, lo = dev_f32(g.sensor_offset.reshape(-1)), dev_f32(g.laser_offset)
-    volume = torch.empty((res[2], res[1], res[0]), dtype=torch.float32, device=dev)
-    d = _cabi.mtr_backproject_desc()
-    d.capture_type, d.interpolation = g.capture_type, _INTERPOLATIONS[interpolation]
-    d.n_sensor, d.n_laser, d.temporal_bins = S, L, T
-    d.start_opl, d.bin_width_opl = np.float32(g.start_opl), np.float32(g.bin_width_opl)
-    for k in range(3):
-        d.volume_min[k], d.volume_max[k] = np.float32(vmin[k]), np.float32(vmax[k])
-    d.nx, d.ny, d.nz = res
-    d.sensor_points, d.laser_points, d.sensor_offset, d.laser_offset = sp.data_ptr(), lp.data_ptr(), so.data_ptr(), lo.data_ptr()
-    with torch.cuda.device(dev):
-        ctx.bind_current_stream()
-        ctx.check(ctx.lib.mtr_backproject(ctx.handle, C.byref(d), C.c_void_p(t.data_ptr()), C.c_void_p(volume.data_ptr())), "mtr_backproject")
-    # (t, sp, lp, so, lo are released to torch's caching allocator, which hands them out again in stream order)
+    projection = _Projection(ctx, g, S, L, T, vmin, vmax, res, interpolation, t.shape)
+    volume = _autograd_pair()[0].apply(t, projection) if wanted else projection.run("mtr_backproject", t)
     return laplacian_filter(volume) if filter == "laplacian" else volume
 
+
+def _checked_forward_call(who, shape, g, volume_min, volume_max, interpolation):
+    """Everything ``forward_project`` can refuse without a GPU; returns (S, L, T, vmin, vmax, (nx, ny, nz), the capture's shape)"""
+    if interpolation not in _INTERPOLATIONS:
+        raise ValueError(f"{who}: interpolation must be 'nearest' or 'linear', not {interpolation!r}")
+    H, W, S, L = _checked_geometry(who, g)
+    T = int(g.temporal_bins)
+    if T <= 0:
+        raise ValueError(f"{who}: a capture of zero size")
+    if not g.bin_width_opl > 0.0:
+        raise ValueError(f"{who}: bin_width_opl must be positive, got {g.bin_width_opl}")
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 3 or min(shape) <= 0:
+        raise ValueError(f"{who}: a (nz, ny, nx) volume is expected, got shape {shape}")
+    if g.capture_type == _cabi.MTR_CAPTURE_EXHAUSTIVE:
+        grid = g.laser_grid
+        if grid is None:
+            raise ValueError(f"{who}: an exhaustive geometry needs laser_grid = (Lx, Ly) to shape the capture")
+        grid = tuple(int(v) for v in grid)
+        if len(grid) != 2 or grid[0] * grid[1] != L:
+            raise ValueError(f"{who}: laser_grid {grid} does not match the geometry's {L} laser points")
+        capture_shape = (H, W, grid[0], grid[1], T)
+    else:
+        capture_shape = (H, W, T)
+    vmin, vmax, res = _checked_box(who, volume_min, volume_max, (shape[2], shape[1], shape[0]))
+    return S, L, T, vmin, vmax, res, capture_shape
+
+
+def forward_project(volume, geometry, volume_min, volume_max, interpolation="nearest"):
+    """The transpose of :func:`backproject`: scatter a volume of the hidden scene into the capture it would produce, on the GPU
+    (``mtr_forward_project``) — the three-bounce forward model of a hidden volume without the cosine and 1/r^2 factors, the
+    gradient of a backprojection, and the other half of every iterative reconstruction (:func:`reconstruct_cgls`).
+
+    ``volume``: (nz, ny, nx), a torch tensor on any device and of any dtype, a numpy array or a ``TensorXf``; the resolution is
+    its shape, the box ``volume_min`` .. ``volume_max``.  Capture cell ``(s, l, b)`` receives the sum of the voxels whose path
+    length ``backproject`` looks up in bin ``b`` — with the same weights, bit for bit, so that with the same arguments
+    ``<backproject(y), x> = <y, forward_project(x)>`` up to f32 rounding.  Returns a CUDA f32 tensor (H, W, T); for an Exhaustive
+    geometry (H, W, Lx, Ly, T) with (Lx, Ly) = ``geometry.laser_grid``.  The cells are summed with float atomics in LDS, whose
+    order is not fixed: the same call gives the same capture to rounding, not to bits.
+
+    Autograd: a volume that requires grad gives a capture with a ``grad_fn`` whose backward is ``backproject``.
+    Refusals are ``ValueError`` before the GPU is touched."""
+    from .tensor import TensorXf
+    if isinstance(volume, TensorXf):
+        volume = volume.torch()
+    if not hasattr(volume, "shape"):
+        volume = np.asarray(volume)
+    g = geometry
+    S, L, T, vmin, vmax, res, capture_shape = _checked_forward_call("forward_project", volume.shape, g, volume_min, volume_max, interpolation)
+    from .runtime import get_context
+    ctx = get_context()
+    import torch
+    t, wanted = _as_tensor(volume)
+    t = t.to(device=torch.device("cuda", ctx.device_index), dtype=torch.float32).contiguous()
+    projection = _Projection(ctx, g, S, L, T, vmin, vmax, res, interpolation, capture_shape)
+    return _autograd_pair()[1].apply(t, projection) if wanted else projection.run("mtr_forward_project", t)
+
+
+def reconstruct_cgls(transient, geometry, volume_min, volume_max, resolution, iterations=10, interpolation="linear", channel=None):
+    """Fit a hidden volume to a capture: CGLS on ``min |forward_project(x) - y|`` from ``x = 0``, one ``forward_project`` and one
+    ``backproject`` per iteration on the GPU, the rest torch ops.
+
+    ``transient`` and ``channel`` as in :func:`backproject` (channels are averaged unless one is picked).  Returns
+    ``(volume, residuals)``: the CUDA f32 volume (nz, ny, nx) after ``iterations`` steps and ``residuals[k] = |r_k| / |y|`` as
+    Python floats, ``k = 0 .. iterations`` (``residuals[0] = 1``).  The result carries no graph.  A capture that is all zero
+    returns a zero volume."""
+    who = "reconstruct_cgls"
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 1:
+        raise ValueError(f"{who}: iterations is a positive int, got {iterations!r}")
+    from .tensor import TensorXf
+    if isinstance(transient, TensorXf):
+        transient = transient.torch()
+    if not hasattr(transient, "shape"):
+        transient = np.asarray(transient)
+    g = geometry
+    S, L, T, has_c, vmin, vmax, res = _checked_call(transient, g, volume_min, volume_max, resolution, interpolation, channel, None, who)
+    from .runtime import get_context
+    ctx = get_context()
+    import torch
+    with torch.no_grad():
+        y = _as_tensor(transient)[0].to(device=torch.device("cuda", ctx.device_index), dtype=torch.float32)
+        if has_c:
+            y = y[..., int(channel)] if channel is not None else (y[..., 0] if y.shape[-1] == 1 else y.mean(dim=-1))
+        y = y.contiguous()
+        projection = _Projection(ctx, g, S, L, T, vmin, vmax, res, interpolation, y.shape)
+
+        def dot(a):
+            return float(torch.sum(a.double() * a.double()))
+        r = y.clone()
+        s = projection.run("mtr_backproject", r)
+        x, p = torch.zeros_like(s), s.clone()
+        gamma, norm_y = dot(s), dot(y) ** 0.5
+        residuals = [1.0]
+        for _ in range(int(iterations)):
+            if gamma == 0.0:                        # (converged, or y = 0)
+                residuals.append(residuals[-1])
+                continue
+            q = projection.run("mtr_forward_project", p)
+            alpha = gamma / dot(q)
+            x += alpha * p
+            r -= alpha * q
+            s = projection.run("mtr_backproject", r)
+            gamma, last = dot(s), gamma
+            p = s + (gamma / last) * p
+            residuals.append(dot(r) ** 0.5 / norm_y)
+    return x, residuals
 
 # ---------------------------------------------------------------- phasor-field reconstruction
 _FLT_MAX = float(np.finfo(np.float32).max)
