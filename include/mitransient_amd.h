@@ -721,6 +721,24 @@ typedef struct mtr_phasor_backproject_desc {
 } mtr_phasor_backproject_desc;
 int  mtr_phasor_backproject(mtr_ctx *, const mtr_phasor_backproject_desc *, const float *phasors_dev, float *volume_dev);
 
+/* The conjugate transpose of mtr_phasor_backproject: a complex voxel volume turned into the phasors it would produce — the forward
+ * model of a phasor-field reconstruction, and the gradient of one (additive, ABI 24: a new entry point on
+ * mtr_phasor_backproject's struct; MTR_ABI_VERSION stays 24).
+ *   value     with mtr_phasor_backproject's tau, window test M(v, p) and factor z(v, p, k) of (voxel v, row p, frequency k):
+ *             Q[p, k] = w_k sum over v of M(v, p) U(v) conj(z(v, p, k)).  z is evaluated by the same functions, at the same
+ *             anchors (every 16th k of a uniform table, rotations in between): with the same description the two calls are exact
+ *             conjugate transposes, up to the order of their f32 sums.  For a real non-negative U this is the film's convention,
+ *             sum of value * exp(-i 2 pi f_k (opl - start_opl)): the phasors of a volume of scatterers, without cosines and 1/r^2.
+ *   volume    (nz, ny, nx, 2) f32, read.  A voxel outside the window of a row does not reach it, whatever it holds.
+ *   phasors   (n_pairs, n_freq, 2) f32 in mtr_phasor_backproject's row order is STORED: every element is written, an element
+ *             nothing reaches is 0.  The sums have a fixed order (no float atomics): the same call gives the same bits.
+ *   weights   NULL means ones; otherwise w_k multiplies the finished sum, two f32 products per element.
+ * All pointers are device pointers (f32, contiguous; volume and phasors 8-byte aligned, or MTR_ERR_INVALID).  Runs on the
+ * context's stream and does not synchronise it, except to grow the context's workspace when few rows meet many voxels
+ * (mtr_ctx_trim releases it).  MTR_ERR_INVALID before any launch, the phasors untouched: whatever mtr_phasor_backproject
+ * refuses, more than 2^31 - 1 voxels, rows or (row, block of 16 frequencies) pairs. */
+int  mtr_phasor_forward_project(mtr_ctx *, const mtr_phasor_backproject_desc *, const float *volume_dev, float *phasors_dev);
+
 /* Release the device workspaces the context keeps between calls (ABI 10: the partition workspace of mtr_splat_add on
  * unsorted input — 32 bytes per contribution; a workspace above 256 MiB is released by the call itself, a smaller one
  * stays with the context; ABI 24: the slabs' rows of MTR_MODE_SAMPLES, under the same rule).  Synchronises the context's stream. */

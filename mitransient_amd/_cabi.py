@@ -190,7 +190,7 @@ EXPORTS = [
     "mtr_render_fwd", "mtr_render_fwd_tier",
     "mtr_scene_tint_layout", "mtr_scene_set_tints", "mtr_render_grad_tint", "mtr_render_fwd_tint",
     "mtr_scene_set_camera", "mtr_render_samples_plan",
-    "mtr_backproject", "mtr_phasor_backproject", "mtr_forward_project",
+    "mtr_backproject", "mtr_phasor_backproject", "mtr_forward_project", "mtr_phasor_forward_project",
 ]
 
 _lib = None
@@ -258,6 +258,7 @@ def load_library() -> C.CDLL:
     lib.mtr_backproject.argtypes = [vp, C.POINTER(mtr_backproject_desc), vp, vp]      # (additive, ABI 24)
     lib.mtr_phasor_backproject.argtypes = [vp, C.POINTER(mtr_phasor_backproject_desc), vp, vp]      # (additive, ABI 24)
     lib.mtr_forward_project.argtypes = [vp, C.POINTER(mtr_backproject_desc), vp, vp]      # (additive, ABI 24)
+    lib.mtr_phasor_forward_project.argtypes = [vp, C.POINTER(mtr_phasor_backproject_desc), vp, vp]      # (additive, ABI 24)
     if lib.mtr_abi_version() != MTR_ABI_VERSION:
         raise MitransientAMDError("libmitransient_amd.so ABI version mismatch; rebuild")
     _lib = lib

@@ -16,6 +16,7 @@
 #include "mtr_backproject.h"
 #include "mtr_forward_project.h"
 #include "mtr_phasor_backproject.h"
+#include "mtr_phasor_forward_project.h"
 
 #include <hip/hip_runtime.h>
 #include <cassert>
@@ -48,7 +49,7 @@ struct mtr_ctx {
     void *d_part = nullptr; size_t part_cap = 0;         // ... and the partition workspace of unsorted input (at most 256 MiB of it kept between calls, until mtr_ctx_trim / destroy)
     void *d_samples = nullptr; size_t samples_cap = 0;   // MTR_MODE_SAMPLES: the slabs' rows (at most 256 MiB kept between calls, until mtr_ctx_trim / destroy)
     void *d_start = nullptr; size_t start_cap = 0;       // k_fused's lean kernels: kStartSlots path-start tables (mtr_start_blocks.h), one per ticket counter of the rotation (until mtr_ctx_trim / destroy)
-    void *d_bp = nullptr; size_t bp_cap = 0;             // mtr_backproject / mtr_forward_project / mtr_phasor_backproject: the slabs' planes of a call with few voxels and many pairs (few rows and many voxels), the weighted rows of a phasor call (until mtr_ctx_trim / destroy)
+    void *d_bp = nullptr; size_t bp_cap = 0;             // mtr_backproject / mtr_forward_project / mtr_phasor_backproject / mtr_phasor_forward_project: the slabs' planes of a call with few voxels and many pairs (few rows and many voxels), the weighted rows of a phasor call (until mtr_ctx_trim / destroy)
 };
 
 struct WfWorkspace {            // MTR_MODE_WAVEFRONT buffers, sized for one tile, reused across renders
@@ -1426,6 +1427,21 @@ int mtr_phasor_backproject(mtr_ctx *c, const mtr_phasor_backproject_desc *d, con
     if (const size_t n = pb_weighted_floats(a) + pb_plane_floats(a, pl))
         if (int r = grow_device_buffer(c, &c->d_bp, &c->bp_cap, n * sizeof(float))) return r;
     HIP_TRY(c, launch_phasor_backproject(a, pl, (float *)c->d_bp, volume, c->stream));
+    return MTR_OK;
+}
+
+int mtr_phasor_forward_project(mtr_ctx *c, const mtr_phasor_backproject_desc *d, const float *volume, float *phasors)
+{
+    if (!c) return fail(nullptr, MTR_ERR_INVALID, "mtr_phasor_forward_project: ctx is NULL");
+    if (const char *why = pf_check(d, volume, phasors)) return fail(c, MTR_ERR_INVALID, std::string("mtr_phasor_forward_project: ") + why);
+    const PbArgs a = pb_args(*d, nullptr);
+    PfPlan pl;
+    if (!pf_plan(a.nx, a.ny, a.nz, a.n_pairs, a.F, c->n_cu, pl))
+        return fail(c, MTR_ERR_INVALID, "mtr_phasor_forward_project: the volume has too many voxels, or the capture too many rows, for one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (const size_t n = pf_plane_floats(a, pl))
+        if (int r = grow_device_buffer(c, &c->d_bp, &c->bp_cap, n * sizeof(float))) return r;
+    HIP_TRY(c, launch_phasor_forward_project(a, pl, volume, (float *)c->d_bp, phasors, c->stream));
     return MTR_OK;
 }
 

@@ -5,7 +5,9 @@ all three resolve to one world-space point and share ``_aim``.
 scene: the sum runs in HIP (``mtr_backproject``, csrc/mtr_backproject.hip), torch is plumbing.  ``forward_project`` is its
 transpose (``mtr_forward_project``, csrc/mtr_forward_project.hip): the two are each other's autograd backward, and
 ``reconstruct_cgls`` iterates them to fit a volume to a capture.  ``phasor_backproject`` does the
-same for the phasors a ``phasor_hdr_film`` develops (``mtr_phasor_backproject``, csrc/mtr_phasor_backproject.hip)."""
+same for the phasors a ``phasor_hdr_film`` develops (``mtr_phasor_backproject``, csrc/mtr_phasor_backproject.hip), and
+``phasor_forward_project`` is its conjugate transpose (``mtr_phasor_forward_project``, csrc/mtr_phasor_forward_project.hip): the
+same pairing in the frequency domain, with autograd and ``phasor_reconstruct_cgls``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -474,11 +476,10 @@ def uniform_frequency_step(frequencies):
     return float(step) if np.all(np.abs(f - (f[0] + np.arange(f.size) * step)) <= tol) else 0.0
 
 
-def _checked_phasor_call(shape, is_complex, g, frequencies, weights, window, volume_min, volume_max, resolution):
-    """Everything ``phasor_backproject`` can refuse without a GPU; returns (S, L, frequencies f32, weights f32 or None,
-    (tau_min, tau_max), vmin, vmax, (nx, ny, nz))"""
+def _checked_phasor_setup(who, g, frequencies, weights, window):
+    """What the phasor calls refuse in a geometry, a frequency table, weights and a window, without a GPU; returns (H, W, S, L,
+    frequencies f32, weights f32 or None, (tau_min, tau_max))"""
     from .films.phasor_hdr_film import PhasorHDRFilm
-    who = "phasor_backproject"
     H, W, S, L = _checked_geometry(who, g)
     if not np.isfinite(np.float32(g.start_opl)):
         raise ValueError(f"{who}: start_opl must be finite, got {g.start_opl}")
@@ -488,16 +489,6 @@ def _checked_phasor_call(shape, is_complex, g, frequencies, weights, window, vol
     F = int(freq.size)
     if F == 0 or not np.all(np.isfinite(freq)):
         raise ValueError(f"{who}: frequencies is a PhasorHDRFilm or a sequence of F >= 1 finite floats")
-    shape = tuple(int(v) for v in shape)
-    if not is_complex:
-        if len(shape) < 1 or shape[-1] != 2:
-            raise ValueError(f"{who}: real phasors end in a (Re, Im) axis of 2, got {shape}; pass a complex tensor otherwise")
-        shape = shape[:-1]
-    if len(shape) not in (3, 5):
-        raise ValueError(f"{who}: phasors are (H, W, F[, 2]), an exhaustive capture (H, W, Lx, Ly, F[, 2]); got {shape}")
-    f_axis = _checked_rows(who, shape + (2,), g, H, W, L, ("(H, W, F[, 2])", "(H, W, Lx, Ly, F[, 2])"))      # (the frequency axis is the last)
-    if shape[f_axis] != F:
-        raise ValueError(f"{who}: the phasors have {shape[f_axis]} frequencies, the table {F}")
     if isinstance(weights, str):
         if weights != "gaussian":
             raise ValueError(f"{who}: weights must be None, an (F,) array or 'gaussian', not {weights!r}")
@@ -522,8 +513,101 @@ def _checked_phasor_call(shape, is_complex, g, frequencies, weights, window, vol
         win = tuple(float(v) for v in np.asarray(window, dtype=np.float64).reshape(-1))
         if len(win) != 2 or not win[0] <= win[1]:
             raise ValueError(f"{who}: window is (lo, hi) with lo <= hi, got {window!r}")
+    return H, W, S, L, freq, w, win
+
+
+def _checked_phasor_call(shape, is_complex, g, frequencies, weights, window, volume_min, volume_max, resolution, who="phasor_backproject"):
+    """Everything ``phasor_backproject`` can refuse without a GPU; returns (S, L, frequencies f32, weights f32 or None,
+    (tau_min, tau_max), vmin, vmax, (nx, ny, nz))"""
+    H, W, S, L, freq, w, win = _checked_phasor_setup(who, g, frequencies, weights, window)
+    F = int(freq.size)
+    shape = tuple(int(v) for v in shape)
+    if not is_complex:
+        if len(shape) < 1 or shape[-1] != 2:
+            raise ValueError(f"{who}: real phasors end in a (Re, Im) axis of 2, got {shape}; pass a complex tensor otherwise")
+        shape = shape[:-1]
+    if len(shape) not in (3, 5):
+        raise ValueError(f"{who}: phasors are (H, W, F[, 2]), an exhaustive capture (H, W, Lx, Ly, F[, 2]); got {shape}")
+    f_axis = _checked_rows(who, shape + (2,), g, H, W, L, ("(H, W, F[, 2])", "(H, W, Lx, Ly, F[, 2])"))      # (the frequency axis is the last)
+    if shape[f_axis] != F:
+        raise ValueError(f"{who}: the phasors have {shape[f_axis]} frequencies, the table {F}")
     vmin, vmax, res = _checked_box(who, volume_min, volume_max, resolution)
     return S, L, freq, w, win, vmin, vmax, res
+
+
+class _PhasorProjection:
+    """One geometry, one frequency table and one volume box on the device: what ``mtr_phasor_backproject`` and
+    ``mtr_phasor_forward_project`` share in a call and in the autograd graph of a call.  ``run(entry, src)`` launches either on
+    a contiguous f32 CUDA tensor of (Re, Im) pairs."""
+
+    def __init__(self, ctx, g, S, L, freq, w, win, vmin, vmax, res, phasor_shape):
+        import torch
+        self.ctx, self.dev = ctx, torch.device("cuda", ctx.device_index)
+
+        def dev_f32(a):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.dev)
+        # (the six arrays live as long as this object: a graph that holds it can run its backward later)
+        self.arrays = (dev_f32(g.sensor_points.reshape(-1, 3)), dev_f32(g.laser_points), dev_f32(g.sensor_offset.reshape(-1)),
+                       dev_f32(g.laser_offset), dev_f32(freq), dev_f32(w) if w is not None else None)
+        d = self.desc = _cabi.mtr_phasor_backproject_desc()
+        d.capture_type, d.n_sensor, d.n_laser, d.n_freq = g.capture_type, S, L, int(freq.size)
+        d.start_opl, d.freq_step = np.float32(g.start_opl), np.float32(uniform_frequency_step(freq))
+        d.tau_min, d.tau_max = np.float32(win[0]), np.float32(win[1])
+        for k in range(3):
+            d.volume_min[k], d.volume_max[k] = np.float32(vmin[k]), np.float32(vmax[k])
+        d.nx, d.ny, d.nz = res
+        d.sensor_points, d.laser_points, d.sensor_offset, d.laser_offset, d.frequencies = (t.data_ptr() for t in self.arrays[:5])
+        d.weights = self.arrays[5].data_ptr() if w is not None else None
+        self.shapes = {"mtr_phasor_backproject": (res[2], res[1], res[0], 2), "mtr_phasor_forward_project": tuple(phasor_shape) + (2,)}
+
+    def run(self, entry, src):
+        import torch
+        src = src.to(device=self.dev, dtype=torch.float32).contiguous()
+        other = "mtr_phasor_forward_project" if entry == "mtr_phasor_backproject" else "mtr_phasor_backproject"
+        if tuple(src.shape) != self.shapes[other]:
+            raise ValueError(f"{entry}: the input has shape {tuple(src.shape)}, {self.shapes[other]} is expected")
+        out = torch.empty(self.shapes[entry], dtype=torch.float32, device=self.dev)
+        with torch.cuda.device(self.dev):
+            self.ctx.bind_current_stream()
+            self.ctx.check(getattr(self.ctx.lib, entry)(self.ctx.handle, C.byref(self.desc), C.c_void_p(src.data_ptr()),
+                                                        C.c_void_p(out.data_ptr())), entry)
+        # (src is released to torch's caching allocator, which hands it out again in stream order)
+        return out
+
+
+_phasor_functions = None
+
+
+def _phasor_autograd_pair():
+    """(PhasorBackproject, PhasorForwardProject): the two kernels as torch.autograd.Functions on (Re, Im) pairs, each the other's
+    backward.  The operators are conjugate transposes of one another (csrc/mtr_phasor_forward_project.h), and on the real view
+    the transpose of a complex-linear map A is the real view of A^H: the views around them carry torch's complex convention."""
+    global _phasor_functions
+    if _phasor_functions is None:
+        import torch
+
+        class PhasorBackproject(torch.autograd.Function):
+            @staticmethod
+            def forward(fctx, phasors, projection):
+                fctx.projection = projection
+                return projection.run("mtr_phasor_backproject", phasors)
+
+            @staticmethod
+            def backward(fctx, grad_volume):
+                return PhasorForwardProject.apply(grad_volume, fctx.projection), None
+
+        class PhasorForwardProject(torch.autograd.Function):
+            @staticmethod
+            def forward(fctx, volume, projection):
+                fctx.projection = projection
+                return projection.run("mtr_phasor_forward_project", volume)
+
+            @staticmethod
+            def backward(fctx, grad_phasors):
+                return PhasorBackproject.apply(grad_phasors, fctx.projection), None
+
+        _phasor_functions = (PhasorBackproject, PhasorForwardProject)
+    return _phasor_functions
 
 
 def phasor_backproject(phasors, geometry, frequencies, volume_min, volume_max, resolution, weights=None, window=None):
@@ -542,8 +626,14 @@ def phasor_backproject(phasors, geometry, frequencies, volume_min, volume_max, r
     Voxel ``v`` receives ``sum over (s, l) in the window, sum over k, of w_k P[s, l, k] exp(+i 2 pi f_k tau)`` with
     ``tau = |P_s - v| + |v - P_l| + offsets - start_opl``.  A uniformly spaced table (:func:`uniform_frequency_step`) is walked
     by rotation between every 16th frequency; any other table evaluates every term.  Returns a ``complex64`` CUDA tensor
-    (nz, ny, nx) without a graph; the sum has a fixed order, the same call gives the same bits.  Shape, geometry and
-    frequency-count mismatches raise ``ValueError`` before the GPU is touched."""
+    (nz, ny, nx); the sum has a fixed order, the same call gives the same bits.  Shape, geometry and frequency-count mismatches
+    raise ``ValueError`` before the GPU is touched.
+
+    Autograd: a torch tensor that requires grad, complex (..., F) or the real view (..., F, 2), with grad enabled, gives a volume
+    with a ``grad_fn`` — the backward pass is :func:`phasor_forward_project`, the conjugate transpose, and the gradient lands on
+    the tensor that was handed in (the complex / real views are torch ops of the graph).  Any other input takes the same path
+    as ever, gives the same bits and carries no graph.  The gradient of a ``phasor_hdr_film`` *render* on the NLOS tier is not
+    offered: the chain from a phasor volume to a scene parameter stops at the phasors."""
     from .tensor import TensorXf
     if isinstance(phasors, TensorXf):
         phasors = phasors.torch()
@@ -556,31 +646,123 @@ def phasor_backproject(phasors, geometry, frequencies, volume_min, volume_max, r
     from .runtime import get_context
     ctx = get_context()
     import torch
-    dev = torch.device("cuda", ctx.device_index)
-    t = phasors if isinstance(phasors, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(phasors))
-    t = t.detach().to(device=dev)
+    t, wanted = _as_tensor(phasors)
+    projection = _PhasorProjection(ctx, g, S, L, freq, w, win, vmin, vmax, res, tuple(t.shape[:-1] if not is_complex else t.shape))
+    t = t.to(device=projection.dev)
     if is_complex:
         t = torch.view_as_real(t.resolve_conj())
     t = t.to(dtype=torch.float32).contiguous()
-
-    def dev_f32(a):
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-    sp, lp = dev_f32(g.sensor_points.reshape(-1, 3)), dev_f32(g.laser_points)
-    so, lo = dev_f32(g.sensor_offset.reshape(-1)), dev_f32(g.laser_offset)
-    fr, wt = dev_f32(freq), (dev_f32(w) if w is not None else None)
-    volume = torch.empty((res[2], res[1], res[0], 2), dtype=torch.float32, device=dev)
-    d = _cabi.mtr_phasor_backproject_desc()
-    d.capture_type, d.n_sensor, d.n_laser, d.n_freq = g.capture_type, S, L, int(freq.size)
-    d.start_opl, d.freq_step = np.float32(g.start_opl), np.float32(uniform_frequency_step(freq))
-    d.tau_min, d.tau_max = np.float32(win[0]), np.float32(win[1])
-    for k in range(3):
-        d.volume_min[k], d.volume_max[k] = np.float32(vmin[k]), np.float32(vmax[k])
-    d.nx, d.ny, d.nz = res
-    d.sensor_points, d.laser_points, d.sensor_offset, d.laser_offset = sp.data_ptr(), lp.data_ptr(), so.data_ptr(), lo.data_ptr()
-    d.frequencies, d.weights = fr.data_ptr(), (wt.data_ptr() if wt is not None else None)
-    with torch.cuda.device(dev):
-        ctx.bind_current_stream()
-        ctx.check(ctx.lib.mtr_phasor_backproject(ctx.handle, C.byref(d), C.c_void_p(t.data_ptr()), C.c_void_p(volume.data_ptr())),
-                  "mtr_phasor_backproject")
-    # (t, sp .. wt are released to torch's caching allocator, which hands them out again in stream order)
+    volume = _phasor_autograd_pair()[0].apply(t, projection) if wanted else projection.run("mtr_phasor_backproject", t)
     return torch.view_as_complex(volume)
+
+
+def phasor_forward_project(volume, geometry, frequencies, volume_min, volume_max, weights=None, window=None):
+    """The conjugate transpose of :func:`phasor_backproject`: the phasors a complex volume of the hidden scene would produce, on
+    the GPU (``mtr_phasor_forward_project``) — the forward model of a phasor-field reconstruction, its gradient, and the other
+    half of :func:`phasor_reconstruct_cgls`.
+
+    ``volume``: complex (nz, ny, nx), real (nz, ny, nx, 2) with a (Re, Im) axis, or real (nz, ny, nx) (an albedo volume, zero
+    imaginary part); a torch tensor on any device, a numpy array or a ``TensorXf``.  The resolution is its shape, the box
+    ``volume_min`` .. ``volume_max``.  ``frequencies``, ``weights`` and ``window`` exactly as in :func:`phasor_backproject`.
+    Element ``(s, l, k)`` receives ``w_k sum over the voxels v in the window of U(v) exp(-i 2 pi f_k tau)`` — for a real
+    non-negative volume the film's own convention, the phasors of a volume of scatterers without cosines and 1/r^2.  The factors
+    are the conjugates of the ones ``phasor_backproject`` multiplies by, bit for bit, so that with the same arguments
+    ``<phasor_backproject(y), x> = <y, phasor_forward_project(x)>`` up to f32 rounding.  Returns a ``complex64`` CUDA tensor
+    (H, W, F); for an Exhaustive geometry (H, W, Lx, Ly, F) with (Lx, Ly) = ``geometry.laser_grid``.  The sums have a fixed order,
+    the same call gives the same bits.
+
+    Autograd: a volume that requires grad gives phasors with a ``grad_fn`` whose backward is ``phasor_backproject``; a real
+    volume receives the real part of the gradient.  Refusals are ``ValueError`` before the GPU is touched."""
+    who = "phasor_forward_project"
+    from .tensor import TensorXf
+    if isinstance(volume, TensorXf):
+        volume = volume.torch()
+    if not hasattr(volume, "shape"):
+        volume = np.asarray(volume)
+    is_complex = volume.is_complex() if hasattr(volume, "is_complex") else np.iscomplexobj(volume)
+    g = geometry
+    H, W, S, L, freq, w, win = _checked_phasor_setup(who, g, frequencies, weights, window)
+    shape = tuple(int(v) for v in volume.shape)
+    pairs = len(shape) == 4 and not is_complex
+    if pairs and shape[-1] != 2:
+        raise ValueError(f"{who}: a real 4-d volume ends in a (Re, Im) axis of 2, got {shape}")
+    if len(shape) != (4 if pairs else 3) or min(shape) <= 0:
+        raise ValueError(f"{who}: a complex or real (nz, ny, nx) or a real (nz, ny, nx, 2) volume is expected, got shape {shape}")
+    if g.capture_type == _cabi.MTR_CAPTURE_EXHAUSTIVE:
+        grid = g.laser_grid
+        if grid is None:
+            raise ValueError(f"{who}: an exhaustive geometry needs laser_grid = (Lx, Ly) to shape the phasors")
+        grid = tuple(int(v) for v in grid)
+        if len(grid) != 2 or grid[0] * grid[1] != L:
+            raise ValueError(f"{who}: laser_grid {grid} does not match the geometry's {L} laser points")
+        phasor_shape = (H, W, grid[0], grid[1], int(freq.size))
+    else:
+        phasor_shape = (H, W, int(freq.size))
+    vmin, vmax, res = _checked_box(who, volume_min, volume_max, (shape[2], shape[1], shape[0]))
+    from .runtime import get_context
+    ctx = get_context()
+    import torch
+    t, wanted = _as_tensor(volume)
+    projection = _PhasorProjection(ctx, g, S, L, freq, w, win, vmin, vmax, res, phasor_shape)
+    t = t.to(device=projection.dev)
+    if is_complex:
+        t = torch.view_as_real(t.resolve_conj())
+    elif not pairs:
+        t = torch.stack((t, torch.zeros_like(t)), dim=-1)
+    t = t.to(dtype=torch.float32).contiguous()
+    out = _phasor_autograd_pair()[1].apply(t, projection) if wanted else projection.run("mtr_phasor_forward_project", t)
+    return torch.view_as_complex(out)
+
+
+def phasor_reconstruct_cgls(phasors, geometry, frequencies, volume_min, volume_max, resolution, iterations=10, weights=None, window=None):
+    """Fit a complex hidden volume to measured phasors: CGLS on ``min |phasor_forward_project(x) - y|`` from ``x = 0``, one
+    ``phasor_forward_project`` and one ``phasor_backproject`` per iteration on the GPU, the rest torch ops (the inner products
+    are accumulated in float64).
+
+    ``phasors``, ``frequencies``, ``weights`` and ``window`` as in :func:`phasor_backproject`.  Returns ``(volume, residuals)``:
+    the ``complex64`` CUDA volume (nz, ny, nx) after ``iterations`` steps and ``residuals[k] = |r_k| / |y|`` as Python floats,
+    ``k = 0 .. iterations`` (``residuals[0] = 1``).  The result carries no graph.  Phasors that are all zero return a zero
+    volume.  Regularised solvers are out of scope."""
+    who = "phasor_reconstruct_cgls"
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 1:
+        raise ValueError(f"{who}: iterations is a positive int, got {iterations!r}")
+    from .tensor import TensorXf
+    if isinstance(phasors, TensorXf):
+        phasors = phasors.torch()
+    if not hasattr(phasors, "shape"):
+        phasors = np.asarray(phasors)
+    is_complex = phasors.is_complex() if hasattr(phasors, "is_complex") else np.iscomplexobj(phasors)
+    g = geometry
+    S, L, freq, w, win, vmin, vmax, res = _checked_phasor_call(phasors.shape, is_complex, g, frequencies, weights, window,
+                                                               volume_min, volume_max, resolution, who)
+    from .runtime import get_context
+    ctx = get_context()
+    import torch
+    with torch.no_grad():
+        y = _as_tensor(phasors)[0]
+        projection = _PhasorProjection(ctx, g, S, L, freq, w, win, vmin, vmax, res, tuple(y.shape[:-1] if not is_complex else y.shape))
+        y = y.to(device=projection.dev)
+        if is_complex:
+            y = torch.view_as_real(y.resolve_conj())
+        y = y.to(dtype=torch.float32).contiguous()
+
+        def dot(a):                                 # <a, a> of a complex tensor held as (Re, Im) pairs
+            return float(torch.sum(a.double() * a.double()))
+        r = y.clone()
+        s = projection.run("mtr_phasor_backproject", r)
+        x, p = torch.zeros_like(s), s.clone()
+        gamma, norm_y = dot(s), dot(y) ** 0.5
+        residuals = [1.0]
+        for _ in range(int(iterations)):
+            if gamma == 0.0:                        # (converged, or y = 0)
+                residuals.append(residuals[-1])
+                continue
+            q = projection.run("mtr_phasor_forward_project", p)
+            alpha = gamma / dot(q)
+            x += alpha * p
+            r -= alpha * q
+            s = projection.run("mtr_phasor_backproject", r)
+            gamma, last = dot(s), gamma
+            p = s + (gamma / last) * p
+            residuals.append(dot(r) ** 0.5 / norm_y)
+    return torch.view_as_complex(x), residuals
