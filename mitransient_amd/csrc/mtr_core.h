@@ -15,6 +15,9 @@
 // Numerics contract: IEEE f32, compiled with -ffp-contract=off, fmaf only
 // where written, correctly rounded 1/x and sqrtf, polynomial sin/cos.  The file is
 // plain C++ so tests can also compile it for the host (tests/host_harness.cpp).
+// "The same operations on host and device" is held function by function: mtr_kat.hip
+// evaluates the MTR_HD families below on the device, tests/test_gpu_kat.py compares
+// every word with the host build (safe_rcp alone differs, on purpose: see there).
 #pragma once
 #ifndef MTR_WIDE
 #define MTR_WIDE 8          // children per wide node (even, <= 16)
@@ -205,7 +208,8 @@ struct alignas(16) q4 { float x, y, z, w; };
 // two independent f32 values that one site evaluates side by side (two triangles of a leaf, two children of a node).
 // The pair is STRUCTURE; what it is lowered to is the template argument of the helpers: PK = one packed instruction on a register pair
 // (v_pk_fma_f32, v_pk_mul_f32, ...), !PK = two plain f32 instructions.  Either form rounds the same (-ffp-contract=off: an fma only
-// where the source says fmaf), so results do not depend on it.  The host has the plain form only.
+// where the source says fmaf), so results do not depend on it (tests/test_gpu_kat.py, family `pairs`: both forms against the host's
+// on the device, under either flag set of the Makefile, specials in either half).  The host has the plain form only.
 // MTR_PAIR_SCALAR, given to a translation unit on its command line, chooses the plain form per family of sites (a mask; 0 when absent:
 // every site packed).  A file built with the SLP vectoriser gets plain pairs packed again by the compiler, so there the mask
 // means something only together with -fno-slp-vectorize (Makefile: KFLAGS, mtr_kernels.hip alone).
@@ -560,6 +564,8 @@ struct Ray { f3 o, d; float tmax; };
 // reciprocal direction of the slab tests.  It only feeds CULLING (conservative: padded boxes, hits are decided by the
 // primitive tests alone), so the device takes the hardware reciprocal (v_rcp_f32, 1 ulp) instead of the ~10-instruction
 // correctly rounded division: an error of 6e-8 * t in an entry / exit distance is far inside the boxes' padding (2e-5 relative).
+// The ONE function of this file whose device result is not the host's bit for bit (tests/test_gpu_kat.py: within one ulp; a result
+// below FLT_MIN, |x| > 8.5e37, comes back as zero).
 MTR_HD float safe_rcp(float x)
 {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -6,6 +6,7 @@
 #include "../mitransient_amd/csrc/mtr_core.h"
 #include "../mitransient_amd/csrc/mtr_scene_host.h"
 #include "../mitransient_amd/csrc/mtr_nlos.h"
+#include "../mitransient_amd/csrc/mtr_kat.h"
 
 #include <algorithm>
 #include <cmath>
@@ -283,6 +284,20 @@ extern "C" void hh_bsdf_sample(const mtr_material *m, uint32_t n, const float *w
         w3[3 * i] = bs.w.x; w3[3 * i + 1] = bs.w.y; w3[3 * i + 2] = bs.w.z;
     }
 }
+
+// the host twins of the device known-answer harness (mitransient_amd/csrc/mtr_kat.hip, tests/test_gpu_kat.py): plain loops over the
+// same mtr_core.h functions, element by element in the array layout of mtr_kat.h (hh_special, hh_angular_falloff and hh_bsdf_*
+// above are the twins of their families)
+extern "C" void hh_trig(int which, uint64_t n, const uint32_t *in, uint32_t *out) { for (uint64_t i = 0; i < n; ++i) kat::trig(which, n, i, in, out); }
+extern "C" void hh_warps(int which, uint64_t n, const uint32_t *in, uint32_t *out) { for (uint64_t i = 0; i < n; ++i) kat::warps(which, n, i, in, out); }
+extern "C" void hh_fresnel(int which, uint64_t n, const uint32_t *in, uint32_t *out) { for (uint64_t i = 0; i < n; ++i) kat::fresnel(which, n, i, in, out); }
+extern "C" void hh_rng(uint64_t n, const uint32_t *in, uint32_t *out) { for (uint64_t i = 0; i < n; ++i) kat::rng(n, i, in, out); }
+extern "C" void hh_film(float start_opl, float bin_width, uint32_t tbins, uint32_t lasers, uint32_t n_freq, uint64_t n, const uint32_t *in, uint32_t *out)
+{
+    const Film f = kat::film_of(start_opl, bin_width, tbins, lasers, n_freq);
+    for (uint64_t i = 0; i < n; ++i) kat::film(f, n, i, in, out);
+}
+extern "C" void hh_pairs(uint64_t n, const uint32_t *in, uint32_t *out) { for (uint64_t i = 0; i < n; ++i) kat::pairs(n, i, in, out); }
 
 // debugging aid: prints the 8-wide tree of a scene (child counts, leaf / inner refs, walk axis)
 extern "C" int hh_print_wide(const mtr_scene_desc *d)
