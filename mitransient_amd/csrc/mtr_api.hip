@@ -476,6 +476,15 @@ int mtr_scene_shadow_hull(const mtr_scene *s, uint32_t *n_hull_rectangles)
     return MTR_OK;
 }
 
+// test hook, outside the C ABI of include/mitransient_amd.h (declared in mtr_kernels.h): the scene's device tables and its SHADOW HULL
+// block as classify_scene left it, for mtr_walk_kat.hip — struct mtr_scene is private to this file
+int mtr_test_scene_dev(const mtr_scene *s, SceneDev *dev, ShadowHull *hull)
+{
+    if (!s || !dev || !hull) return MTR_ERR_INVALID;
+    *dev = s->dev; *hull = s->hull;
+    return MTR_OK;
+}
+
 } // extern "C"
 
 // ---- MTR_MODE_WAVEFRONT: host loop over tiles and bounces ------------------------------------

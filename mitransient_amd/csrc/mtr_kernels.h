@@ -291,3 +291,10 @@ extern "C" uint32_t mtr_test_fused_chunk(uint32_t n_pixels, uint32_t spp_chunk, 
 extern "C" uint32_t mtr_test_fused_chunk_cap(uint32_t chunk, uint32_t spp_chunk);
 extern "C" void mtr_test_start_blocks(uint32_t n_lanes, uint32_t grid, uint32_t wg, uint32_t wave, uint32_t entry, uint32_t base, uint32_t *out);
 extern "C" int mtr_test_start_blocks_sweep(uint32_t n_lo, uint32_t n_hi, uint32_t g_lo, uint32_t g_hi);
+// the device ray-query harness of the walkers (mtr_walk_kat.hip, one hook per flag set; forms and error codes there) and the accessor
+// it reads a scene through (mtr_api.hip)
+extern "C" int mtr_test_scene_dev(const mtr_scene *s, mtr::SceneDev *dev, mtr::ShadowHull *hull);
+extern "C" int mtr_test_dev_walk(const mtr_scene *scene, uint32_t form, uint64_t n, const float *o3, const float *d3, const float *tmax,
+                                 uint32_t *hit4, uint8_t *occ);
+extern "C" int mtr_test_dev_walk_k(const mtr_scene *scene, uint32_t form, uint64_t n, const float *o3, const float *d3, const float *tmax,
+                                   uint32_t *hit4, uint8_t *occ);

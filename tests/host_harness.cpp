@@ -245,6 +245,75 @@ extern "C" int hh_intersect(const mtr_scene_desc *d, uint32_t n, const float *o3
     return 0;
 }
 
+// the host twin of the device ray-query harness (mitransient_amd/csrc/mtr_walk_kat.hip, tests/test_gpu_walk.py): hh_intersect's rays
+// through the tree hh_set_node_pairs / hh_set_wide select, with everything the closest-hit walk returns — hit4 = (t, u, v bits, the
+// raw slot; 0xffffffff for none), the original index (-1 for none) — and the any-hit walk's flag
+extern "C" int hh_walk(const mtr_scene_desc *d, uint32_t n, const float *o3, const float *d3, const float *maxt,
+                       uint32_t *hit4, int32_t *orig_out, uint8_t *occ_out)
+{
+    HostScene hs;
+    if (derive_scene(*d, hs)) return -1;
+    SceneView sv{};
+    sv.nodes = hs.nodes.data(); sv.tpairs = hs.tpairs.data(); sv.tshade = hs.tshade.data();
+    sv.node_pairs = g_node_pairs;
+    sv.wnodes = (g_wide == 1 && hs.has_wide && !hs.wnodes.empty()) ? hs.wnodes.data() : nullptr;
+    sv.wnodes4 = (g_wide == 2 && !hs.wnodes4.empty()) ? hs.wnodes4.data() : nullptr;
+    sv.wnodes8q = (g_wide == 3 && !hs.wnodes8q.empty()) ? hs.wnodes8q.data() : nullptr;
+    sv.mats = hs.mats.data(); sv.ems = hs.ems.data();
+    sv.n_emitters = (uint32_t)hs.ems.size(); sv.n_slots = (uint32_t)hs.tshade.size();
+    ArrStack st; st.sp = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const f3 o = mk(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), dd = mk(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]);
+        const float mt = maxt ? maxt[i] : kInf;
+        const Hit h = traverse<false>(sv, o, dd, mt, st);
+        hit4[4 * i] = fbits(h.t); hit4[4 * i + 1] = fbits(h.u); hit4[4 * i + 2] = fbits(h.v); hit4[4 * i + 3] = (uint32_t)h.prim;
+        orig_out[i] = h.prim >= 0 ? (int32_t)hs.slot_orig[h.prim] : -1;
+        const Hit a = traverse<true>(sv, o, dd, mt, st);
+        occ_out[i] = a.prim >= 0;
+    }
+    return 0;
+}
+// ... and of its shadow forms: the ray of (sp, gn, u1, u2) is built as shade_hit builds it — ep = rect_emitter_point(E, u1, u2) on the
+// scene's first emitter, shadow_ray_to(sp, gn, ep) — and walked like hh_walk's; ray7 receives (o, d, tmax) of every ray
+extern "C" int hh_walk_shadow(const mtr_scene_desc *d, uint32_t n, const float *sp3, const float *gn3, const float *u2,
+                              float *ray7, uint32_t *hit4, int32_t *orig_out, uint8_t *occ_out)
+{
+    HostScene hs;
+    if (derive_scene(*d, hs)) return -1;
+    if (hs.ems.empty() || hs.ems[0].kind != kEmRect) return -2;
+    const Emitter E = hs.ems[0];
+    std::vector<float> o3(3 * (size_t)n), d3(3 * (size_t)n), mt(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const Ray r = shadow_ray_to(mk(sp3[3 * i], sp3[3 * i + 1], sp3[3 * i + 2]), mk(gn3[3 * i], gn3[3 * i + 1], gn3[3 * i + 2]),
+                                    rect_emitter_point(E, u2[2 * i], u2[2 * i + 1]));
+        o3[3 * i] = r.o.x; o3[3 * i + 1] = r.o.y; o3[3 * i + 2] = r.o.z; d3[3 * i] = r.d.x; d3[3 * i + 1] = r.d.y; d3[3 * i + 2] = r.d.z; mt[i] = r.tmax;
+        float *q = ray7 + 7 * (size_t)i;
+        q[0] = r.o.x; q[1] = r.o.y; q[2] = r.o.z; q[3] = r.d.x; q[4] = r.d.y; q[5] = r.d.z; q[6] = r.tmax;
+    }
+    return hh_walk(d, n, o3.data(), d3.data(), mt.data(), hit4, orig_out, occ_out);
+}
+// the scene's SHADOW HULL block as classify_scene leaves it (mtr_shadow_hull.h: 48 words), its trait word, and the sizes of its four trees
+// (BVH2 packets, 8-wide, quantised 4-wide, quantised 8-wide nodes) followed by whether the 8-wide tree is one a kernel stages in LDS
+extern "C" int hh_walk_scene_info(const mtr_scene_desc *d, uint32_t *hull48, uint32_t *traits, uint32_t *sizes5)
+{
+    HostScene hs;
+    if (derive_scene(*d, hs)) return -1;
+    static_assert(sizeof(ShadowHull) == 48 * 4, "the block as words");
+    memcpy(hull48, &hs.hull, sizeof(ShadowHull));
+    *traits = hs.traits;
+    sizes5[0] = (uint32_t)hs.nodes.size(); sizes5[1] = (uint32_t)hs.wnodes.size(); sizes5[2] = (uint32_t)hs.wnodes4.size();
+    sizes5[3] = (uint32_t)hs.wnodes8q.size(); sizes5[4] = hs.has_wide ? 1u : 0u;
+    return 0;
+}
+// the slot -> original index table of a scene (n_slots entries; returns n_slots, or -1): a device hit's slot as an original index
+extern "C" int hh_slot_orig(const mtr_scene_desc *d, uint32_t cap, uint32_t *out)
+{
+    HostScene hs;
+    if (derive_scene(*d, hs)) return -1;
+    for (size_t i = 0; i < hs.slot_orig.size() && i < cap; ++i) out[i] = hs.slot_orig[i];
+    return (int)hs.slot_orig.size();
+}
+
 // the product's restatements of exp / log / erf / erfinv (Beckmann lobes): which = 0 exp, 1 log, 2 erf, 3 erfinv
 extern "C" void hh_special(int which, uint64_t n, const float *x, float *y)
 {
