@@ -739,6 +739,36 @@ int  mtr_phasor_backproject(mtr_ctx *, const mtr_phasor_backproject_desc *, cons
  * refuses, more than 2^31 - 1 voxels, rows or (row, block of 16 frequencies) pairs. */
 int  mtr_phasor_forward_project(mtr_ctx *, const mtr_phasor_backproject_desc *, const float *volume_dev, float *phasors_dev);
 
+/* f-k migration of a confocal capture of a planar wall (Lindell et al. 2019): the three passes around the caller's two FFTs
+ * (additive, ABI 24: three new entry points and a new struct; MTR_ABI_VERSION stays 24).  With T' = depth_bins, q = bin_factor:
+ *   mtr_fk_prepare  capture (H, W, T) f32 and shift (H, W) int32 -> padded (2H, 2W, 2T') f32, EVERY element stored (no memset
+ *                   is needed before it).  In the low corner padded[y, x, k] = sqrt(max(S, 0)) ((k + 1/2) / T') with
+ *                   S = sum over j = kq .. kq + q - 1 of capture[y, x, j - shift[y, x]], terms outside [0, T) dropped, added in
+ *                   f32 in increasing j; zero elsewhere.
+ *   mtr_fk_stolt    spectrum (2H, 2W, T' + 1) complex64 — the real-to-complex transform of `padded` over its three axes, depth
+ *                   last — -> resampled (2H, 2W, 2T') complex64, EVERY element stored.  With signed FFT indices my in [-H, H),
+ *                   mx in [-W, W), mz in [-T', T') and ky = my / H, kx = mx / W, kz = mz / T': for kz > 0,
+ *                   k' = sqrt((ax kx)^2 + (ay ky)^2 + kz^2), p = k' T', i0 = floor(p), w = p - i0 and
+ *                   resampled = ((1 - w) spectrum[iy, ix, i0] + w spectrum[iy, ix, i0 + 1]) (kz / k') when i0 + 1 <= T';
+ *                   zero otherwise, and for kz <= 0.  ax, ay: the depth spacing over the scan spacing along x and y.
+ *   mtr_fk_finish   field (2H, 2W, 2T') complex64 — the inverse complex transform of `resampled` — -> volume (nz, H, W) f32,
+ *                   volume[iz, iy, ix] = |field[iy, ix, z_begin + iz]|^2.
+ * f32 arithmetic in a fixed order and no sums across threads: the same call gives the same bits.  All pointers are device
+ * pointers (contiguous, 16-byte aligned, or MTR_ERR_INVALID).  Each runs on the context's stream and does not synchronise it.
+ * MTR_ERR_INVALID before any launch, the output untouched: a NULL pointer, height or width below 2 or above 32767, a zero size,
+ * bin_factor 0, z_begin + nz > depth_bins, ax or ay not positive and finite. */
+typedef struct mtr_fk_desc {
+    uint32_t height, width;         /* H, W: the scan grid                            */
+    uint32_t temporal_bins;         /* T                                              */
+    uint32_t bin_factor;            /* q                                              */
+    uint32_t depth_bins;            /* T'                                             */
+    uint32_t z_begin, nz;           /* the depth rows mtr_fk_finish keeps             */
+    float    ax, ay;
+} mtr_fk_desc;
+int  mtr_fk_prepare(mtr_ctx *, const mtr_fk_desc *, const float *capture_dev, const int32_t *shift_dev, float *padded_dev);
+int  mtr_fk_stolt(mtr_ctx *, const mtr_fk_desc *, const float *spectrum_dev, float *resampled_dev);
+int  mtr_fk_finish(mtr_ctx *, const mtr_fk_desc *, const float *field_dev, float *volume_dev);
+
 /* Release the device workspaces the context keeps between calls (ABI 10: the partition workspace of mtr_splat_add on
  * unsorted input — 32 bytes per contribution; a workspace above 256 MiB is released by the call itself, a smaller one
  * stays with the context; ABI 24: the slabs' rows of MTR_MODE_SAMPLES, under the same rule).  Synchronises the context's stream. */

@@ -121,6 +121,11 @@ class mtr_phasor_backproject_desc(C.Structure):          # (additive, ABI 24)
                 ("frequencies", C.c_void_p), ("weights", C.c_void_p)]
 
 
+class mtr_fk_desc(C.Structure):          # (additive, ABI 24)
+    _fields_ = [("height", C.c_uint32), ("width", C.c_uint32), ("temporal_bins", C.c_uint32), ("bin_factor", C.c_uint32),
+                ("depth_bins", C.c_uint32), ("z_begin", C.c_uint32), ("nz", C.c_uint32), ("ax", C.c_float), ("ay", C.c_float)]
+
+
 class mtr_scene_desc(C.Structure):
     _fields_ = [("n_tris", C.c_uint32),
                 ("tri_verts", C.POINTER(C.c_float)),
@@ -191,6 +196,7 @@ EXPORTS = [
     "mtr_scene_tint_layout", "mtr_scene_set_tints", "mtr_render_grad_tint", "mtr_render_fwd_tint",
     "mtr_scene_set_camera", "mtr_render_samples_plan",
     "mtr_backproject", "mtr_phasor_backproject", "mtr_forward_project", "mtr_phasor_forward_project",
+    "mtr_fk_prepare", "mtr_fk_stolt", "mtr_fk_finish",
 ]
 
 _lib = None
@@ -259,6 +265,9 @@ def load_library() -> C.CDLL:
     lib.mtr_phasor_backproject.argtypes = [vp, C.POINTER(mtr_phasor_backproject_desc), vp, vp]      # (additive, ABI 24)
     lib.mtr_forward_project.argtypes = [vp, C.POINTER(mtr_backproject_desc), vp, vp]      # (additive, ABI 24)
     lib.mtr_phasor_forward_project.argtypes = [vp, C.POINTER(mtr_phasor_backproject_desc), vp, vp]      # (additive, ABI 24)
+    lib.mtr_fk_prepare.argtypes = [vp, C.POINTER(mtr_fk_desc), vp, vp, vp]      # (additive, ABI 24)
+    lib.mtr_fk_stolt.argtypes = [vp, C.POINTER(mtr_fk_desc), vp, vp]
+    lib.mtr_fk_finish.argtypes = [vp, C.POINTER(mtr_fk_desc), vp, vp]
     if lib.mtr_abi_version() != MTR_ABI_VERSION:
         raise MitransientAMDError("libmitransient_amd.so ABI version mismatch; rebuild")
     _lib = lib

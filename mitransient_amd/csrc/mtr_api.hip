@@ -17,6 +17,7 @@
 #include "mtr_forward_project.h"
 #include "mtr_phasor_backproject.h"
 #include "mtr_phasor_forward_project.h"
+#include "mtr_fk.h"
 
 #include <hip/hip_runtime.h>
 #include <cassert>
@@ -1451,6 +1452,35 @@ int mtr_phasor_forward_project(mtr_ctx *c, const mtr_phasor_backproject_desc *d,
     if (const size_t n = pf_plane_floats(a, pl))
         if (int r = grow_device_buffer(c, &c->d_bp, &c->bp_cap, n * sizeof(float))) return r;
     HIP_TRY(c, launch_phasor_forward_project(a, pl, volume, (float *)c->d_bp, phasors, c->stream));
+    return MTR_OK;
+}
+
+int mtr_fk_prepare(mtr_ctx *c, const mtr_fk_desc *d, const float *capture, const int32_t *shift, float *padded)
+{
+    if (!c) return fail(nullptr, MTR_ERR_INVALID, "mtr_fk_prepare: ctx is NULL");
+    const char *why = fk_check(d, capture, padded);
+    if (!why && !shift) why = "NULL argument";
+    if (why) return fail(c, MTR_ERR_INVALID, std::string("mtr_fk_prepare: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_fk_prepare(fk_args(*d), capture, shift, padded, c->stream));
+    return MTR_OK;
+}
+
+int mtr_fk_stolt(mtr_ctx *c, const mtr_fk_desc *d, const float *spectrum, float *resampled)
+{
+    if (!c) return fail(nullptr, MTR_ERR_INVALID, "mtr_fk_stolt: ctx is NULL");
+    if (const char *why = fk_check(d, spectrum, resampled)) return fail(c, MTR_ERR_INVALID, std::string("mtr_fk_stolt: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_fk_stolt(fk_args(*d), spectrum, resampled, c->stream));
+    return MTR_OK;
+}
+
+int mtr_fk_finish(mtr_ctx *c, const mtr_fk_desc *d, const float *field, float *volume)
+{
+    if (!c) return fail(nullptr, MTR_ERR_INVALID, "mtr_fk_finish: ctx is NULL");
+    if (const char *why = fk_check(d, field, volume)) return fail(c, MTR_ERR_INVALID, std::string("mtr_fk_finish: ") + why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, launch_fk_finish(fk_args(*d), field, volume, c->stream));
     return MTR_OK;
 }
 

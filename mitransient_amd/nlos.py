@@ -7,7 +7,9 @@ transpose (``mtr_forward_project``, csrc/mtr_forward_project.hip): the two are e
 ``reconstruct_cgls`` iterates them to fit a volume to a capture.  ``phasor_backproject`` does the
 same for the phasors a ``phasor_hdr_film`` develops (``mtr_phasor_backproject``, csrc/mtr_phasor_backproject.hip), and
 ``phasor_forward_project`` is its conjugate transpose (``mtr_phasor_forward_project``, csrc/mtr_phasor_forward_project.hip): the
-same pairing in the frequency domain, with autograd and ``phasor_reconstruct_cgls``."""
+same pairing in the frequency domain, with autograd and ``phasor_reconstruct_cgls``.  ``fk_migration`` is the closed-form
+reconstruction of a confocal capture of a planar wall: two ``torch.fft`` transforms with three HIP passes around them
+(``mtr_fk_prepare`` / ``mtr_fk_stolt`` / ``mtr_fk_finish``, csrc/mtr_fk.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -329,8 +331,9 @@ def backproject(transient, geometry, volume_min, volume_max, resolution, interpo
     gives the same bits and carries no graph.
 
     A capture rendered in the frequency domain (``phasor_hdr_film``) is reconstructed by :func:`phasor_backproject`.
-    Out of scope: LCT / f-k migration, non-rectangular relay walls in ``capture_geometry`` (a hand-built ``CaptureGeometry``
-    takes any points).  Shape and geometry mismatches raise ``ValueError`` before the GPU is touched."""
+    A confocal capture of a planar wall also has the closed-form ``N^3 log N`` reconstruction of :func:`fk_migration`.
+    Out of scope: the light-cone transform (LCT), non-rectangular relay walls in ``capture_geometry`` (a hand-built
+    ``CaptureGeometry`` takes any points).  Shape and geometry mismatches raise ``ValueError`` before the GPU is touched."""
     from .tensor import TensorXf
     if isinstance(transient, TensorXf):
         transient = transient.torch()
@@ -766,3 +769,216 @@ def phasor_reconstruct_cgls(phasors, geometry, frequencies, volume_min, volume_m
             p = s + (gamma / last) * p
             residuals.append(dot(r) ** 0.5 / norm_y)
     return torch.view_as_complex(x), residuals
+
+
+# ---------------------------------------------------------------- f-k migration
+@dataclass
+class _FkPlan:
+    """What one ``fk_migration`` call computes on, all of it known without a GPU"""
+    H: int
+    W: int
+    T: int
+    q: int
+    depth_bins: int               # T'
+    z_begin: int
+    nz: int
+    ax: float
+    ay: float
+    dz: float                     # depth of one sample: q bin_width / 2
+    shift: np.ndarray             # (H, W) int32
+
+    def desc(self):
+        d = _cabi.mtr_fk_desc()
+        d.height, d.width, d.temporal_bins, d.bin_factor = self.H, self.W, self.T, self.q
+        d.depth_bins, d.z_begin, d.nz = self.depth_bins, self.z_begin, self.nz
+        d.ax, d.ay = np.float32(self.ax), np.float32(self.ay)
+        return d
+
+    def depths(self):
+        return (np.arange(self.z_begin, self.z_begin + self.nz, dtype=np.float64) + 0.5) * self.dz
+
+
+def _next_5_smooth(n):
+    """the smallest integer >= n whose prime factors are 2, 3 and 5 (sizes the FFT libraries have fast paths for)"""
+    n = max(int(n), 1)
+    best = 1
+    while best < n:
+        best *= 2
+    p5 = 1
+    while p5 < best:
+        p35 = p5
+        while p35 < best:
+            v = p35
+            while v < n:
+                v *= 2
+            best = min(best, v)
+            p35 *= 3
+        p5 *= 5
+    return best
+
+
+def _fk_plan(who, g, depth_range=None, bin_factor=1):
+    """Everything f-k migration can refuse in a geometry and its options without a GPU, and the grid it would run on"""
+    H, W, S, L = _checked_geometry(who, g)
+    if g.capture_type != _cabi.MTR_CAPTURE_CONFOCAL:
+        raise ValueError(f"{who}: f-k migration needs a confocal capture, this one is {_CAPTURE_NAMES[g.capture_type]} "
+                         "(backproject takes every capture type)")
+    if H < 2 or W < 2:
+        raise ValueError(f"{who}: the scan must be at least 2 x 2 points, got {H} x {W}")
+    T = int(g.temporal_bins)
+    if T <= 0:
+        raise ValueError(f"{who}: a capture of zero size")
+    bw = float(g.bin_width_opl)
+    if not (bw > 0.0 and np.isfinite(bw) and np.isfinite(g.start_opl)):
+        raise ValueError(f"{who}: bin_width_opl must be positive and start_opl finite, got {g.bin_width_opl} and {g.start_opl}")
+    if isinstance(bin_factor, bool) or not isinstance(bin_factor, (int, np.integer)):
+        raise ValueError(f"{who}: bin_factor must be an integer, got {bin_factor!r}")
+    q = int(bin_factor)
+    if q < 1:
+        raise ValueError(f"{who}: bin_factor must be at least 1, got {q}")
+    P = g.sensor_points
+    if not np.all(np.isfinite(P)):
+        raise ValueError(f"{who}: sensor_points must be finite")
+    ex, ey = P[0, 1] - P[0, 0], P[1, 0] - P[0, 0]
+    dx, dy = float(np.linalg.norm(ex)), float(np.linalg.norm(ey))
+    tol = 1e-6 * max(dx, dy)
+    grid = P[0, 0] + np.arange(W)[None, :, None] * ex + np.arange(H)[:, None, None] * ey
+    if not (dx > 0.0 and dy > 0.0) or float(np.max(np.linalg.norm(P - grid, axis=-1))) > tol or abs(float(ex @ ey)) > 1e-6 * dx * dy:
+        raise ValueError(f"{who}: the scan points must form an orthogonal affine grid P0 + x ex + y ey (a planar wall scanned in "
+                         "equal steps); backproject takes any points")
+    off = g.sensor_offset.reshape(H, W) + g.laser_offset.reshape(H, W)
+    if not np.all(np.isfinite(off)):
+        raise ValueError(f"{who}: the offsets must be finite")
+    shift = np.rint((float(g.start_opl) - off) / bw)
+    if float(np.max(np.abs(shift))) > 2.0 ** 30:
+        raise ValueError(f"{who}: the capture starts more than 2^30 bins from the wall")
+    zmin, zmax = 0.0, np.inf
+    if depth_range is not None:
+        try:
+            lo, hi = depth_range
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: depth_range is (zmin, zmax), got {depth_range!r}") from None
+        zmin = 0.0 if lo is None else float(lo)
+        zmax = np.inf if hi is None else float(hi)
+        if np.isnan(zmin) or np.isnan(zmax) or not zmax > zmin:
+            raise ValueError(f"{who}: an empty depth_range {depth_range!r}")
+        if not zmax > 0.0:
+            raise ValueError(f"{who}: depth_range {depth_range!r} lies behind the wall")
+    dz = q * bw / 2.0
+    n = -(-(T + max(int(shift.max()), 0)) // q)
+    if np.isfinite(zmax):
+        n = min(n, max(int(np.ceil(zmax / dz)), 1))
+    Tp = _next_5_smooth(n)
+    centres = (np.arange(Tp, dtype=np.float64) + 0.5) * dz
+    keep = np.nonzero((centres >= zmin) & (centres <= zmax))[0]
+    if keep.size == 0:
+        raise ValueError(f"{who}: no depth sample of the capture has its centre inside depth_range {depth_range!r} "
+                         f"(the samples are {dz} apart and end at {Tp * dz})")
+    if H > 0x7fff or W > 0x7fff or Tp > 0x3fffffff:
+        raise ValueError(f"{who}: the scan or the depth grid is too large for one call")
+    return _FkPlan(H, W, T, q, Tp, int(keep[0]), int(keep.size), dz / dx, dz / dy, dz, shift.astype(np.int32))
+
+
+def fk_depths(geometry, depth_range=None, bin_factor=1):
+    """The (nz,) depth centres, as float64 numpy, of the volume :func:`fk_migration` returns for the same arguments:
+    ``(k + 1/2) bin_factor bin_width_opl / 2`` for the depth samples ``k`` whose centres lie inside ``depth_range``."""
+    return _fk_plan("fk_depths", geometry, depth_range, bin_factor).depths()
+
+
+def fk_migration(transient, geometry, depth_range=None, bin_factor=1, channel=None):
+    """f-k migration (Lindell, Wetzstein, O'Toole 2019) of a confocal capture of a planar wall, on the GPU: the closed-form
+    ``N^3 log N`` reconstruction of the case whose direct sum (:func:`backproject`) costs ``H W nx ny nz``.
+
+    ``transient``: what ``mi.render`` returned (used where it lies, no host copy), a torch tensor or a numpy array, of shape
+    (H, W, T) or (H, W, T, C); channels are averaged unless ``channel=k`` picks one.  ``geometry``: a Confocal
+    :class:`CaptureGeometry` whose ``sensor_points`` form an orthogonal affine grid ``P0 + x ex + y ey`` (checked to 1e-6 of
+    the larger spacing), at least 2 x 2.
+
+    Time origin: bin ``b`` of scan point (y, x) is taken as wall-to-wall bin ``b + shift[y, x]`` with ``shift = round((start_opl -
+    sensor_offset - laser_offset) / bin_width_opl)``, an integer: the capture is moved by whole bins, never resampled.  The
+    residue is at most half a bin of path length, which is at most ``bin_width_opl / 4`` of depth.  ``bin_factor = q`` adds
+    ``q`` consecutive wall-to-wall bins before the migration (f32, in increasing order).
+
+    Returns a CUDA f32 tensor (nz, H, W): voxel (iz, iy, ix) sits at ``sensor_points[iy, ix] + n z`` with ``n`` the wall's
+    normal and ``z = fk_depths(...)[iz] = (k + 1/2) q bin_width_opl / 2`` — the method cannot tell the two sides of the wall apart
+    and does not need to.  The depth grid has ``T'`` samples, the next 5-smooth integer at or above ``ceil((T + max(shift, 0)) /
+    q)``; ``depth_range = (zmin, zmax)`` keeps the samples whose centres lie inside it (either end may be None), and a ``zmax``
+    also shortens ``T'`` to what covers it.  The steps: ``sqrt(max(S, 0)) (k + 1/2) / T'`` zero-padded to (2H, 2W, 2T')
+    (``mtr_fk_prepare``), ``torch.fft.rfftn``, the Stolt resampling with linear interpolation and the Jacobian ``kz / k'``
+    (``mtr_fk_stolt``), ``torch.fft.ifftn``, ``|.|^2`` of the low corner (``mtr_fk_finish``).  No atomics: the same call
+    gives the same bits.
+
+    Device memory: with ``N = 2H 2W 2T'``, the padded input (4N bytes) and its half spectrum (about 4N) are alive together, then
+    the half spectrum and the resampled spectrum (8N), then the resampled spectrum and the field (8N): 16N bytes at the peak,
+    plus the FFT's own workspace (up to the size of its output; where torch returns a transform with permuted strides, a
+    contiguous copy of it as well) and the (nz, H, W) volume.  A 256 x 256 x 4096 capture that
+    starts 3789 bins from the wall has ``T' = 2000`` with ``bin_factor=4`` and peaks near 16 GiB; with ``bin_factor=1``,
+    ``T' = 8000`` and 63 GiB.  ``depth_range=(None, zmax)`` is what shrinks it.
+
+    Not differentiable: a tensor that requires grad raises (detach it yourself if that is what you mean).  ``ValueError``
+    before the GPU is touched also for a geometry that is not a Confocal ``CaptureGeometry`` on such a grid, a shape or
+    ``temporal_bins`` mismatch, a ``bin_factor`` that is not an integer >= 1, and a ``depth_range`` that is empty or behind the
+    wall."""
+    who = "fk_migration"
+    from .tensor import TensorXf
+    if isinstance(transient, TensorXf):
+        transient = transient.torch()
+    if not hasattr(transient, "shape"):
+        transient = np.asarray(transient)
+    plan = _fk_plan(who, geometry, depth_range, bin_factor)
+    shape = tuple(int(v) for v in transient.shape)
+    if len(shape) not in (3, 4):
+        raise ValueError(f"{who}: a confocal capture is (H, W, T) or (H, W, T, C), got {shape}")
+    if shape[:2] != (plan.H, plan.W):
+        raise ValueError(f"{who}: the capture is {shape[0]} x {shape[1]} scan points, the geometry {plan.H} x {plan.W}")
+    if shape[2] != plan.T:
+        raise ValueError(f"{who}: the capture has {shape[2]} time bins, the geometry {plan.T}")
+    has_c = len(shape) == 4
+    if channel is not None:
+        if not has_c:
+            raise ValueError(f"{who}: channel= needs a capture with a channel axis")
+        if not 0 <= int(channel) < shape[-1]:
+            raise ValueError(f"{who}: channel {channel} is outside the capture's {shape[-1]} channels")
+    if has_c and shape[-1] == 0:
+        raise ValueError(f"{who}: a capture without channels")
+    if getattr(transient, "requires_grad", False):
+        raise ValueError(f"{who}: the capture requires grad, and f-k migration is not differentiable here; pass "
+                         "transient.detach() if the volume is all you want (backproject carries a graph)")
+
+    from .runtime import get_context
+    ctx = get_context()
+    import torch
+    dev = torch.device("cuda", ctx.device_index)
+    t = transient if isinstance(transient, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(transient))
+    t = t.to(device=dev, dtype=torch.float32)
+    if has_c:
+        t = t[..., int(channel)] if channel is not None else (t[..., 0] if t.shape[-1] == 1 else t.mean(dim=-1))
+    t = t.contiguous()
+    return _fk_run(ctx, plan, t)
+
+
+def _fk_run(ctx, plan, capture):
+    """the five steps of a planned call on a contiguous f32 CUDA (H, W, T) capture"""
+    import torch
+    dev = capture.device
+    H, W, Tp = plan.H, plan.W, plan.depth_bins
+    desc = plan.desc()
+    shift = torch.from_numpy(plan.shift).to(dev)
+
+    def launch(entry, *tensors):
+        ctx.bind_current_stream()
+        ctx.check(getattr(ctx.lib, entry)(ctx.handle, C.byref(desc), *(C.c_void_p(x.data_ptr()) for x in tensors)), entry)
+
+    with torch.cuda.device(dev), torch.no_grad():
+        padded = torch.empty((2 * H, 2 * W, 2 * Tp), dtype=torch.float32, device=dev)
+        launch("mtr_fk_prepare", capture, shift, padded)
+        spectrum = torch.fft.rfftn(padded).contiguous()       # (torch may hand a multi-axis transform back with permuted strides: then a copy)
+        del padded
+        resampled = torch.empty((2 * H, 2 * W, 2 * Tp), dtype=torch.complex64, device=dev)
+        launch("mtr_fk_stolt", spectrum, resampled)
+        del spectrum
+        field = torch.fft.ifftn(resampled).contiguous()
+        del resampled
+        volume = torch.empty((plan.nz, H, W), dtype=torch.float32, device=dev)
+        launch("mtr_fk_finish", field, volume)
+    return volume
